@@ -5,6 +5,13 @@ float32; achieved HBM GB/s vs roofline @1/2/4/8 GPU").
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks through torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W        (the driver's form: WORLD_SIZE must equal N)
+    python bench.py ... --full                  (also every context leg below: batch, configs[2], other engines and
+                                                 precisions, roofline probes, host API, CPU baseline, full record)
+    python bench.py ... --dump-outputs DIR      (after the timed steps: the last step's output as DIR/resampled.npy)
+
+A plain run (no --full) does what the headline needs and nothing else: plan, input, W warm-up launches, the K timed
+launches, the line.  Its `roofline.launch_us` is then the timed steps' own wall time per step; --full takes it from
+HIP-event windows around the timed region instead, and adds the legs described below.
 
 A "step" is one pass of the hot path (one hipsoxr_run_device launch) over one batch of synthetic
 input that is already resident in HBM.  Workload (config.workload):
@@ -799,6 +806,27 @@ def compact_line(result, budget=LINE_BUDGET):
     return line
 
 
+DUMP_BYTES = 63 * 10 ** 6   # --dump-outputs: under 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, y, rank, world, budget=DUMP_BYTES):
+    """--dump-outputs DIR: what the timed path handed back in its last step (the resampled clip, float32) as
+    DIR/resampled.npy; rank r > 0 of an N-GPU run writes DIR/resampled_rank<r>.npy.  An output larger than its share of
+    the budget (a long --seconds) is written as every s-th sample from the first on, s the smallest stride that fits:
+    the same positions in every run with the same arguments."""
+    import numpy as np
+    a = y.detach().cpu().numpy().reshape(-1)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float32)
+    stride = -(-a.nbytes // (budget // world))
+    if stride > 1:
+        a = np.ascontiguousarray(a[::stride])
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "resampled.npy" if rank == 0 else f"resampled_rank{rank}.npy")
+    np.save(path, a)
+    return path
+
+
 def write_full_record(result):
     path = os.environ.get("BENCH_FULL_JSON", os.path.join(ROOT, "gpurun_out", "bench_full.json"))
     try:
@@ -825,9 +853,16 @@ def main():
     ap.add_argument("--sustained-s", type=float, default=3.0, help="wall seconds of the sustained batch leg")
     ap.add_argument("--no-sustained", action="store_true")
     ap.add_argument("--kernels-only", action="store_true", help="device-kernel legs only (profiling target: no host API / stream / CPU / ceiling legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every context leg too (batch, configs[2], other engines and precisions, roofline probes, host API, "
+                         "CPU baseline) and write the full record; without it only the headline workload is timed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's output as DIR/resampled.npy (float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))     # N ranks, one per GPU; rank 0 of them prints the line
 
@@ -875,7 +910,11 @@ def main():
     g.manual_seed(1000 + rank)
     n_in = IN_RATE * args.seconds
     x = torch.randn(n_in, device=device, dtype=torch.float32, generator=g) * 0.25
-    wall, kern, y = time_workload(plan, x, args.steps, args.warmup, world, device, args.kernel, windows=args.windows)
+    # (a plain run: no HIP-event windows around the timed steps — launch_us is then the steps' own wall time per step)
+    wall, kern, y = time_workload(plan, x, args.steps, args.warmup, world, device, args.kernel,
+                                  windows=args.windows if args.full else 0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
     n_out = y.shape[0]
     algo_bytes = 4.0 * (n_in + n_out)
     flops = 2.0 * plan.taps * n_out
@@ -900,7 +939,17 @@ def main():
                      "algorithmic_bytes_per_launch": algo_bytes,
                      "valu_issue_frac": c1_valu / (VALU_SLOTS_PER_S * kern) if c1_valu else None,
                      "direct_form_equiv_tflops": flops / kern / 1e12, **c1_prov},
+        "full": args.full,
     }
+    if not args.full:   # a plain run ends here: the line, no context legs, no full record
+        if rank == 0:
+            result["cpu_baseline"] = None
+            result["ranks"] = rank_info
+            print(compact_line(result))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     if rank == 0 and fft_kernel and args.seconds == 60 and not args.no_sustained:
         # what bounds THIS line: one 22 MB buffer pair re-launched — it lives in the 256 MB Infinity Cache, and its 643
         # workgroups are a single round on 1024 slots: latency (launch floor + one workgroup's six passes), not HBM traffic.

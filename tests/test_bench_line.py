@@ -66,3 +66,28 @@ def test_contract_values_are_not_rounded_away():
     c = json.loads(b.compact_line(d))
     assert abs(c["value"] / d["value"] - 1) < 1e-4 and abs(c["ms_per_step"] / d["ms_per_step"] - 1) < 1e-4
     assert c["steps"] == d["steps"] and c["warmup"] == d["warmup"] and c["n_gpus"] == d["n_gpus"]
+
+
+def test_plain_run_options_are_there():
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stderr
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout
+
+
+def test_dump_outputs_writes_float32_within_budget(tmp_path):
+    import numpy as np
+    import torch
+    b = _bench()
+    y = torch.arange(10000, dtype=torch.float32)
+    path = b.dump_outputs(str(tmp_path), y, 0, 1)
+    assert os.path.basename(path) == "resampled.npy"
+    a = np.load(path)
+    assert a.dtype == np.float32 and np.array_equal(a, y.numpy())
+    # over the budget: a fixed stride from the first sample on, the same positions every time, within the budget
+    path = b.dump_outputs(str(tmp_path), y, 1, 2, budget=8000)
+    assert os.path.basename(path) == "resampled_rank1.npy"
+    a = np.load(path)
+    assert a.nbytes <= 8000 // 2 and np.array_equal(a, y.numpy()[::10])
+    assert b.DUMP_BYTES < 64 * 10 ** 6

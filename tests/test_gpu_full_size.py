@@ -168,3 +168,36 @@ def test_bench_two_ranks_harness():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 20 and d["scaling"] == "weak" and d["value"] > 0
     assert d["cpu_baseline"] is None and "roofline" in d
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_output(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: the headline workload alone, K timed steps, and with
+    --dump-outputs DIR the last step's output — the same from run to run, and what resample_tensor gives on that input."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    from soxr_amd import device as dev
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+        assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and "roofline" in d
+        assert not {"batch_shard", "configs2", "exact_engine", "hbm_ceiling", "host_api"} & set(d) and d["cpu_baseline"] is None
+        assert sorted(os.listdir(out)) == ["resampled.npy"]
+        dumps.append(np.load(out / "resampled.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (d["config"]["frames_out"],) and dumps[0].nbytes < 64 * 10 ** 6
+    assert np.array_equal(dumps[0], dumps[1])
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(1000)
+    x = torch.randn(d["config"]["frames_in"], device="cuda:0", dtype=torch.float32, generator=g) * 0.25
+    y = dev.resample_tensor(dev.Plan(48000, 44100, "VHQ"), x)
+    assert _rel_rms(torch.from_numpy(dumps[0]), y.cpu()) <= 1e-6

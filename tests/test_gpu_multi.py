@@ -152,7 +152,7 @@ def test_bench_gpus_8_gloo_harness_partitions_the_batch():
     import time
     env = dict(os.environ, BENCH_DIST_BACKEND="gloo")
     t0 = time.time()
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--kernels-only", "--steps", "5", "--warmup", "2"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--full", "--kernels-only", "--steps", "5", "--warmup", "2"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     wall = time.time() - t0
     assert p.returncode == 0, p.stderr[-3000:]

@@ -12,9 +12,9 @@ for rep in 1 2; do
 for cfg in "${CFGS[@]}"; do
   set -- $cfg; v=$1; shift; envs="$@"
   if [ "$v" = "-" ]; then
-    out=$(env $envs python bench.py --no-cpu --steps 60 --windows 20 --sustained-s 1.0 2>/dev/null | tail -1)
+    out=$(env $envs python bench.py --full --no-cpu --steps 60 --windows 20 --sustained-s 1.0 2>/dev/null | tail -1)
   else
-    out=$(env $envs tools/with_variant.sh $v python bench.py --no-cpu --steps 60 --windows 20 --sustained-s 1.0 2>/dev/null | tail -1)
+    out=$(env $envs tools/with_variant.sh $v python bench.py --full --no-cpu --steps 60 --windows 20 --sustained-s 1.0 2>/dev/null | tail -1)
   fi
   echo -n "[$v $envs] "; echo "$out" | line
 done; done
