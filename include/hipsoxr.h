@@ -94,7 +94,8 @@ typedef enum { HIPSOXR_F32 = 0, HIPSOXR_F64 = 1, HIPSOXR_I32 = 2, HIPSOXR_I16 = 
 
 /* Kernel selector for hipsoxr_run_device. */
 typedef enum {
-    HIPSOXR_KERNEL_AUTO = 0,   /* fastest admissible engine, including the FFT engine for large float32 jobs */
+    HIPSOXR_KERNEL_AUTO = 0,   /* fastest admissible engine, including the FFT engine for large float jobs
+                                  (integer jobs: always the canonical-order kernels, bit for bit) */
     HIPSOXR_KERNEL_GATHER = 1, /* one lane per output sample, operands gathered through L1/L2 */
     HIPSOXR_KERNEL_TILE = 2,   /* period-tiled, best variant for the engine (MFMA f32, else VALU) */
     HIPSOXR_KERNEL_TILE_VALU = 3, /* period-tiled: input slab in LDS, coefficients on the scalar path */
@@ -105,18 +106,26 @@ typedef enum {
     HIPSOXR_KERNEL_WAVE_DOT = 7, /* reference point only: one wavefront per output sample + shuffle reduction
                                   (the shape BASELINE.json's north star describes); 64-way tree order, so
                                   1e-6-class like FFT, never chosen automatically */
-    HIPSOXR_KERNEL_FFT_F64 = 8  /* the frequency-domain engine computing in float64 whatever the I/O type: float32
+    HIPSOXR_KERNEL_FFT_F64 = 8, /* the frequency-domain engine computing in float64 whatever the I/O type: float32
                                   jobs at the width libsoxr's VHQ recipe itself computes in (its float64 engine;
                                   reference src/soxr_ext.cpp:74,228 pass the recipe through unchanged) — results
                                   differ from the float64 direct form by the float32 OUTPUT rounding only
                                   (~3e-8 relative RMS).  Unit-stride columns of the tabled ratios. */
+    HIPSOXR_KERNEL_FFT_PCM = 9  /* the frequency-domain engine on int16 / int32 device jobs: int16 in float32 arithmetic,
+                                  int32 in float64 (the exact engine's widths), samples in LSB units, then the exact
+                                  engine's own output stage — dither (job.dither, job.dither_seed), round half to even,
+                                  saturate, job.clip_counter.  Opt-in by name only: integer results are within 1 LSB
+                                  of the canonical order, not bit-identical, and AUTO keeps integers on the exact
+                                  engine.  Whole signals on HQ / VHQ plans of the tabled ratios; unit-stride columns
+                                  (ragged batches included) and int16 interleaved channel pairs; float jobs and
+                                  anything else it cannot serve are an error, never a run of another engine. */
 } hipsoxr_kernel_t;
 
 typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase bank (host + device) */
 typedef struct hipsoxr_stream hipsoxr_stream_t; /* stateful converter: the `soxr_t` counterpart */
 
 /* ---- library ---------------------------------------------------------------------------- */
-#define HIPSOXR_VERSION_STRING "0.5.0" /* one number for hipsoxr_version() and the libsoxr-named soxr_version() */
+#define HIPSOXR_VERSION_STRING "0.6.0" /* one number for hipsoxr_version() and the libsoxr-named soxr_version() */
 HIPSOXR_API const char *hipsoxr_version(void);
 HIPSOXR_API int hipsoxr_device_count(void); /* 0 when no HIP device is visible (never throws) */
 
@@ -195,7 +204,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */

@@ -166,9 +166,11 @@ const char *launch_chain_items(Plan *p, int elem, uint32_t n_channels, bool dith
 // ~2x the API time and queues behind a barrier packet)
 const char *launch_copy(void *dst, const void *src, size_t bytes, void *stream);
 
-// frequency-domain engine (fft.hip): whole-signal float32 jobs
+// frequency-domain engine (fft.hip): whole-signal float32 / float64 jobs; int16 / int32 jobs that name it
+// (HIPSOXR_KERNEL_FFT_PCM).  ch0: index of the job's channel 0 in the caller's whole signal (the dither key of jobs
+// folded over channel ranges)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &job);
-const char *launch_fft(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+const char *launch_fft(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled, uint32_t ch0 = 0);
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);

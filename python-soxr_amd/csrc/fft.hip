@@ -13,8 +13,9 @@
 // overlap by more than the filter length, and only the outputs whose whole filter support lies inside the block are
 // kept.  ~70 flop per output instead of 592.  What is neglected is the aliasing of g's stop band (<= -176 dB for VHQ):
 // against the direct form 2.5e-10 relative RMS in float64, ~2e-7 in float32 (FFT rounding) — inside the 1e-6 bar but
-// NOT bit-identical to the canonical order, so this engine serves only whole-signal float32 / float64 device jobs
-// (hipsoxr_run_device); the host surface (soxr.resample / ResampleStream) and integer I/O stay on the exact engine.
+// NOT bit-identical to the canonical order, so this engine serves only whole-signal device jobs (hipsoxr_run_device):
+// float32 / float64 ones, and int16 / int32 ones that name it (HIPSOXR_KERNEL_FFT_PCM); the host surface
+// (soxr.resample / ResampleStream) and integer I/O under AUTO stay on the exact engine.
 //
 // Kernels:
 //   k_fft_block     general path, any 7-smooth plan: one workgroup per block, run-time radix schedule, real FFT through
@@ -23,7 +24,8 @@
 //                   FFT -> *H -> truncate -> inverse FFT (the chain is linear and real-to-real; H is real); compile-time
 //                   three-pass schedules for the standard audio ratios; unit-stride columns (mono, planar, batches):
 //                   raw buffer loads with the hardware range check, output runs staged through LDS and stored as
-//                   16-byte granules.  float32, float64 and float32-on-float64 instances.
+//                   16-byte granules.  float32, float64 and float32-on-float64 instances; int16-on-float32 and
+//                   int32-on-float64 ones (HIPSOXR_KERNEL_FFT_PCM) with the exact engine's output stage in the store loop.
 //   k_fft_strided2  the same chain for columns with a frame stride: interleaved data paired by channel (CP = true:
 //                   one (Real, Real) word per frame) or strided columns paired by block (CP = false).
 // Build switches: -DFFT2_TRACE (per-wave s_memtime stamps of k_fft_pair2, tools/trace_pair2.py).  The experiments of
@@ -45,6 +47,7 @@
 #define FFT_NO_PK // (the packed-FMA forms of fft_dev.h: +8 % on k_fft_pair2 — 124 against 114 us — and -7 % on k_fft_wave, which alone uses them)
 #endif
 #include "fft_dev.h"
+#include "pcm_out.h"
 
 namespace hipsoxr {
 
@@ -425,6 +428,29 @@ __device__ __forceinline__ C spectrum_load(const C *buf, __amdgpu_buffer_rsrc_t 
 // vector instructions in front of the first inverse butterfly), and the staging stores test their range per butterfly
 // OUTPUT in the scalar unit — only the two outputs that can straddle an end of the kept run compare per lane.
 // ---------------------------------------------------------------------------------------------
+// Integer samples (IO = int16_t on float arithmetic, int32_t on double: HIPSOXR_KERNEL_FFT_PCM).  Loads widen exactly;
+// the output stage is the exact engine's (pcm_out.h): dither keyed by (seed, channel, absolute output index k), round
+// half to even, saturate, count.  The value that goes into it must be the one the float kernel stores — that identity is
+// what tests/test_gpu_fft_pcm.py holds the engine to — and with contraction allowed that is a matter of code shape:
+// a multiply and an add fuse only inside one basic block, so control flow behind a butterfly decides which of its
+// last products fuse.  k_fft_pair2 therefore keeps the float kernel's last pass as it is and converts on the way out of
+// LDS; k_fft_strided2, which has no staging, converts in the storer (this function), with `v` pinned in its register
+// first: a value that is a bare product would otherwise fuse with the dither into one FMA.
+// exists: output k is part of the signal — the kernels also convert values past the end of their column, which are
+// dropped by the stores' range check and must not count as clips.
+template <typename IO, typename Real>
+__device__ __forceinline__ IO pcm_stage(Real v, const FftArgs &a, uint32_t ch, int64_t k, bool exists)
+{
+    static_assert((sizeof(IO) == 2 && sizeof(Real) == 4) || (sizeof(IO) == 4 && sizeof(Real) == 8), "int16 on float32, int32 on float64");
+    asm("" : "+v"(v));
+    bool clip;
+    IO r;
+    if constexpr (sizeof(IO) == 2) r = pcm_quantize_i16(v, a.dither != 0, a.seed, ch + a.ch0, k, clip);
+    else r = pcm_quantize_i32(v, clip);
+    if (clip && exists && a.clip_counter) atomicAdd((unsigned long long *)a.clip_counter, 1ULL);
+    return r;
+}
+
 template <typename Spec, typename Real, typename IO>
 __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem_raw, uint32_t col, int64_t bx)
 {
@@ -435,7 +461,11 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     constexpr int NsL = NB / Spec::RB2;   // the last inverse pass writes element o + t * NsL, o < NsL
     constexpr int LB = NA > NB ? NA : NB; // complex points of the transform buffer
     C *buf = reinterpret_cast<C *>(smem_raw);
-    IO *stage = reinterpret_cast<IO *>(smem_raw);
+    // integer samples: the run is staged as the arithmetic's own values — up to there the kernel is the float kernel,
+    // line for line — and converted on its way out of LDS (the store loop below)
+    constexpr bool PCM = std::is_integral<IO>::value;
+    typedef typename std::conditional<PCM, Real, IO>::type ST;
+    ST *stage = reinterpret_cast<ST *>(smem_raw);
 #ifdef FFT2_TRACE
     unsigned long long *g_tr = a.trace ? a.trace + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) + threadIdx.x / 64) * 16 : nullptr;
     int g_tri = 0;
@@ -492,14 +522,14 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     const bool typical = v0 >= 0 && v0 <= NsL && v1 >= NB - NsL && v1 <= NB;
     Spec::inv_staged(FFT_STAMP_ARGS buf, PairTabs<Real>::wb(a), h_load,
         [&](int o, int t, C w) { // typical geometry
-            IO *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
-            if (t == 0) { if (o >= v0) { *sa = (IO)w.x; *sb = (IO)w.y; } }
-            else if (t == Spec::RB2 - 1) { if (o < v1 - t * NsL) { *sa = (IO)w.x; *sb = (IO)w.y; } }
-            else { *sa = (IO)w.x; *sb = (IO)w.y; }
+            ST *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
+            if (t == 0) { if (o >= v0) { *sa = (ST)w.x; *sb = (ST)w.y; } }
+            else if (t == Spec::RB2 - 1) { if (o < v1 - t * NsL) { *sa = (ST)w.x; *sb = (ST)w.y; } }
+            else { *sa = (ST)w.x; *sb = (ST)w.y; }
         },
         [&](int o, int t, C w) { // any geometry
-            IO *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
-            if ((unsigned)(o + t * NsL - v0) < (unsigned)hop_out) { *sa = (IO)w.x; *sb = (IO)w.y; }
+            ST *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
+            if ((unsigned)(o + t * NsL - v0) < (unsigned)hop_out) { *sa = (ST)w.x; *sb = (ST)w.y; }
         }, !typical);
     __syncthreads();
     FFT_STAMP();
@@ -511,7 +541,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     // and ends with the run, so the hardware range check drops what lies beyond the column (and the trips past the
     // run: no trip count, no branches — every LDS read and every store of the thread is in flight at once).  The
     // first granule's sh leading elements belong to the previous run: that one granule goes element by element.
-    {
+    if constexpr (!PCM) {
         const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)(ybase - sh)), 0,
                                                                              __builtin_amdgcn_readfirstlane((valid + sh) * ES), 0x00020000);
         constexpr int QMAX = (2 * (NB - 1) + EPS - 1 + EPS) / EPS; // 2 hop_out < 2 NB elements, + sh
@@ -530,6 +560,59 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), ro, q * 16, 0, FFT_STORE_AUX);
             }
         }
+    } else {
+        // Integer samples: the same granules of the column — EPS staged values (32 bytes of LDS) become one 16-byte store
+        // through the exact engine's output stage (pcm_out.h): staged element e is run element e - sh, output
+        // outa + v0 + e - sh of the column.  Only run elements [0, valid) exist: the others are converted like the rest
+        // (whatever the LDS holds there), dropped by the range check, and not counted as clips.
+        // 2-byte elements: the range check works on whole dwords, so the descriptor ends with the last WHOLE dword of
+        // the run and an odd last element goes out by itself — never half a dword more or less than the run.
+        const int run_bytes = ES == 2 ? ((valid + sh) * ES) & ~3 : (valid + sh) * ES;
+        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)(ybase - sh)), 0,
+                                                                             __builtin_amdgcn_readfirstlane(run_bytes), 0x00020000);
+        constexpr int QMAX = (2 * (NB - 1) + EPS - 1 + EPS) / EPS;
+        constexpr int LQ = (int)((size_t)LB * sizeof(C) / (EPS * sizeof(ST))); // granules' worth of staged values in the LDS buffer
+        const int64_t k_run = outa + v0 - sh; // output index of staged element 0
+        const bool dither = a.dither != 0;
+        const uint32_t dch = ch + a.ch0;
+        unsigned nclip = 0;
+        auto conv = [&](ST v, int e) -> IO {
+            bool clip;
+            IO r;
+            if constexpr (ES == 2) r = pcm_quantize_i16(v, dither, a.seed, dch, k_run + e, clip);
+            else r = pcm_quantize_i32(v, clip);
+            nclip += (clip && e >= sh && e - sh < valid) ? 1u : 0u;
+            return r;
+        };
+        if (ES == 2 && ((valid + sh) & 1) && valid > 0 && threadIdx.x == NT - 1) {
+            const unsigned keep = nclip; // (its granule's thread counts it)
+            ybase[valid - 1] = conv(stage[valid - 1 + sh], valid - 1 + sh);
+            nclip = keep;
+        }
+        const int tid_out = (int)threadIdx.x;
+#pragma unroll
+        for (int it = 0; it < (QMAX + NT - 1) / NT; ++it) {
+            const int q = tid_out + it * NT;
+            const ST *src = stage + EPS * (q < LQ ? q : LQ - 1);
+            IO e[EPS];
+#pragma unroll
+            for (int c = 0; c < EPS; c += 16 / (int)sizeof(ST)) {
+                const typename PairTabs<Real>::V16 v = *reinterpret_cast<const typename PairTabs<Real>::V16 *>(src + c);
+                const ST *pv = reinterpret_cast<const ST *>(&v);
+#pragma unroll
+                for (int i = 0; i < 16 / (int)sizeof(ST); ++i) e[c + i] = conv(pv[i], q * EPS + c + i);
+            }
+            if (q == 0 && sh != 0) {
+#pragma unroll
+                for (int c = 0; c < EPS; ++c)
+                    if (c >= sh && c - sh < valid) ybase[c - sh] = e[c];
+            } else {
+                v4u_t v;
+                __builtin_memcpy(&v, e, 16);
+                __builtin_amdgcn_raw_buffer_store_b128(v, ro, q * 16, 0, FFT_STORE_AUX);
+            }
+        }
+        if (nclip && a.clip_counter) atomicAdd((unsigned long long *)a.clip_counter, (unsigned long long)nclip);
     }
 #ifdef FFT2_TRACE
     if (g_tr && (threadIdx.x & 63) == 0) { // where the wave ran: HW_ID (wave/simd/cu/sh/se fields) and the XCC id
@@ -587,11 +670,15 @@ template <> struct CpIo<double> {
     }
 };
 
-template <typename Spec, typename Real, bool CP>
+// IO = int16_t (CP only, HIPSOXR_KERNEL_FFT_PCM): the common [frames, 2 c] int16 layout — one aligned 4-byte (l, r) word
+// per frame in, the output stage of pcm_stage on both halves and one 4-byte word out.
+template <typename Spec, typename Real, bool CP, typename IO = Real>
 __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 {
     typedef typename PairTabs<Real>::C C;
-    constexpr int ES = (int)sizeof(Real);
+    constexpr bool PCM = !std::is_same<IO, Real>::value;
+    static_assert(!PCM || (CP && std::is_same<IO, int16_t>::value && std::is_same<Real, float>::value), "integer samples: int16 channel pairs");
+    constexpr int ES = (int)sizeof(IO);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     C *cur = reinterpret_cast<C *>(smem_raw);
     constexpr int NA = Spec::NA, NB = Spec::NB, R0 = Spec::RA0, nbA = NA / R0;
@@ -617,7 +704,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     if (bx >= a.pairs_per_col) return; // grid.x is padded to a multiple of 8 items per unit
     const uint32_t ch = CP ? 2 * cu : cu;
     const int32_t hop_in = (int32_t)(a.hop_periods * a.M), hop_out = a.hop_out;
-    const Real *xin = (const Real *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
+    const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
     const int32_t ifb = (int32_t)a.ifs * ES, ofb = (int32_t)a.ofs * ES; // bytes per frame (launcher: 2 N * frame < 2^30)
     auto last_fwd_store = [&](int o, int t, C v) { cur[o + t * (NA / Spec::RA2)] = v; };
     const int32_t v0 = a.v0, v1 = a.v0 + hop_out;
@@ -631,7 +718,10 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
             uniform_ptr((void *)(xin + ina * a.ifs)), 0, __builtin_amdgcn_readfirstlane((int)(left < 0 ? 0 : left > 0x40000000 ? 0x40000000 : left)), 0x00020000);
         const int32_t stepb = nbA * ifb; // one butterfly input further: N/R0 frames
         Spec::fwd(FFT_STAMP_ARGS cur, PairTabs<Real>::wa(a), [&](int j, int t) -> C {
-            if constexpr (CP) return CpIo<Real>::load(rs, j * ifb, t * stepb);
+            if constexpr (PCM) {
+                const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(rs, j * ifb, t * stepb, 0);
+                return C((Real)(int16_t)(w & 0xffffu), (Real)(int16_t)(w >> 16));
+            } else if constexpr (CP) return CpIo<Real>::load(rs, j * ifb, t * stepb);
             else return C(buf_load_real<Real>(rs, j * ifb, t * stepb), buf_load_real<Real>(rs, j * ifb, t * stepb + hop_in * ifb));
         }, last_fwd_store);
     } else { // the first block of a column reaches before its start: explicit zero-extension
@@ -639,7 +729,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
             const int64_t l = ina + j + t * nbA, lb = l + hop_in;
             if constexpr (CP) {
                 C v = C((Real)0, (Real)0);
-                if (l >= a.in_lo && l < a.in_frames) v = C(xin[l * a.ifs], xin[l * a.ifs + 1]);
+                if (l >= a.in_lo && l < a.in_frames) v = C((Real)xin[l * a.ifs], (Real)xin[l * a.ifs + 1]);
                 return v;
             } else {
                 return C((l >= a.in_lo && l < a.in_frames) ? xin[l * a.ifs] : (Real)0, (lb >= a.in_lo && lb < a.in_frames) ? xin[lb * a.ifs] : (Real)0);
@@ -650,7 +740,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     FFT_STAMP();
 
     // ---- inverse (see k_fft_pair2), outputs straight to HBM -----------------------------------------
-    Real *ybase = (Real *)a.out + (int64_t)clip * a.ocs + (int64_t)ch * a.ochs + (outa + v0) * a.ofs; // outa + v0 >= 0
+    IO *ybase = (IO *)a.out + (int64_t)clip * a.ocs + (int64_t)ch * a.ochs + (outa + v0) * a.ofs; // outa + v0 >= 0
     const int64_t oleft = (a.out_frames - (outa + v0)) * (int64_t)ofb;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr((void *)ybase), 0, __builtin_amdgcn_readfirstlane((int)(oleft < 0 ? 0 : oleft > 0x40000000 ? 0x40000000 : oleft)), 0x00020000);
@@ -660,7 +750,11 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     Spec::inv(FFT_STAMP_ARGS cur, PairTabs<Real>::wb(a), h_load, [&](int o, int t, C wv) {
         const int n = o + t * (NB / Spec::RB2);
         if (n >= v0 && n < v1) {
-            if constexpr (CP) {
+            if constexpr (PCM) {
+                const int64_t k = outa + n; // (>= 0: n >= v0)
+                const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, k, k < a.out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, k, k < a.out_frames);
+                __builtin_amdgcn_raw_buffer_store_b32((unsigned)l | ((unsigned)r << 16), ro, (n - v0) * ofb, 0, 0);
+            } else if constexpr (CP) {
                 CpIo<Real>::store(wv, ro, (n - v0) * ofb); // frame outa + n holds (y_c, y_{c+1})
             } else {
                 buf_store_real(wv.x, ro, (n - v0) * ofb);             // block a
@@ -680,7 +774,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 // float32-on-float64, k_fft_strided2 x 2 in float32 and float64); compiled in one piece they are the build's critical
 // path.  build.sh compiles this file three times: -DFFT_PART=0 = everything except the kernels of the schedules listed
 // here (declared extern), -DFFT_PART=1 / =2 = the templates above plus exactly the kernels of one of the two lists, no
-// host code.  Without FFT_PART: one piece.
+// host code (=3 / =4: the integer-sample kernels of the same lists, below).  Without FFT_PART: one piece.
 // ---------------------------------------------------------------------------------------------
 #define HIPSOXR_PART1_SPECS(X) X(4096, 2048, 256) X(2048, 4096, 256) X(2048, 1024, 256) X(1024, 2048, 256) X(5376, 1792, 384) X(1792, 5376, 384) X(5376, 3584, 384) X(3584, 5376, 384) X(2688, 896, 384) X(896, 2688, 384) X(2688, 1792, 384) X(1792, 2688, 384) X(5120, 1280, 320) X(1280, 5120, 320) X(5376, 896, 384) X(896, 5376, 384)
 #define HIPSOXR_PART2_SPECS(X) X(7056, 5120, 448) X(5120, 7056, 448) X(4704, 2560, 384) X(2560, 4704, 384) X(5120, 2352, 384) X(2352, 5120, 384) X(7056, 1280, 448) X(1280, 7056, 448) X(5120, 1176, 320) X(1176, 5120, 320) X(3528, 5120, 384) X(5120, 3528, 384) X(4704, 1280, 384) X(1280, 4704, 384) X(3840, 5120, 384) X(5120, 3840, 384)
@@ -692,16 +786,30 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, double, true>(FftArgs);   \
     HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, false>(FftArgs);   \
     HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, double, false>(FftArgs);
+// ... and three more for integer samples (HIPSOXR_KERNEL_FFT_PCM): units of their own, FFT_PART=3 / =4, over the same
+// two lists — shorter than the float units, so the parallel build's longest unit stays what it was
+#define HIPSOXR_INST_PCM(NA, NB, NT)                                                                             \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>(FftArgs);             \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>(FftArgs);            \
+    HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>(FftArgs);
 #if defined(FFT_PART) && FFT_PART == 0
 #define HIPSOXR_EXTERN extern
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
 HIPSOXR_PART2_SPECS(HIPSOXR_INST)
+HIPSOXR_PART1_SPECS(HIPSOXR_INST_PCM)
+HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
 #elif defined(FFT_PART) && FFT_PART == 1
 #define HIPSOXR_EXTERN
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
 #elif defined(FFT_PART) && FFT_PART == 2
 #define HIPSOXR_EXTERN
 HIPSOXR_PART2_SPECS(HIPSOXR_INST)
+#elif defined(FFT_PART) && FFT_PART == 3
+#define HIPSOXR_EXTERN
+HIPSOXR_PART1_SPECS(HIPSOXR_INST_PCM)
+#elif defined(FFT_PART) && FFT_PART == 4
+#define HIPSOXR_EXTERN
+HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
 #endif
 
 #if !defined(FFT_PART) || FFT_PART == 0
@@ -841,18 +949,20 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
     return nullptr;
 }
 
-// Whole-signal float32 / float64 job?  (zero-extended signal starting at absolute index 0, all outputs)
+// Whole-signal float32 / float64 job (or an int16 / int32 one that names the engine)?  (zero-extended signal starting at absolute index 0, all outputs)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
 {
     // what the method neglects is the aliasing of the filter's stop band: only recipes whose stop band
     // is far below the 1e-6 bar qualify (HQ 128 dB, VHQ 177 dB; MQ/LQ at 104 dB do not)
-    return p.phases == 0 && p.att_db >= 120. && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && j.in_abs0 == 0 &&
+    // (integer samples only by name — HIPSOXR_KERNEL_FFT_PCM: AUTO keeps them on the canonical order, bit for bit)
+    const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32) : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64);
+    return p.phases == 0 && p.att_db >= 120. && elem_ok && j.in_abs0 == 0 &&
            j.out_k0 == 0 && (uint64_t)j.out_frames <= plan_out_len(p, (uint64_t)j.in_frames);
 }
 
 // (job.in_abs0 != 0 — in[0] is sample in_abs0 of a column that is zero outside [in_abs0, in_abs0 + in_frames) — is served
 // for the two-stage form's inner calls; the public paths come here through fft_job_eligible, which wants 0.)
-const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0)
 {
     *handled = false;
     // geometry cache key: (plan, variant) with variant 0 = default search, 1 = small-block search,
@@ -873,12 +983,16 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
         void (*kern2fd)(FftArgs);                        // float32 I/O on float64 arithmetic (HIPSOXR_KERNEL_FFT_F64)
         void (*kcp)(FftArgs); void (*kcpd)(FftArgs);     // channel-pair mode (interleaved data), float32 / float64
         void (*kst)(FftArgs); void (*kstd)(FftArgs);     // strided columns, two blocks per transform
+        void (*kern2i16)(FftArgs); void (*kern2i32)(FftArgs); // integer samples (HIPSOXR_KERNEL_FFT_PCM): unit-stride columns,
+        void (*kcpi16)(FftArgs);                         // int16 on float32 / int32 on float64 arithmetic; int16 channel pairs
     };
 #define HIPSOXR_PAIR(L, M, k, small, NA, NB, NT) \
     {L, M, k, small, NT, k_fft_pair2<PairOf<NA, NB, NT>, float>, k_fft_pair2<PairOf<NA, NB, NT>, double>, \
      k_fft_pair2<PairOf<NA, NB, NT>, double, float>, \
      k_fft_strided2<PairOf<NA, NB, NT>, float, true>, k_fft_strided2<PairOf<NA, NB, NT>, double, true>, \
-     k_fft_strided2<PairOf<NA, NB, NT>, float, false>, k_fft_strided2<PairOf<NA, NB, NT>, double, false>}
+     k_fft_strided2<PairOf<NA, NB, NT>, float, false>, k_fft_strided2<PairOf<NA, NB, NT>, double, false>, \
+     k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>, k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>, \
+     k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>}
     static const PairEntry pairs[] = {
         // L, M (out/in = L/M), periods per block, small-job variant, N_in, N_out, threads
         HIPSOXR_PAIR(147, 160, 32, false, 5120, 4704, 384), HIPSOXR_PAIR(147, 160, 16, true, 2560, 2352, 384),   // 48k -> 44.1k
@@ -909,9 +1023,13 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
     // f64: the ARITHMETIC is float64 (block size, LDS bytes per point, table set) — float64 jobs, and float32 jobs that
     // ask for libsoxr's own VHQ width with HIPSOXR_KERNEL_FFT_F64 (io64 = the signal's elements are 8 bytes)
     const bool io64 = j.elem == HIPSOXR_F64, wide32 = !io64 && j.kernel == HIPSOXR_KERNEL_FFT_F64;
-    const bool f64 = io64 || wide32;
-    // float64: the paired kernels only (unit-stride columns; channel pairs; strided columns) — else the exact engine
-    if (f64 && (no_pair || cols_p > 65535)) return nullptr;
+    // pcm: integer samples (HIPSOXR_KERNEL_FFT_PCM), int16 on float32 and int32 on float64 arithmetic — every size rule
+    // below is the float job's of that arithmetic width
+    const bool pcm = j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32, pcm32 = j.elem == HIPSOXR_I32;
+    const bool f64 = io64 || wide32 || pcm32;
+    // float64, integer samples: the paired kernels only (unit-stride columns; channel pairs; strided columns) — else the
+    // exact engine (integer samples: the caller's error)
+    if ((f64 || pcm) && (no_pair || cols_p > 65535)) return nullptr;
     if (!no_pair && cols_p <= 65535) {
         const PairEntry *big = nullptr, *sml = nullptr, *tiny = nullptr;
         int big_i = 0, sml_i = 0, tiny_i = 0;
@@ -954,7 +1072,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
             }
             if (use) {
                 FftArgs a;
-                a.in = (const char *)j.in - j.in_abs0 * j.in_frame_stride * (int64_t)(j.elem == HIPSOXR_F64 ? 8 : 4); a.out = j.out; // (sample 0 of the columns)
+                a.in = (const char *)j.in - j.in_abs0 * j.in_frame_stride * (int64_t)elem_size(j.elem); a.out = j.out; // (sample 0 of the columns)
                 auto set_geom = [](FftArgs &a, const FftGeom &g) {
                     a.WA = g.dev; a.WB = a.WA + g.A; a.P = a.WB + g.B; a.Q = a.P + (g.A + 1); a.Hs = a.Q + g.B;
                     a.WA2 = a.Hs + (g.B + 1); a.WB2 = a.WA2 + g.N_in;
@@ -971,13 +1089,17 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
                 a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
                 a.in_lo = j.in_abs0; a.in_frames = j.in_abs0 + j.in_frames; a.out_frames = j.out_frames;
                 a.clip_tab = j.clip_table_dev;
+                a.clip_counter = pcm ? j.clip_counter : nullptr; a.dither = j.dither; a.seed = j.dither_seed; a.ch0 = ch0;
                 const int64_t n_blocks = (j.out_frames + g.hop_out - 1) / g.hop_out;
                 if (n_blocks > 2147483647LL) return "job too long for one launch";
                 // interleaved data with an even channel count: pair channels (one (Real, Real) word per frame)
-                const size_t esz = io64 ? sizeof(double) : sizeof(float);
+                const size_t esz = elem_size(j.elem);
                 const bool cp_layout = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && !switches().fft_no_chpair;
                 // ... when a block's byte offsets fit the kernel's 32-bit operands (buffer loads: element alignment is enough)
-                const bool cp2 = !wide32 && (int64_t)std::max(g.N_in, g.N_out) * std::max(j.in_frame_stride, j.out_frame_stride) * (int64_t)esz < (1LL << 30);
+                // (int16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
+                const bool cp_pcm_ok = !pcm || (!pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
+                                                ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0);
+                const bool cp2 = !wide32 && cp_pcm_ok && (int64_t)std::max(g.N_in, g.N_out) * std::max(j.in_frame_stride, j.out_frame_stride) * (int64_t)esz < (1LL << 30);
                 // (channel pairing rides on the XCD-aware work-item map: decided together, so that a job without the
                 //  map — HIPSOXR_FFT_NO_XCD_MAP, or too many work items — runs unpaired on the strided kernel instead of failing)
                 const int64_t cp_items8 = (n_blocks + 7) / 8 * 8;
@@ -996,19 +1118,20 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
                 dim3 grid = a.xcd_map ? dim3((unsigned)(items8 * units), j.n_clips, 1)
                                       : dim3((unsigned)((n_blocks + 1) / 2), (unsigned)cols_p, 1);
                 // unit-stride columns (mono / planar): buffer loads, staged aligned stores
-                const bool v2ok = !a.xcd_map && !a.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 &&
-                                  2 * (size_t)g.hop_out * esz + 16 <= lds1;
+                // (integer samples are staged as the arithmetic's values, up to 7 elements into the run's first granule)
+                const size_t stage_bytes = pcm ? 2 * (size_t)g.hop_out * (f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * esz + 16;
+                const bool v2ok = !a.xcd_map && !a.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 && stage_bytes <= lds1;
                 const bool cp2ok = a.chpair && a.xcd_map && cp2;
                 // strided columns that are not channel pairs (odd channel counts, channel slices): two blocks of one column
                 // per transform when the byte offsets of a pair of blocks fit the 32-bit operands
-                const bool st2ok = !wide32 && !a.chpair && !v2ok &&
+                const bool st2ok = !wide32 && !pcm && !a.chpair && !v2ok &&
                                    2 * (int64_t)std::max(g.N_in, g.N_out) * std::max(j.in_frame_stride, j.out_frame_stride) * (int64_t)esz < (1LL << 30);
                 // Throughput form (fftwave.hip): one wave per pair of 24-period blocks, two register passes per transform —
                 // float32 unit-stride columns with enough pairs to fill the chip's 2048 wave slots four times over (below
                 // that the last, partly filled round costs more than the form gains; and a single pair's latency is
                 // longer than on the 6-wave workgroups of k_fft_pair2).
                 FftWaveKernel wk;
-                if (v2ok && !f64 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
+                if (v2ok && !f64 && !pcm && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
                     FftGeom gw;
                     if (const char *err = get(1000 + wk.k, wk.k, &gw)) return err;
                     const int64_t pairs_w = gw.ok ? ((j.out_frames + gw.hop_out - 1) / gw.hop_out + 1) / 2 : 0;
@@ -1028,9 +1151,9 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
                 unsigned nt = use->nt;
                 size_t lds = lds1;
                 if (v2ok) {
-                    kern = io64 ? use->kern2d : wide32 ? use->kern2fd : use->kern2;
+                    kern = pcm ? (pcm32 ? use->kern2i32 : use->kern2i16) : io64 ? use->kern2d : wide32 ? use->kern2fd : use->kern2;
                 } else {
-                    kern = cp2ok ? (f64 ? use->kcpd : use->kcp) : (f64 ? use->kstd : use->kst);
+                    kern = pcm ? use->kcpi16 : cp2ok ? (f64 ? use->kcpd : use->kcp) : (f64 ? use->kstd : use->kst); // (pcm: cp2ok — st2ok wants floats)
                 }
                 if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
 #ifdef FFT2_TRACE
@@ -1058,7 +1181,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
         }
     }
     // ---- general path: one block per workgroup ---------------------------------------------------
-    if (f64 || j.clip_table) return nullptr; // float32 only, no ragged batches
+    if (f64 || pcm || j.clip_table) return nullptr; // float32 only, no ragged batches
     FftGeom g;
     if (const char *err = get(0, 0, &g)) return err;
     if (g.ok) {
@@ -1077,6 +1200,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
     a.Hr = reinterpret_cast<const float *>(a.WB2 + g.N_out); a.trace = nullptr;
     a.WA2d = a.WB2d = nullptr; a.Hrd = nullptr; a.clip_tab = nullptr;
     a.chpair = 0; a.pairs_per_col = 0; a.xcd_map = 0;
+    a.clip_counter = nullptr; a.dither = a.seed = a.ch0 = 0;
     a.A = g.A; a.B = g.B; a.nA = g.nA; a.nB = g.nB;
     for (int i = 0; i < 8; ++i) { a.radA[i] = g.radA[i]; a.radB[i] = g.radB[i]; }
     a.L = p->L; a.M = p->M;

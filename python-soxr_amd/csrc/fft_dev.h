@@ -287,6 +287,10 @@ struct FftArgs {
     int32_t chpair;          // k_fft_strided2: 1 = pair neighbouring channels of interleaved data instead of blocks
     int64_t pairs_per_col;   // xcd_map: work items (blocks, or pairs of blocks) per channel unit
     int32_t xcd_map;         // interleaved multi-channel data: XCD-aware workgroup ids (see k_fft_strided2)
+    // integer jobs (HIPSOXR_KERNEL_FFT_PCM): the output stage's context, as the exact engine's OutCtx
+    uint64_t *clip_counter;  // device counter of saturated outputs, or nullptr
+    uint32_t dither, seed;   // int16: TPDF dither keyed by (seed, channel + ch0, absolute output index)
+    uint32_t ch0;            // index of the job's channel 0 in the caller's whole signal
 };
 
 // fftwave.hip: the one-wave-per-block-pair kernel of a ratio — block size (periods), the geometry it is compiled for,
@@ -328,6 +332,16 @@ template <> __device__ __forceinline__ double buf_load_real<double>(__amdgpu_buf
 {
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0));
 }
+// integer samples (HIPSOXR_KERNEL_FFT_PCM): 2- / 4-byte loads — a column of int16 may start on any even address, so
+// the general form is one element per load — widened to the arithmetic type by the caller (exact in float / double)
+template <> __device__ __forceinline__ int16_t buf_load_real<int16_t>(__amdgpu_buffer_rsrc_t r, int voff, int soff)
+{
+    return (int16_t)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, FFT_LOAD_AUX);
+}
+template <> __device__ __forceinline__ int32_t buf_load_real<int32_t>(__amdgpu_buffer_rsrc_t r, int voff, int soff)
+{
+    return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, FFT_LOAD_AUX);
+}
 __device__ __forceinline__ void buf_store_real(float v, __amdgpu_buffer_rsrc_t r, int voff)
 {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, 0, 0);
@@ -350,5 +364,9 @@ template <> struct PairTabs<double> {
     static __device__ __forceinline__ const C *wb(const FftArgs &a) { return a.WB2d; }
     static __device__ __forceinline__ const double *hr(const FftArgs &a) { return a.Hrd; }
 };
+
+// (element types that are I/O only: the 16-byte granule of the staged output run)
+template <> struct PairTabs<int16_t> { typedef v4u_t V16; };
+template <> struct PairTabs<int32_t> { typedef v4u_t V16; };
 
 } // namespace hipsoxr

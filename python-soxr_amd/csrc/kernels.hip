@@ -60,6 +60,7 @@
 #include <vector>
 
 #include "device.h"
+#include "pcm_out.h"
 
 namespace hipsoxr {
 
@@ -95,21 +96,7 @@ const Switches &switches()
 // ---------------------------------------------------------------------------------------------
 // conversions
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ULL;
-    z ^= z >> 27; z *= 0x94D049BB133111EBULL;
-    z ^= z >> 31;
-    return z;
-}
-// TPDF dither in (-1, 1) LSB: pure function of (seed, channel, absolute output index).
-__device__ __forceinline__ float dither_tpdf(uint32_t seed, uint32_t ch, int64_t k)
-{
-    uint64_t z = mix64((uint64_t)k * 0x9E3779B97F4A7C15ULL + (((uint64_t)ch << 32) | seed));
-    int32_t u1 = (int32_t)(z & 0xFFFFFF), u2 = (int32_t)((z >> 24) & 0xFFFFFF);
-    return (float)(u1 - u2) * (1.f / 16777216.f);
-}
-
+// (mix64 / dither_tpdf and the integer conversions: pcm_out.h, shared with the frequency-domain engine)
 struct OutCtx {
     uint64_t *clip_counter;
     uint32_t dither, seed;
@@ -137,24 +124,18 @@ __device__ __forceinline__ void store_out(double *p, Real v, const OutCtx &, uin
 template <typename Real>
 __device__ __forceinline__ void store_out(int16_t *p, Real v, const OutCtx &c, uint32_t ch, int64_t k)
 {
-    float a = (float)v;
-    if (c.dither) a = a + dither_tpdf(c.seed, ch + c.ch0, k);
-    float r = __builtin_rintf(a);
-    bool clip = false;
-    if (r > 32767.f) { r = 32767.f; clip = true; }
-    else if (r < -32768.f) { r = -32768.f; clip = true; }
+    bool clip;
+    const int16_t r = pcm_quantize_i16((float)v, c.dither != 0, c.seed, ch + c.ch0, k, clip);
     if (clip && c.clip_counter) atomicAdd((unsigned long long *)c.clip_counter, 1ULL);
-    put_out(p, (int16_t)r);
+    put_out(p, r);
 }
 template <typename Real>
 __device__ __forceinline__ void store_out(int32_t *p, Real v, const OutCtx &c, uint32_t, int64_t)
 {
-    double r = __builtin_rint((double)v);
-    bool clip = false;
-    if (r > 2147483647.) { r = 2147483647.; clip = true; }
-    else if (r < -2147483648.) { r = -2147483648.; clip = true; }
+    bool clip;
+    const int32_t r = pcm_quantize_i32((double)v, clip);
     if (clip && c.clip_counter) atomicAdd((unsigned long long *)c.clip_counter, 1ULL);
-    put_out(p, (int32_t)r);
+    put_out(p, r);
 }
 
 __device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -1420,11 +1401,26 @@ const char *launch_chain_items(Plan *p, int elem, uint32_t n_channels, bool dith
     return "unknown element type";
 }
 
+// HIPSOXR_KERNEL_FFT_PCM is an explicit request for the frequency-domain engine on integer samples: whatever it cannot
+// serve is an error, never a quiet run of the exact engine (whose results differ in the last bit).
+static const char *fft_pcm_refusal(const Plan &p, const hipsoxr_job_t &j, const VrPos *vr, const ResidentLaunch *res)
+{
+    if (vr || res) return "FFT engine: whole-signal device jobs only";
+    if (j.elem != HIPSOXR_I16 && j.elem != HIPSOXR_I32)
+        return "HIPSOXR_KERNEL_FFT_PCM serves int16 / int32 jobs (float jobs have HIPSOXR_KERNEL_FFT / HIPSOXR_KERNEL_FFT_F64)";
+    if (!fft_job_eligible(p, j))
+        return "FFT engine (integer samples) needs a whole-signal job (in_abs0 == 0, out_k0 == 0) on an HQ/VHQ exact-ratio plan";
+    return nullptr;
+}
+
 const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPos *vr, ResidentLaunch *res, ChainDone *cd)
 {
     if (cd) cd->n_wgs = 0;
     if (j.out_frames <= 0 || j.n_clips == 0 || j.n_channels == 0) return res ? "resident kernel: empty job" : nullptr;
     if (res && (uint64_t)j.n_clips * j.n_channels > 65535) return "resident kernel: too many columns";
+    const bool want_pcm = j.kernel == HIPSOXR_KERNEL_FFT_PCM;
+    if (want_pcm)
+        if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
     // (the kernel reads its clip's row), else clip by clip through the ordinary path — clips are independent, so the
     // results are the same either way; bit-exact engines stay bit-exact.
@@ -1440,7 +1436,7 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         }
         // AUTO takes the 1e-6-class engine under the same rule as for equal-length jobs (>= 2^13 outputs in all): engine
         // choice — and with it bit-exactness — does not depend on whether a table is present
-        const bool want_fft = j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64;
+        const bool want_fft = j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64 || want_pcm;
         const bool big = total_out * (int64_t)j.n_channels >= (1 << 13);
         if ((want_fft || (j.kernel == HIPSOXR_KERNEL_AUTO && big && !switches().no_fft)) &&
             (uint64_t)j.n_clips * j.n_channels <= 65535 && fft_job_eligible(*p, j)) {
@@ -1460,12 +1456,13 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
                 jj.clip_table_dev = (const int64_t *)tmp;
             }
             bool handled = false;
-            const char *e = launch_fft(p, jj, stream, &handled);
+            const char *e = launch_fft(p, jj, stream, &handled, t_ch_base);
             if (tmp) (void)hipFreeAsync(tmp, (hipStream_t)stream);
             if (e) return e;
             if (handled) return nullptr;
         }
         if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (unit-stride float columns of a tabled ratio)";
+        if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (unit-stride int16 / int32 columns of a tabled ratio)";
         const size_t es = elem_size(j.elem);
         for (uint32_t c = 0; c < j.n_clips; ++c) {
             const int64_t *r = j.clip_table + 4 * (size_t)c;
@@ -1551,6 +1548,12 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             if (want_fft) return j.kernel == HIPSOXR_KERNEL_FFT_F64 ? "FFT engine (float64 arithmetic) unavailable for this plan or layout (unit-stride columns of a tabled ratio)"
                                                                      : "FFT engine unavailable for this plan";
         }
+    }
+    if (want_pcm) { // (eligible: checked on entry)
+        bool handled = false;
+        if (const char *e = launch_fft(p, j, stream, &handled, t_ch_base)) return e;
+        if (handled) return nullptr;
+        return "FFT engine (integer samples) unavailable for this plan or layout (unit-stride columns, or int16 interleaved channel pairs, of a tabled ratio)";
     }
     hipStream_t st = (hipStream_t)stream;
     switch (j.elem) {

@@ -12,7 +12,7 @@ import numpy as np
 from . import _native as _n
 from . import _quality_to_enum
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
-                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64)
+                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM)
 
 
 class Plan:
@@ -80,7 +80,7 @@ class PreparedJob:
     (benchmarks, fixed-shape pipelines) where Python-side argument handling would otherwise
     cost as much as the 13 us kernel."""
 
-    def __init__(self, plan, x, out, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None):
+    def __init__(self, plan, x, out, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
         import torch
         x3 = x[None, :, None] if x.ndim == 1 else (x[None] if x.ndim == 2 else x)
         o3 = out[None, :, None] if out.ndim == 1 else (out[None] if out.ndim == 2 else out)
@@ -94,7 +94,7 @@ class PreparedJob:
         j.out_clip_stride, j.out_frame_stride, j.out_chan_stride = o3.stride()
         j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, frames, 0, o3.shape[1]
         j.clip_counter = clip_counter.data_ptr() if clip_counter is not None else None
-        j.dither, j.dither_seed = int(bool(dither)), 0
+        j.dither, j.dither_seed = int(bool(dither)), int(dither_seed) & 0xFFFFFFFF
         self._job, self._ref = j, _C.byref(j)
         self._plan, self._keep = plan, (x, out, clip_counter)
         self._stream = torch.cuda.current_stream(x.device).cuda_stream
@@ -121,12 +121,16 @@ def _torch_elem(dtype):
         raise TypeError(f"Data type must be one of [float32, float64, int16, int32], not {dtype}")
 
 
-def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None):
+def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
     """Resample a device tensor on the current torch stream, asynchronously.
 
     x : [frames] | [frames, channels] | [clips, frames, channels] torch tensor on a HIP device
         (any strides; channel-last is the python-soxr [frame, channel] convention).
     Returns a tensor of the same rank with plan.out_len(frames) frames (`out` may be supplied).
+    Integer tensors: dither / dither_seed = TPDF dither on int16 output, keyed by (seed, channel, output index);
+    clip_counter = a one-element int64 / uint64 device tensor that counts saturated outputs.  AUTO keeps them on the
+    canonical-order engine; kernel=KERNEL_FFT_PCM asks for the frequency-domain engine (int16 in float32, int32 in
+    float64 arithmetic, the same output stage: within 1 LSB of the canonical order, not bit-identical to it).
     """
     import torch
     if not x.is_cuda:
@@ -152,7 +156,8 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     if n_out and clips and ch:
         stream = torch.cuda.current_stream(x.device).cuda_stream
         plan.run(x3.data_ptr(), o3.data_ptr(), elem, clips, ch, frames, n_out, tuple(x3.stride()),
-                 tuple(o3.stride()), stream=stream, kernel=kernel, clip_counter=cc, dither=dither)
+                 tuple(o3.stride()), stream=stream, kernel=kernel, clip_counter=cc, dither=dither,
+                 dither_seed=int(dither_seed) & 0xFFFFFFFF)
     if x.ndim == 1:
         return o3[0, :, 0]
     if x.ndim == 2:

@@ -117,9 +117,11 @@ class RaggedJob:
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
 
-    def __init__(self, plan, clips, kernel=_n.KERNEL_AUTO, stream=None, dither=None):
+    def __init__(self, plan, clips, kernel=_n.KERNEL_AUTO, stream=None, dither=None, dither_seed=0, clip_counter=None):
         """dither: TPDF dither on int16 output (None = on for int16, as `soxr_amd.resample` and libsoxr do; keyed by
-        channel and output index within each clip, so a clip's result does not depend on its neighbours).
+        dither_seed, channel and output index within each clip, so a clip's result does not depend on its neighbours).
+        clip_counter: a one-element 64-bit integer device tensor that counts saturated integer outputs.
+        kernel: KERNEL_FFT_PCM serves an int16 / int32 corpus (mono clips) on the frequency-domain engine in one launch.
         stream: a torch.cuda.Stream (ordering handled here) or a raw hipStream_t handle (the caller orders it)."""
         import torch
         if not clips:
@@ -150,7 +152,9 @@ class RaggedJob:
         j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, max(n_in), 0, max(n_out)
         j.clip_table, j.clip_table_dev = self._table.ctypes.data, self._table_dev.data_ptr()
         j.dither = int(keep[0].dtype == torch.int16 if dither is None else bool(dither))
-        j.dither_seed = 0
+        j.dither_seed = int(dither_seed) & 0xFFFFFFFF
+        j.clip_counter = clip_counter.data_ptr() if clip_counter is not None else None
+        self._counter = clip_counter
         self._job, self._ref, self._plan = j, _C.byref(j), plan
         cur = torch.cuda.current_stream(device)
         if isinstance(stream, torch.cuda.Stream):
@@ -464,7 +468,9 @@ def resample_batch(clips, in_rate, out_rate, quality="VHQ", devices=None, kernel
                fresh pageable arrays filled by one more CPU copy.  None: yes while the call's results stay under
                PINNED_RESULTS_MAX bytes.  The arrays are ordinary writable numpy arrays either way.
     kernel   : engine selector for the device jobs (AUTO: the frequency-domain engine for large float jobs,
-               1e-6-class; KERNEL_EXACT: the canonical-order engine, bit-identical to `soxr_amd.resample`).
+               1e-6-class; KERNEL_EXACT: the canonical-order engine, bit-identical to `soxr_amd.resample`;
+               KERNEL_FFT_PCM: the frequency-domain engine for an int16 / int32 corpus — mono clips, one launch per
+               block, within 1 LSB of the canonical order).
     Returns a list of arrays of the same kind (numpy in -> numpy out; tensor in -> tensor on the device that
     computed it), in the order given."""
     import torch

@@ -8,6 +8,6 @@ mkdir -p $R/_obj/$N $R/_variants/$N
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -I$R/../include \
   -ffp-contract=off -DHIPSOXR_DEBUG_SWITCHES "$@" -c $R/csrc/kernels.hip -o $R/_obj/$N/kernels.o
 O=$R/_obj
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/plan.o $O/engine.o $O/$N/kernels.o $O/fft.o $O/fft1.o $O/fft2.o $O/twostage.o $O/fftwave.o $O/soxr_abi.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $O/plan.o $O/engine.o $O/$N/kernels.o $O/fft.o $O/fft1.o $O/fft2.o $O/fft3.o $O/fft4.o $O/twostage.o $O/fftwave.o $O/soxr_abi.o \
   -o $R/_variants/$N/libhipsoxr.so
 echo built $N
