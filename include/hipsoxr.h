@@ -88,6 +88,16 @@ typedef enum {
                                   such instances may hold at most an eighth of the chip.  Not a default: while a
                                   resident kernel spins, hipDeviceSynchronize / hipFree anywhere in the process wait
                                   until it leaves (up to the idle time, longer if another thread keeps feeding it). */
+#define HIPSOXR_STREAM_FFT 512UL /* (extension, opt-in) every emission of the stream runs on the frequency-domain engine
+                                  (HIPSOXR_KERNEL_FFT's, 2-3x faster than the canonical order on chunks of seconds of
+                                  audio) instead of the canonical-order kernels: same frame counts per call, same delay
+                                  and flush behaviour, values 1e-6-class (integers within 1 LSB) — NOT bit-identical to
+                                  the default stream or to another cut of the same signal into chunks.  For
+                                  hipsoxr_stream_process_device only (host-pointer and grouped calls on such a handle
+                                  are an error).  Refused at creation, by name, where the engine cannot serve the
+                                  stream: variable rate, ratios without an exact bank or outside the engine's schedule
+                                  table, recipes below HQ, split layouts, HIPSOXR_DEFER / _RESIDENT / _AUTO_RESIDENT,
+                                  int32 with more than one channel, int16 with an odd channel count above one. */
 
 /* Element types used by device jobs (layout is given by strides, not by the type). */
 typedef enum { HIPSOXR_F32 = 0, HIPSOXR_F64 = 1, HIPSOXR_I32 = 2, HIPSOXR_I16 = 3 } hipsoxr_elem_t;
@@ -125,7 +135,7 @@ typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase 
 typedef struct hipsoxr_stream hipsoxr_stream_t; /* stateful converter: the `soxr_t` counterpart */
 
 /* ---- library ---------------------------------------------------------------------------- */
-#define HIPSOXR_VERSION_STRING "0.6.0" /* one number for hipsoxr_version() and the libsoxr-named soxr_version() */
+#define HIPSOXR_VERSION_STRING "0.7.0" /* one number for hipsoxr_version() and the libsoxr-named soxr_version() */
 HIPSOXR_API const char *hipsoxr_version(void);
 HIPSOXR_API int hipsoxr_device_count(void); /* 0 when no HIP device is visible (never throws) */
 
@@ -204,7 +214,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
@@ -235,7 +245,8 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_stream_process(hipsoxr_stream_t *, const voi
  * (in == NULL: end of input; variable-rate streams and hipsoxr_stream_set_io_ratio included); frames and call
  * boundaries are those of hipsoxr_stream_process on the same input.  What CSoxr::process (src/soxr_ext.cpp:129-187)
  * would be for a caller whose audio already lives in HBM.  Not for streams created with HIPSOXR_DEFER / HIPSOXR_RESIDENT
- * flags or the split layout. */
+ * flags or the split layout.  A stream created with HIPSOXR_STREAM_FFT (version 0.7.0) emits the same frame counts through the
+ * frequency-domain engine. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_stream_process_device(hipsoxr_stream_t *, const void *in, size_t ilen,
                                                           void *out, size_t olen, size_t *odone, void *hip_stream);
 /* Many INDEPENDENT streams in one call (round 5; version 0.5.0): handles[i] gets chunk ins[i] / ilens[i] and writes up to

@@ -171,6 +171,12 @@ const char *launch_copy(void *dst, const void *src, size_t bytes, void *stream);
 // folded over channel ranges)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &job);
 const char *launch_fft(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled, uint32_t ch0 = 0);
+// Streams on that engine (HIPSOXR_STREAM_FFT, engine.cpp): fft_stream_refusal names what it cannot serve (nullptr: served)
+// and reports the periods of input a block reads in front of its first kept output; launch_fft_window is the chunk's job —
+// outputs [job.out_k0, out_k0 + out_frames) of a column whose samples [in_abs0, in_abs0 + in_frames) are at job.in, zero
+// outside — on the paired kernels only (*handled = false: not served, nothing launched; the caller's error).
+const char *fft_stream_refusal(const Plan &p, int elem, uint32_t n_channels, int32_t *lead_periods);
+const char *launch_fft_window(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled, uint32_t ch0 = 0);
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);

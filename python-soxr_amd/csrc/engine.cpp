@@ -150,6 +150,10 @@ struct hipsoxr_stream {
         unsigned failed = 0;         // launches refused (job not eligible): stop trying
     } res;
     int device = -1;         // the device the HIP stream and every buffer above live on
+    // Frequency-domain streams (flag STREAM_FFT): every emission of hipsoxr_stream_process_device is a job window on the
+    // frequency-domain engine (launch_fft_window); fft_lead = periods a block reads in front of its first kept output
+    bool fft = false;
+    int32_t fft_lead = 0;
     uint32_t dither_seed = 0; // int16 TPDF dither: hash(seed, channel, absolute output index); see hipsoxr_stream_set_dither_seed
     char engine_name[32] = {0};
 };
@@ -506,6 +510,20 @@ static int64_t first_needed(const hipsoxr_stream *s)
     if (s->vr.on) return (int64_t)(s->vr.pos(s->k_done) >> 64) - (p.T / 2 - 1);
     int64_t n0, ph;
     locate(p, (int64_t)s->k_done, &n0, &ph);
+    if (s->fft) {
+        // Frequency-domain streams keep history back to where the first BLOCK of the next call starts: the engine's origin
+        // for outputs from k_done on is the period boundary P0 = floor(k_done / L), and block 0 begins lead periods in front
+        // of it — (P0 - lead) M, from the geometry (fft_stream_refusal; the same for every block size of the ratio).
+        // That is never later than n0: lead L >= ceil((T/2 + 2) L / M) outputs, i.e. lead M >= T/2 + 2 inputs, and
+        // P0 M <= k_done M / L.  With it the ring's base never lies inside a block (in_base only moves to a value this
+        // function returned, and k_done only grows), so the frames the kernels read as zero in front of the ring
+        // (FftArgs::in_lo) are the true zeros before the stream's start and nothing else.  Even a base at n0 would only
+        // reach discarded outputs — every kept output >= k_done has its whole support [n0, ...) in the ring — but the
+        // rounding of a block depends on all of its input, and a result must not depend on when the ring was compacted
+        // (a pooled ring, clear(), another element size).
+        const int64_t blk0 = ((int64_t)(s->k_done / (uint64_t)p.L) - s->fft_lead) * p.M;
+        return std::min(n0, blk0);
+    }
     return n0;
 }
 
@@ -1072,6 +1090,14 @@ static const char *stream_new(hipsoxr_plan *plan, bool own, unsigned ch, hipsoxr
     if (ch < 1) return "invalid channel count";
     if ((int)io < 0 || (int)io > 7) return "invalid io datatype";
     if ((flags & HIPSOXR_VR) && !plan->p.phases) return "variable-rate streams need an interpolated-phase plan";
+    int32_t fft_lead = 0;
+    if (flags & HIPSOXR_STREAM_FFT) { // whatever the engine cannot serve is refused here, by name: never another engine quietly
+        if (flags & HIPSOXR_VR) return "STREAM_FFT stream: variable-rate streams are not served by the frequency-domain engine";
+        if ((int)io & 4) return "STREAM_FFT stream: split layouts are not served (interleaved device streams only)";
+        if (flags & (HIPSOXR_DEFER | HIPSOXR_RESIDENT | HIPSOXR_AUTO_RESIDENT))
+            return "STREAM_FFT stream: not together with the DEFER / RESIDENT / AUTO_RESIDENT flags (device chunks only)";
+        if (const char *e = fft_stream_refusal(plan->p, (int)io & 3, ch, &fft_lead)) return e;
+    }
     if (device_count() <= 0) return kNoDevice;
     hipsoxr_stream *s = new (std::nothrow) hipsoxr_stream();
     if (!s) return "out of memory";
@@ -1080,6 +1106,10 @@ static const char *stream_new(hipsoxr_plan *plan, bool own, unsigned ch, hipsoxr
     s->defer = (flags & HIPSOXR_DEFER) && !(flags & HIPSOXR_VR) && !s->split;
     s->resident = ((flags & HIPSOXR_RESIDENT) || switches().resident) && !s->defer && !s->split;
     s->resident_auto_ok = !s->resident && !s->defer && !s->split && ((flags & HIPSOXR_AUTO_RESIDENT) || switches().auto_resident);
+    if (flags & HIPSOXR_STREAM_FFT) { // (the environment's resident switches are for host-pointer streams: this one has no such calls)
+        s->fft = true; s->fft_lead = fft_lead;
+        s->resident = s->resident_auto_ok = false;
+    }
     if (flags & HIPSOXR_VR) {
         const double io0 = plan->p.in_rate / plan->p.out_rate;
         if (!(io0 > 9.5367431640625e-07) || !(io0 < 1048576.)) { delete s; return "io ratio out of range for variable rate"; }
@@ -1128,8 +1158,8 @@ static const char *stream_new(hipsoxr_plan *plan, bool own, unsigned ch, hipsoxr
         }
         err = device_bank_ensure(&plan->p, engine_prec(s->elem));
     } while (0);
-    std::snprintf(s->engine_name, sizeof s->engine_name, "hip-gfx950-%s",
-                  engine_prec(s->elem) == 0 ? "f32" : "f64");
+    std::snprintf(s->engine_name, sizeof s->engine_name, "hip-gfx950-%s%s",
+                  s->fft ? "fft-" : "", engine_prec(s->elem) == 0 ? "f32" : "f64");
     if (err) {
         hipsoxr_stream_delete(s);
         return err;
@@ -1246,7 +1276,14 @@ static const char *device_emit_once(hipsoxr_stream *s, void *d_out, size_t olen,
     j.clip_counter = s->d_clips;
     j.dither = (s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER)) ? 1u : 0u;
     j.dither_seed = s->dither_seed;
-    if (v.on) {
+    if (s->fft) {
+        // the chunk's outputs as a job window on the frequency-domain engine — every emission, whatever its size (a
+        // 10-frame call is legal and merely wasteful); not served = an error, never the exact engine
+        bool handled = false;
+        j.kernel = (s->elem == HIPSOXR_I16 || s->elem == HIPSOXR_I32) ? HIPSOXR_KERNEL_FFT_PCM : HIPSOXR_KERNEL_FFT;
+        if (const char *e = launch_fft_window(&s->plan->p, j, s->st, &handled)) return e;
+        if (!handled) return "STREAM_FFT stream: the frequency-domain engine cannot serve this call (plan or layout outside its paired kernels)";
+    } else if (v.on) {
         const i128 T0 = v.pos(s->k_done), S0 = v.step(s->k_done), D = s->k_done < v.k_s + v.n_slew ? v.delta : 0;
         const VrPos vp = {(uint64_t)((u128)T0 >> 64), (uint64_t)(u128)T0, (uint64_t)((u128)S0 >> 64), (uint64_t)(u128)S0,
                           (uint64_t)((u128)D >> 64), (uint64_t)(u128)D};
@@ -1287,7 +1324,7 @@ static bool stream_item_prepare(hipsoxr_stream *s, const void *d_in, size_t ilen
 {
     const Plan &p = s->plan->p;
     *err = nullptr;
-    if (s->vr.on || s->ended || !d_in || !ilen || !d_out || s->ring_on_host || s->split) return false;
+    if (s->vr.on || s->ended || !d_in || !ilen || !d_out || s->ring_on_host || s->split || s->fft) return false; // (fft: the small-launch kernel is the exact engine)
     const uint64_t n_total = s->n_in_total + ilen;
     const uint64_t k_end = k_avail(p, n_total);
     const size_t n = k_end > s->k_done ? (size_t)std::min<uint64_t>(k_end - s->k_done, olen) : 0;
@@ -1475,6 +1512,8 @@ hipsoxr_error_t hipsoxr_streams_process_device(hipsoxr_stream_t *const *handles,
         if (!handles[i]) return "null argument";
         odones[i] = 0;
     }
+    for (size_t i = 0; i < n; ++i)
+        if (handles[i]->fft) return "grouped device calls do not take streams created with the STREAM_FFT flag (call hipsoxr_stream_process_device per handle)";
     hipsoxr_stream *s0 = handles[0];
     // one launch serves streams of ONE plan, element type, channel count and dither setting on one device, constant rate,
     // each with a chunk to append and fewer than 4096 outputs due; anything else goes handle by handle (same results)
@@ -1547,8 +1586,9 @@ hipsoxr_error_t hipsoxr_stream_process(hipsoxr_stream_t *s, const void *in, size
                                        size_t olen, size_t *odone)
 {
     if (!s || !odone) return "null argument";
-    DeviceGuard guard(s->device);
     *odone = 0;
+    if (s->fft) return "host-pointer calls do not take streams created with the STREAM_FFT flag (device chunks only: hipsoxr_stream_process_device)";
+    DeviceGuard guard(s->device);
     ext_sync(s);
     s->own_used = true;
     if (s->split_io && !s->adapt_decided && in && ilen) {
@@ -1717,6 +1757,7 @@ hipsoxr_error_t hipsoxr_oneshot(double in_rate, double out_rate, unsigned num_ch
 {
     if (!odone) return "null argument";
     *odone = 0;
+    if (flags & HIPSOXR_STREAM_FFT) return "the STREAM_FFT flag is for device-chunk streams (host one-shot calls run the canonical order)";
     hipsoxr_stream_t *s = nullptr;
     if (const char *e = hipsoxr_stream_create(in_rate, out_rate, num_channels, io_type, recipe, flags, &s))
         return e;

@@ -13,9 +13,10 @@
 // overlap by more than the filter length, and only the outputs whose whole filter support lies inside the block are
 // kept.  ~70 flop per output instead of 592.  What is neglected is the aliasing of g's stop band (<= -176 dB for VHQ):
 // against the direct form 2.5e-10 relative RMS in float64, ~2e-7 in float32 (FFT rounding) — inside the 1e-6 bar but
-// NOT bit-identical to the canonical order, so this engine serves only whole-signal device jobs (hipsoxr_run_device):
-// float32 / float64 ones, and int16 / int32 ones that name it (HIPSOXR_KERNEL_FFT_PCM); the host surface
-// (soxr.resample / ResampleStream) and integer I/O under AUTO stay on the exact engine.
+// NOT bit-identical to the canonical order, so this engine serves whole-signal device jobs (hipsoxr_run_device) —
+// float32 / float64 ones, and int16 / int32 ones that name it (HIPSOXR_KERNEL_FFT_PCM) — and device-chunk streams that
+// name it at creation (HIPSOXR_STREAM_FFT: every chunk a job WINDOW on the paired kernels, launch_fft_window); the host
+// surface (soxr.resample / ResampleStream), every other stream and integer I/O under AUTO stay on the exact engine.
 //
 // Kernels:
 //   k_fft_block     general path, any 7-smooth plan: one workgroup per block, run-time radix schedule, real FFT through
@@ -537,27 +538,39 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     // ---- store the run: elements [0, valid) of it exist in the column ----------------------------------
     const int64_t remain = out_frames - (outa + v0);
     const int32_t valid = (int32_t)(remain < 0 ? 0 : remain > 2 * (int64_t)hop_out ? 2 * (int64_t)hop_out : remain);
+    // Job window (a.out_lo, stream chunks): the column's outputs below out_lo are not this job's — the first run of a
+    // chunk begins in the middle of a run and of a 16-byte granule, and the bytes in front of it are the caller's (the
+    // previous chunk's result, or somebody else's memory).  Run elements [lo, valid) are the job's.  lo != 0 only in the
+    // pair that holds out_lo (the host keeps out_lo < hop_out: the first pair of a launch), which stores its run element
+    // by element; every other pair — every pair of a whole-signal job — takes the granule path below as it was
+    // (wave-uniform: one scalar branch).
+    const int64_t below = a.out_lo - (outa + v0);
+    const int32_t lo = (int32_t)(below <= 0 ? 0 : below > valid ? valid : below);
     // 16-byte buffer stores: the descriptor starts at the 16-byte granule that holds run[0] (sh elements before it)
     // and ends with the run, so the hardware range check drops what lies beyond the column (and the trips past the
     // run: no trip count, no branches — every LDS read and every store of the thread is in flight at once).  The
     // first granule's sh leading elements belong to the previous run: that one granule goes element by element.
     if constexpr (!PCM) {
-        const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)(ybase - sh)), 0,
-                                                                             __builtin_amdgcn_readfirstlane((valid + sh) * ES), 0x00020000);
-        constexpr int QMAX = (2 * (NB - 1) + EPS - 1 + EPS) / EPS; // 2 hop_out < 2 NB elements, + sh
-        constexpr int LQ = (int)((size_t)LB * sizeof(C) / 16);     // 16-byte granules of the LDS buffer
-        const int tid_out = (int)threadIdx.x;
+        if (lo != 0) {
+            for (int e = lo + (int)threadIdx.x; e < valid; e += NT) ybase[e] = stage[e + sh];
+        } else {
+            const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)(ybase - sh)), 0,
+                                                                                 __builtin_amdgcn_readfirstlane((valid + sh) * ES), 0x00020000);
+            constexpr int QMAX = (2 * (NB - 1) + EPS - 1 + EPS) / EPS; // 2 hop_out < 2 NB elements, + sh
+            constexpr int LQ = (int)((size_t)LB * sizeof(C) / 16);     // 16-byte granules of the LDS buffer
+            const int tid_out = (int)threadIdx.x;
 #pragma unroll
-        for (int it = 0; it < (QMAX + NT - 1) / NT; ++it) {
-            const int q = tid_out + it * NT;
-            const V16 v = *reinterpret_cast<const V16 *>(stage + EPS * (q < LQ ? q : LQ - 1));
-            if (q == 0 && sh != 0) {
-                const IO *e = reinterpret_cast<const IO *>(&v);
+            for (int it = 0; it < (QMAX + NT - 1) / NT; ++it) {
+                const int q = tid_out + it * NT;
+                const V16 v = *reinterpret_cast<const V16 *>(stage + EPS * (q < LQ ? q : LQ - 1));
+                if (q == 0 && sh != 0) {
+                    const IO *e = reinterpret_cast<const IO *>(&v);
 #pragma unroll
-                for (int c = 0; c < EPS; ++c)
-                    if (c >= sh && c - sh < valid) ybase[c - sh] = e[c];
-            } else {
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), ro, q * 16, 0, FFT_STORE_AUX);
+                    for (int c = 0; c < EPS; ++c)
+                        if (c >= sh && c - sh < valid) ybase[c - sh] = e[c];
+                } else {
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u_t, v), ro, q * 16, 0, FFT_STORE_AUX);
+                }
             }
         }
     } else {
@@ -572,7 +585,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
                                                                              __builtin_amdgcn_readfirstlane(run_bytes), 0x00020000);
         constexpr int QMAX = (2 * (NB - 1) + EPS - 1 + EPS) / EPS;
         constexpr int LQ = (int)((size_t)LB * sizeof(C) / (EPS * sizeof(ST))); // granules' worth of staged values in the LDS buffer
-        const int64_t k_run = outa + v0 - sh; // output index of staged element 0
+        const int64_t k_run = a.out_abs0 + outa + v0 - sh; // ABSOLUTE output index of staged element 0 (the dither key)
         const bool dither = a.dither != 0;
         const uint32_t dch = ch + a.ch0;
         unsigned nclip = 0;
@@ -581,35 +594,39 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
             IO r;
             if constexpr (ES == 2) r = pcm_quantize_i16(v, dither, a.seed, dch, k_run + e, clip);
             else r = pcm_quantize_i32(v, clip);
-            nclip += (clip && e >= sh && e - sh < valid) ? 1u : 0u;
+            nclip += (clip && e >= sh + lo && e - sh < valid) ? 1u : 0u; // (only stored elements count)
             return r;
         };
-        if (ES == 2 && ((valid + sh) & 1) && valid > 0 && threadIdx.x == NT - 1) {
-            const unsigned keep = nclip; // (its granule's thread counts it)
-            ybase[valid - 1] = conv(stage[valid - 1 + sh], valid - 1 + sh);
-            nclip = keep;
-        }
-        const int tid_out = (int)threadIdx.x;
-#pragma unroll
-        for (int it = 0; it < (QMAX + NT - 1) / NT; ++it) {
-            const int q = tid_out + it * NT;
-            const ST *src = stage + EPS * (q < LQ ? q : LQ - 1);
-            IO e[EPS];
-#pragma unroll
-            for (int c = 0; c < EPS; c += 16 / (int)sizeof(ST)) {
-                const typename PairTabs<Real>::V16 v = *reinterpret_cast<const typename PairTabs<Real>::V16 *>(src + c);
-                const ST *pv = reinterpret_cast<const ST *>(&v);
-#pragma unroll
-                for (int i = 0; i < 16 / (int)sizeof(ST); ++i) e[c + i] = conv(pv[i], q * EPS + c + i);
+        if (lo != 0) { // the pair that holds the job's lower bound: element by element (see `lo`)
+            for (int e = lo + (int)threadIdx.x; e < valid; e += NT) ybase[e] = conv(stage[e + sh], e + sh);
+        } else {
+            if (ES == 2 && ((valid + sh) & 1) && valid > 0 && threadIdx.x == NT - 1) {
+                const unsigned keep = nclip; // (its granule's thread counts it)
+                ybase[valid - 1] = conv(stage[valid - 1 + sh], valid - 1 + sh);
+                nclip = keep;
             }
-            if (q == 0 && sh != 0) {
+            const int tid_out = (int)threadIdx.x;
 #pragma unroll
-                for (int c = 0; c < EPS; ++c)
-                    if (c >= sh && c - sh < valid) ybase[c - sh] = e[c];
-            } else {
-                v4u_t v;
-                __builtin_memcpy(&v, e, 16);
-                __builtin_amdgcn_raw_buffer_store_b128(v, ro, q * 16, 0, FFT_STORE_AUX);
+            for (int it = 0; it < (QMAX + NT - 1) / NT; ++it) {
+                const int q = tid_out + it * NT;
+                const ST *src = stage + EPS * (q < LQ ? q : LQ - 1);
+                IO e[EPS];
+#pragma unroll
+                for (int c = 0; c < EPS; c += 16 / (int)sizeof(ST)) {
+                    const typename PairTabs<Real>::V16 v = *reinterpret_cast<const typename PairTabs<Real>::V16 *>(src + c);
+                    const ST *pv = reinterpret_cast<const ST *>(&v);
+#pragma unroll
+                    for (int i = 0; i < 16 / (int)sizeof(ST); ++i) e[c + i] = conv(pv[i], q * EPS + c + i);
+                }
+                if (q == 0 && sh != 0) {
+#pragma unroll
+                    for (int c = 0; c < EPS; ++c)
+                        if (c >= sh && c - sh < valid) ybase[c - sh] = e[c];
+                } else {
+                    v4u_t v;
+                    __builtin_memcpy(&v, e, 16);
+                    __builtin_amdgcn_raw_buffer_store_b128(v, ro, q * 16, 0, FFT_STORE_AUX);
+                }
             }
         }
         if (nclip && a.clip_counter) atomicAdd((unsigned long long *)a.clip_counter, (unsigned long long)nclip);
@@ -710,6 +727,10 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     const int32_t v0 = a.v0, v1 = a.v0 + hop_out;
     const int64_t pa = (CP ? 1 : 2) * bx * a.hop_periods - a.lead_periods; // first period of the (first) block
     const int64_t ina = pa * a.M, outa = pa * a.L;
+    // job window (a.out_lo, stream chunks): local outputs below vlo are not the job's and are not stored (v0 for every
+    // block but the one that holds out_lo; the host keeps out_lo < hop_out, so of a pair of blocks only the first is cut)
+    const int64_t below = a.out_lo - outa;
+    const int32_t vlo = (int32_t)(below <= v0 ? v0 : below > v1 ? v1 : below);
 
     // ---- forward: z[n] = x_c[n] + i x_{c+1}[n]  (CP)  or  x_a[n] + i x_b[n]  (two blocks), first pass straight from HBM
     if (ina >= a.in_lo) {
@@ -749,15 +770,15 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     auto h_load = [&](int j, int t) -> C { return spectrum_load<Spec, Real>(cur, rh, j, t); };
     Spec::inv(FFT_STAMP_ARGS cur, PairTabs<Real>::wb(a), h_load, [&](int o, int t, C wv) {
         const int n = o + t * (NB / Spec::RB2);
-        if (n >= v0 && n < v1) {
+        if (n >= (CP ? vlo : v0) && n < v1) {
             if constexpr (PCM) {
-                const int64_t k = outa + n; // (>= 0: n >= v0)
-                const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, k, k < a.out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, k, k < a.out_frames);
+                const int64_t k = outa + n; // (>= 0: n >= v0); the dither key is the ABSOLUTE index
+                const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, a.out_abs0 + k, k < a.out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, a.out_abs0 + k, k < a.out_frames);
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)l | ((unsigned)r << 16), ro, (n - v0) * ofb, 0, 0);
             } else if constexpr (CP) {
                 CpIo<Real>::store(wv, ro, (n - v0) * ofb); // frame outa + n holds (y_c, y_{c+1})
             } else {
-                buf_store_real(wv.x, ro, (n - v0) * ofb);             // block a
+                if (n >= vlo) buf_store_real(wv.x, ro, (n - v0) * ofb); // block a
                 buf_store_real(wv.y, ro, (n - v0 + hop_out) * ofb);   // block b: hop_out frames further
             }
         }
@@ -858,12 +879,20 @@ void fft_release(const Plan *p)
         } else ++i;
 }
 
-static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_k = 0)
+// Outputs a block discards at either end, in whole periods at its front: the filter support [n_k, n_k + T) of a kept
+// output lies inside the block.  A function of the plan alone — the same for every block size of a ratio.
+static int32_t fft_lead_periods(const Plan &p)
 {
-    FftGeom g;
+    const int64_t disc = ((int64_t)(p.T / 2 + 2) * p.L + p.M - 1) / p.M;
+    return (int32_t)((disc + p.L - 1) / p.L);
+}
+
+// Block geometry (arithmetic only; fft_build adds the device tables).  False: no admissible block.
+static bool fft_geometry(const Plan &p, FftGeom &g, bool small, int force_k)
+{
     const int64_t L = p.L, M = p.M;
     const int32_t T = p.T;
-    if (p.q.bits == 0.) { *out = g; return nullptr; } // QQ: not worth a transform
+    if (p.q.bits == 0.) return false; // QQ: not worth a transform
     // block of k periods: candidates are power-of-two k with 7-smooth even half-lengths; take the largest block whose
     // transforms stay <= 2600 points (one 20 KB LDS buffer, least overlap waste), else the smallest admissible one
     for (int k = force_k ? force_k : 1; k <= (force_k ? force_k : 4096); k *= 2) {
@@ -881,20 +910,28 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
         g.nA = (int32_t)ra.size(); g.nB = (int32_t)rb.size();
         for (int i = 0; i < 8; ++i) { g.radA[i] = i < g.nA ? ra[i] : 1; g.radB[i] = i < g.nB ? rb[i] : 1; }
     }
-    if (!g.k) { *out = g; return nullptr; }
+    if (!g.k) return false;
     // outputs whose filter support [n_k, n_k + T) lies inside the block: discard ceil((T/2+2)*L/M)
     // outputs at either end, keep a whole number of periods
     const int64_t disc = ((int64_t)(T / 2 + 2) * L + M - 1) / M;
-    g.lead_periods = (int32_t)((disc + L - 1) / L);
+    g.lead_periods = fft_lead_periods(p);
     g.hop_periods = (int32_t)((g.N_out - disc - (int64_t)g.lead_periods * L) / L);
-    if (g.hop_periods < 1) { *out = g; return nullptr; }
+    if (g.hop_periods < 1) return false;
     g.v0 = (int32_t)(g.lead_periods * L);
     g.hop_out = (int32_t)(g.hop_periods * L);
     g.lds_bytes = (size_t)(std::max(g.A, g.B) + 8) * sizeof(float2);
-    if (g.lds_bytes > 150 * 1024) { *out = g; return nullptr; }
+    if (g.lds_bytes > 150 * 1024) return false;
     // a block must keep a worthwhile share of its outputs (long filters on short blocks do not)
-    if (force_k && 2 * (int64_t)g.hop_out < g.N_out) { *out = g; return nullptr; }
+    if (force_k && 2 * (int64_t)g.hop_out < g.N_out) return false;
+    return true;
+}
 
+static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_k = 0)
+{
+    FftGeom g;
+    if (!fft_geometry(p, g, small, force_k)) { *out = g; return nullptr; }
+    const int64_t L = p.L;
+    const int32_t T = p.T;
     const int A = g.A, B = g.B;
     std::vector<float2> tab((size_t)A + B + (A + 1) + B + (B + 1) + g.N_in + g.N_out + (B + 2) / 2 + 1);
     float2 *WA = tab.data(), *WB = WA + A, *P = WB + B, *Q = P + (A + 1), *Hs = Q + B;
@@ -949,43 +986,17 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
     return nullptr;
 }
 
-// Whole-signal float32 / float64 job (or an int16 / int32 one that names the engine)?  (zero-extended signal starting at absolute index 0, all outputs)
-bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
-{
-    // what the method neglects is the aliasing of the filter's stop band: only recipes whose stop band
-    // is far below the 1e-6 bar qualify (HQ 128 dB, VHQ 177 dB; MQ/LQ at 104 dB do not)
-    // (integer samples only by name — HIPSOXR_KERNEL_FFT_PCM: AUTO keeps them on the canonical order, bit for bit)
-    const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32) : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64);
-    return p.phases == 0 && p.att_db >= 120. && elem_ok && j.in_abs0 == 0 &&
-           j.out_k0 == 0 && (uint64_t)j.out_frames <= plan_out_len(p, (uint64_t)j.in_frames);
-}
-
-// (job.in_abs0 != 0 — in[0] is sample in_abs0 of a column that is zero outside [in_abs0, in_abs0 + in_frames) — is served
-// for the two-stage form's inner calls; the public paths come here through fft_job_eligible, which wants 0.)
-const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0)
-{
-    *handled = false;
-    // geometry cache key: (plan, variant) with variant 0 = default search, 1 = small-block search,
-    // 2 + i = forced k of paired-kernel entry i
-    auto get = [&](int variant, int force_k, FftGeom *g) -> const char * {
-        std::lock_guard<std::mutex> lk(g_fft_mu);
-        for (auto &e : g_fft)
-            if (e.first.first == p && e.first.second == variant) { *g = e.second; return nullptr; }
-        if (const char *err = fft_build(*p, g, variant == 1, force_k)) return err;
-        g_fft.push_back({{p, variant}, *g});
-        return nullptr;
-    };
-    // ---- paired-block kernels: compile-time schedules for the common ratios -------------------
-    struct PairEntry {
-        int64_t L, M; int k; int small; /* 0: full-size blocks, 1: half-size (small jobs), 2: quarter-size (smaller still) */
-        unsigned nt;
-        void (*kern2)(FftArgs); void (*kern2d)(FftArgs); // unit-stride columns, float32 / float64
-        void (*kern2fd)(FftArgs);                        // float32 I/O on float64 arithmetic (HIPSOXR_KERNEL_FFT_F64)
-        void (*kcp)(FftArgs); void (*kcpd)(FftArgs);     // channel-pair mode (interleaved data), float32 / float64
-        void (*kst)(FftArgs); void (*kstd)(FftArgs);     // strided columns, two blocks per transform
-        void (*kern2i16)(FftArgs); void (*kern2i32)(FftArgs); // integer samples (HIPSOXR_KERNEL_FFT_PCM): unit-stride columns,
-        void (*kcpi16)(FftArgs);                         // int16 on float32 / int32 on float64 arithmetic; int16 channel pairs
-    };
+// ---- paired-block kernels: compile-time schedules for the common ratios -------------------
+struct PairEntry {
+    int64_t L, M; int k; int small; /* 0: full-size blocks, 1: half-size (small jobs), 2: quarter-size (smaller still) */
+    unsigned nt;
+    void (*kern2)(FftArgs); void (*kern2d)(FftArgs); // unit-stride columns, float32 / float64
+    void (*kern2fd)(FftArgs);                        // float32 I/O on float64 arithmetic (HIPSOXR_KERNEL_FFT_F64)
+    void (*kcp)(FftArgs); void (*kcpd)(FftArgs);     // channel-pair mode (interleaved data), float32 / float64
+    void (*kst)(FftArgs); void (*kstd)(FftArgs);     // strided columns, two blocks per transform
+    void (*kern2i16)(FftArgs); void (*kern2i32)(FftArgs); // integer samples (HIPSOXR_KERNEL_FFT_PCM): unit-stride columns,
+    void (*kcpi16)(FftArgs);                         // int16 on float32 / int32 on float64 arithmetic; int16 channel pairs
+};
 #define HIPSOXR_PAIR(L, M, k, small, NA, NB, NT) \
     {L, M, k, small, NT, k_fft_pair2<PairOf<NA, NB, NT>, float>, k_fft_pair2<PairOf<NA, NB, NT>, double>, \
      k_fft_pair2<PairOf<NA, NB, NT>, double, float>, \
@@ -993,6 +1004,8 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
      k_fft_strided2<PairOf<NA, NB, NT>, float, false>, k_fft_strided2<PairOf<NA, NB, NT>, double, false>, \
      k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>, k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>, \
      k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>}
+static const PairEntry *fft_pairs(int *n)
+{
     static const PairEntry pairs[] = {
         // L, M (out/in = L/M), periods per block, small-job variant, N_in, N_out, threads
         HIPSOXR_PAIR(147, 160, 32, false, 5120, 4704, 384), HIPSOXR_PAIR(147, 160, 16, true, 2560, 2352, 384),   // 48k -> 44.1k
@@ -1017,7 +1030,74 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
         HIPSOXR_PAIR(40, 147, 32, false, 4704, 1280, 384), HIPSOXR_PAIR(147, 40, 32, false, 1280, 4704, 384),    // 44.1k <-> 12k, 88.2k <-> 24k
         HIPSOXR_PAIR(4, 3, 1280, false, 3840, 5120, 384), HIPSOXR_PAIR(3, 4, 1280, false, 5120, 3840, 384),      // 24k <-> 32k, 12k <-> 16k, 48k <-> 64k
     };
+    *n = (int)(sizeof pairs / sizeof pairs[0]);
+    return pairs;
+}
 #undef HIPSOXR_PAIR
+
+// Whole-signal float32 / float64 job (or an int16 / int32 one that names the engine)?  (zero-extended signal starting at absolute index 0, all outputs)
+bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
+{
+    // what the method neglects is the aliasing of the filter's stop band: only recipes whose stop band
+    // is far below the 1e-6 bar qualify (HQ 128 dB, VHQ 177 dB; MQ/LQ at 104 dB do not)
+    // (integer samples only by name — HIPSOXR_KERNEL_FFT_PCM: AUTO keeps them on the canonical order, bit for bit)
+    const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32) : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64);
+    return p.phases == 0 && p.att_db >= 120. && elem_ok && j.in_abs0 == 0 &&
+           j.out_k0 == 0 && (uint64_t)j.out_frames <= plan_out_len(p, (uint64_t)j.in_frames);
+}
+
+// Streams on this engine (HIPSOXR_STREAM_FFT): what it cannot serve is refused when the stream is created, by name.
+// The chunks of a stream are windows of one column (launch_fft_window), served by the paired kernels alone — so the
+// ratio must be in their schedule table for every element type, and the layout one they take: interleaved frames of
+// `ch` channels = unit-stride columns (mono), channel pairs (even counts) or strided columns (odd counts, floats).
+// *lead_periods: periods a block starts before its first kept output (what the stream's ring must keep, engine.cpp).
+const char *fft_stream_refusal(const Plan &p, int elem, uint32_t ch, int32_t *lead_periods)
+{
+    *lead_periods = 0;
+    if (p.phases) return "STREAM_FFT stream: the ratio has no exact polyphase bank (interpolated-phase plan); the frequency-domain engine serves streams of exact-ratio plans";
+    if (p.att_db < 120.) return "STREAM_FFT stream: the frequency-domain engine serves HQ and VHQ only (recipes below 120 dB are not 1e-6-class on it)";
+    if (elem == HIPSOXR_I32 && ch > 1) return "STREAM_FFT stream: int32 streams are served with one channel only (as HIPSOXR_KERNEL_FFT_PCM: unit-stride columns)";
+    if (elem == HIPSOXR_I16 && ch > 1 && ch % 2) return "STREAM_FFT stream: int16 streams are served with one channel or an even channel count (as HIPSOXR_KERNEL_FFT_PCM: interleaved channel pairs)";
+    int n = 0;
+    const PairEntry *pairs = fft_pairs(&n);
+    const PairEntry *big = nullptr;
+    for (int i = 0; i < n; ++i)
+        if (pairs[i].L == p.L && pairs[i].M == p.M && !pairs[i].small) big = &pairs[i];
+    FftGeom g;
+    if (!big || !fft_geometry(p, g, false, big->k))
+        return "STREAM_FFT stream: the ratio is outside the paired-kernel schedule table of the frequency-domain engine (fft.hip)";
+    // the kernels' 32-bit byte offsets over a pair of blocks at the frame stride (launch_fft: cp2 / st2ok)
+    if (2 * (int64_t)std::max(g.N_in, g.N_out) * (int64_t)ch * (int64_t)elem_size(elem) >= (1LL << 30))
+        return "STREAM_FFT stream: too many channels for the frequency-domain engine's interleaved kernels";
+    *lead_periods = g.lead_periods; // (fft_lead_periods: the same for every block size of the ratio)
+    return nullptr;
+}
+
+// (job.in_abs0 != 0 — in[0] is sample in_abs0 of a column that is zero outside [in_abs0, in_abs0 + in_frames) — is served
+// for the two-stage form's inner calls; the public paths come here through fft_job_eligible, which wants 0.)
+// window (launch_fft_window, stream chunks): the job is outputs [out_k0, out_k0 + out_frames) of the column.  The paired
+// kernels get their origin moved to the period boundary P0 = floor(out_k0 / L): `in` / `out` are shifted by P0 M / P0 L
+// frames, so block 0 starts lead_periods before P0 and the block arithmetic is the whole-signal job's; the one thing the
+// kernels do for it is drop the outputs below out_lo = out_k0 - P0 L (< L <= hop_out: inside the first block's run) and
+// key the dither by P0 L + local index.  Served by k_fft_pair2 / k_fft_strided2 only: *handled stays false otherwise.
+static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0, bool window)
+{
+    *handled = false;
+    const int64_t P0 = window ? j.out_k0 / p->L : 0, out_lo = window ? j.out_k0 - P0 * p->L : 0;
+    const int64_t span = out_lo + j.out_frames; // outputs from the origin to the end of the job: what blocks are counted over
+    // geometry cache key: (plan, variant) with variant 0 = default search, 1 = small-block search,
+    // 2 + i = forced k of paired-kernel entry i
+    auto get = [&](int variant, int force_k, FftGeom *g) -> const char * {
+        std::lock_guard<std::mutex> lk(g_fft_mu);
+        for (auto &e : g_fft)
+            if (e.first.first == p && e.first.second == variant) { *g = e.second; return nullptr; }
+        if (const char *err = fft_build(*p, g, variant == 1, force_k)) return err;
+        g_fft.push_back({{p, variant}, *g});
+        return nullptr;
+    };
+    // ---- paired-block kernels: compile-time schedules for the common ratios (fft_pairs) -------------------
+    int n_pairs = 0;
+    const PairEntry *pairs = fft_pairs(&n_pairs);
     const bool no_pair = switches().fft_no_pair;
     const uint64_t cols_p = (uint64_t)j.n_clips * j.n_channels;
     // f64: the ARITHMETIC is float64 (block size, LDS bytes per point, table set) — float64 jobs, and float32 jobs that
@@ -1033,7 +1113,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
     if (!no_pair && cols_p <= 65535) {
         const PairEntry *big = nullptr, *sml = nullptr, *tiny = nullptr;
         int big_i = 0, sml_i = 0, tiny_i = 0;
-        for (int i = 0; i < (int)(sizeof pairs / sizeof pairs[0]); ++i)
+        for (int i = 0; i < n_pairs; ++i)
             if (pairs[i].L == p->L && pairs[i].M == p->M) {
                 if (pairs[i].small == 2) { tiny = &pairs[i]; tiny_i = i; }
                 else if (pairs[i].small) { sml = &pairs[i]; sml_i = i; }
@@ -1046,7 +1126,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
             if (g.ok && sml) {
                 // few work items (one 60 s clip = 300 pairs): half-size blocks give twice as many,
                 // shorter workgroups, at the price of more overlap
-                const int64_t wgs = ((j.out_frames + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
+                const int64_t wgs = ((span + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
                 // (float64: LDS is 16 bytes per point — the half-size blocks keep four workgroups per CU)
                 // (7056-point blocks: 56 KB of LDS, two workgroups per CU — the 35 KB blocks of the k = 10 geometry keep
                 //  four and win at every size: 44.1k -> 16k VHQ, 8 x 60 s planar 41 vs 68 us, 80 x 60 s 427 vs 638 us)
@@ -1061,7 +1141,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
             // latency of one workgroup plus what queues behind it; quarter-size blocks (10 KB of LDS, 32 % overlap)
             // shorten both: 2 s clip 7.4 -> 6.5 us, 10 s HQ 7.6 -> 6.2 us, 30 s 9.0 -> 7.7 us (60 s: 10.85 vs 10.73 us).
             if (use == sml && tiny && !switches().fft_large_only && !switches().fft_no_tiny) {
-                const int64_t wgs = ((j.out_frames + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
+                const int64_t wgs = ((span + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
                 // (float32: at 612 pairs — the 60 s clip — the two sizes are within 1 %.  float64: 16 bytes per point, and
                 //  the 20 KB blocks win at every size — 60 s mono 27.1 -> 21.6 us, 64 x 10 s 236 -> 202 us, stereo 60 s 47 -> 37 us)
                 if (f64 || wgs <= 500) {
@@ -1072,7 +1152,11 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
             }
             if (use) {
                 FftArgs a;
-                a.in = (const char *)j.in - j.in_abs0 * j.in_frame_stride * (int64_t)elem_size(j.elem); a.out = j.out; // (sample 0 of the columns)
+                // (sample 0 of the columns; window: frame P0 M / P0 L of them.  int16 channel pairs: the shift is a whole
+                //  number of frames, so with the even frame strides cp_pcm_ok asks for, the 4-byte alignment it checks on
+                //  j.in / j.out holds for the shifted pointers too)
+                a.in = (const char *)j.in - (j.in_abs0 - P0 * p->M) * j.in_frame_stride * (int64_t)elem_size(j.elem);
+                a.out = (char *)j.out - out_lo * j.out_frame_stride * (int64_t)elem_size(j.elem);
                 auto set_geom = [](FftArgs &a, const FftGeom &g) {
                     a.WA = g.dev; a.WB = a.WA + g.A; a.P = a.WB + g.B; a.Q = a.P + (g.A + 1); a.Hs = a.Q + g.B;
                     a.WA2 = a.Hs + (g.B + 1); a.WB2 = a.WA2 + g.N_in;
@@ -1087,10 +1171,12 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
                 a.n_clips = j.n_clips; a.n_channels = j.n_channels;
                 a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
                 a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-                a.in_lo = j.in_abs0; a.in_frames = j.in_abs0 + j.in_frames; a.out_frames = j.out_frames;
+                a.in_lo = j.in_abs0 - P0 * p->M; a.in_frames = a.in_lo + j.in_frames; a.out_frames = span;
+                a.out_lo = out_lo; a.out_abs0 = P0 * p->L;
+                if (out_lo >= g.hop_out) return "internal: the job window starts beyond the first block"; // (cannot happen: out_lo < L <= hop_out)
                 a.clip_tab = j.clip_table_dev;
                 a.clip_counter = pcm ? j.clip_counter : nullptr; a.dither = j.dither; a.seed = j.dither_seed; a.ch0 = ch0;
-                const int64_t n_blocks = (j.out_frames + g.hop_out - 1) / g.hop_out;
+                const int64_t n_blocks = (span + g.hop_out - 1) / g.hop_out;
                 if (n_blocks > 2147483647LL) return "job too long for one launch";
                 // interleaved data with an even channel count: pair channels (one (Real, Real) word per frame)
                 const size_t esz = elem_size(j.elem);
@@ -1131,7 +1217,9 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
                 // that the last, partly filled round costs more than the form gains; and a single pair's latency is
                 // longer than on the 6-wave workgroups of k_fft_pair2).
                 FftWaveKernel wk;
-                if (v2ok && !f64 && !pcm && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
+                // (never a window, and never a column with frames missing in FRONT — a.in_lo > 0, data-dependent front
+                //  extension: k_fft_wave's front guard covers the lead-in of block 0 only)
+                if (v2ok && !f64 && !pcm && !window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
                     FftGeom gw;
                     if (const char *err = get(1000 + wk.k, wk.k, &gw)) return err;
                     const int64_t pairs_w = gw.ok ? ((j.out_frames + gw.hop_out - 1) / gw.hop_out + 1) / 2 : 0;
@@ -1181,7 +1269,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
         }
     }
     // ---- general path: one block per workgroup ---------------------------------------------------
-    if (f64 || pcm || j.clip_table) return nullptr; // float32 only, no ragged batches
+    if (f64 || pcm || j.clip_table || window) return nullptr; // float32 only, no ragged batches, whole signals
     FftGeom g;
     if (const char *err = get(0, 0, &g)) return err;
     if (g.ok) {
@@ -1201,6 +1289,7 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
     a.WA2d = a.WB2d = nullptr; a.Hrd = nullptr; a.clip_tab = nullptr;
     a.chpair = 0; a.pairs_per_col = 0; a.xcd_map = 0;
     a.clip_counter = nullptr; a.dither = a.seed = a.ch0 = 0;
+    a.out_lo = a.out_abs0 = 0;
     a.A = g.A; a.B = g.B; a.nA = g.nA; a.nB = g.nB;
     for (int i = 0; i < 8; ++i) { a.radA[i] = g.radA[i]; a.radB[i] = g.radB[i]; }
     a.L = p->L; a.M = p->M;
@@ -1220,6 +1309,16 @@ const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *hand
     HIP_TRY(hipGetLastError());
     *handled = true;
     return nullptr;
+}
+
+const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0)
+{
+    return launch_fft_impl(p, j, stream, handled, ch0, false);
+}
+
+const char *launch_fft_window(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0)
+{
+    return launch_fft_impl(p, j, stream, handled, ch0, true);
 }
 
 #endif // host part (FFT_PART != 1)

@@ -291,6 +291,10 @@ struct FftArgs {
     uint64_t *clip_counter;  // device counter of saturated outputs, or nullptr
     uint32_t dither, seed;   // int16: TPDF dither keyed by (seed, channel + ch0, absolute output index)
     uint32_t ch0;            // index of the job's channel 0 in the caller's whole signal
+    // job window (stream chunks, launch_fft_window): the paired kernels' origin — `in` / `out` sample 0, block 0 — is a
+    // period boundary P0 of the column, not its start; every index above is relative to it
+    int64_t out_lo;          // outputs below out_lo are not part of the job: nothing is stored, nothing counted (0: whole signals)
+    int64_t out_abs0;        // absolute output index of the origin, P0 * L (the dither key of integer jobs; 0: whole signals)
 };
 
 // fftwave.hip: the one-wave-per-block-pair kernel of a ratio — block size (periods), the geometry it is compiled for,

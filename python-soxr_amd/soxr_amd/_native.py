@@ -58,6 +58,7 @@ NO_DITHER = 8
 DEFER = 64
 RESIDENT = 128
 AUTO_RESIDENT = 256
+STREAM_FFT = 512  # device-chunk streams on the frequency-domain engine (TensorStream(engine="fft"))
 KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA, KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM = range(10)
 
 
@@ -134,7 +135,7 @@ def version():
 
 # The ctypes mirrors above (Job = hipsoxr_job_t with its clip_table fields) are laid out for this ABI generation: a
 # library of another generation would read garbage from the struct's tail, so loading one is an import error.
-ABI_VERSION = "hipsoxr-0.6"
+ABI_VERSION = "hipsoxr-0.7"
 if not version().startswith(ABI_VERSION):
     raise ImportError(f"{LIB_PATH} is {version()!r}; this package binds {ABI_VERSION}.x (rebuild: python-soxr_amd/build.sh)")
 
