@@ -33,17 +33,19 @@ P8=""
 if [ -z "$HIPSOXR_VARIANT" ]; then
   "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -DHIPSOXR_DEBUG_SWITCHES -c "$SRC/kernels.hip" -o "$OBJ/kernels_dbg.o" & P8=$!
 fi
-# (fft.hip in five translation units: see "Three translation units" there; 3 and 4 hold the integer-sample kernels)
+# (fft.hip in six translation units: see "Three translation units" there; 3 and 4 hold the integer-sample kernels, 5 the
+#  float32-only block sizes of one-round jobs)
 FFTFLAGS="${HIPSOXR_FFTFLAGS:--ffp-contract=fast -fno-slp-vectorize}"
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=0 -c "$SRC/fft.hip" -o "$OBJ/fft.o" & P4=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=1 -c "$SRC/fft.hip" -o "$OBJ/fft1.o" & P6=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=2 -c "$SRC/fft.hip" -o "$OBJ/fft2.o" & P7=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=3 -c "$SRC/fft.hip" -o "$OBJ/fft3.o" & P11=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=4 -c "$SRC/fft.hip" -o "$OBJ/fft4.o" & P12=$!
+"$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=5 -c "$SRC/fft.hip" -o "$OBJ/fft5.o" & P13=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/twostage.hip" -o "$OBJ/twostage.o" & P9=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/fftwave.hip" -o "$OBJ/fftwave.o" & P10=$!
-wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12   # set -e: any failed compile aborts here
-OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/soxr_abi.o"
+wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13   # set -e: any failed compile aborts here
+OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/soxr_abi.o"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC $OBJS -o "$OUT"
 # The same engine under libsoxr's name: what `find_library(SOXR_LIBRARY NAMES soxr)` of the
 # reference's USE_SYSTEM_LIBSOXR build picks up (reference CMakeLists.txt:83-93).

@@ -91,6 +91,7 @@ struct Switches {
     bool fft_large_only = false;  // HIPSOXR_FFT_LARGE_ONLY   never the small-block variant
     bool fft_small_only = false;  // HIPSOXR_FFT_SMALL_ONLY   always the small-block variant
     bool fft_no_tiny = false;     // HIPSOXR_FFT_NO_TINY      never the quarter-size blocks
+    int dbg_fft_k = 0;            // HIPSOXR_DEBUG_FFT_K      one-round float32 jobs (fft.hip, kOneRoundCost): k > 0 forces blocks of k periods, k < 0 = the size thresholds alone
     bool fft_no_wave = false;     // HIPSOXR_FFT_NO_WAVE      never the one-wave-per-pair kernel (fftwave.hip)
     int dbg_wave_min = 0;         // HIPSOXR_DEBUG_WAVE_MIN   ... from this many block pairs up (default 4096)
     int dbg_wave_slots = 0;       // HIPSOXR_DEBUG_WAVE_SLOTS ... at most this many persistent waves per launch (default: what the chip holds)

@@ -361,7 +361,8 @@ template <int N> struct Sched;
     X(4410, 21, 14, 15, false) X(4096, 16, 16, 16, true) X(3840, 16, 16, 15, true) X(3584, 14, 16, 16, false)        \
     X(3528, 21, 12, 14, false) X(2688, 21, 16, 8, false) X(2560, 16, 16, 10, true) X(2352, 21, 16, 7, false)         \
     X(2048, 16, 16, 8, true) X(1792, 7, 16, 16, false) X(1024, 16, 8, 8, true) X(1600, 16, 10, 10, true)             \
-    X(1280, 5, 16, 16, false) X(1176, 21, 8, 7, false) X(896, 7, 16, 8, false)
+    X(1280, 5, 16, 16, false) X(1176, 21, 8, 7, false) X(896, 7, 16, 8, false)                                        \
+    X(2240, 16, 14, 10, true) X(2058, 21, 14, 7, false) X(3200, 16, 20, 10, true) X(2940, 21, 14, 10, false)
 #define HIPSOXR_SCHED(N, r0, r1, r2, swz) \
     template <> struct Sched<N> { static constexpr int R0 = r0, R1 = r1, R2 = r2; static constexpr bool SWZ = swz; };
 HIPSOXR_SCHED_LIST(HIPSOXR_SCHED)
@@ -795,7 +796,8 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 // float32-on-float64, k_fft_strided2 x 2 in float32 and float64); compiled in one piece they are the build's critical
 // path.  build.sh compiles this file three times: -DFFT_PART=0 = everything except the kernels of the schedules listed
 // here (declared extern), -DFFT_PART=1 / =2 = the templates above plus exactly the kernels of one of the two lists, no
-// host code (=3 / =4: the integer-sample kernels of the same lists, below).  Without FFT_PART: one piece.
+// host code (=3 / =4: the integer-sample kernels of the same lists, =5: the float32-only block sizes of one-round jobs,
+// below).  Without FFT_PART: one piece.
 // ---------------------------------------------------------------------------------------------
 #define HIPSOXR_PART1_SPECS(X) X(4096, 2048, 256) X(2048, 4096, 256) X(2048, 1024, 256) X(1024, 2048, 256) X(5376, 1792, 384) X(1792, 5376, 384) X(5376, 3584, 384) X(3584, 5376, 384) X(2688, 896, 384) X(896, 2688, 384) X(2688, 1792, 384) X(1792, 2688, 384) X(5120, 1280, 320) X(1280, 5120, 320) X(5376, 896, 384) X(896, 5376, 384)
 #define HIPSOXR_PART2_SPECS(X) X(7056, 5120, 448) X(5120, 7056, 448) X(4704, 2560, 384) X(2560, 4704, 384) X(5120, 2352, 384) X(2352, 5120, 384) X(7056, 1280, 448) X(1280, 7056, 448) X(5120, 1176, 320) X(1176, 5120, 320) X(3528, 5120, 384) X(5120, 3528, 384) X(4704, 1280, 384) X(1280, 4704, 384) X(3840, 5120, 384) X(5120, 3840, 384)
@@ -813,12 +815,22 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>(FftArgs);             \
     HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>(FftArgs);            \
     HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>(FftArgs);
+// ... and ONE for the block sizes that exist for one-round float32 jobs only (48k <-> 44.1k at 14 and 20 periods, see
+// "one-round jobs" below): unit-stride float32 columns, nothing else — a unit of its own, FFT_PART=5, four kernels.
+// Threads: the largest butterfly count of any pass is 294 (2058 = 21*14*7: 98 / 147 / 294; 2240: 140 / 160 / 224) and
+// 320 (3200 = 16*20*10: 200 / 160 / 320; 2940: 140 / 210 / 294) — five waves.
+#ifndef FFT_ONE_ROUND_NT
+#define FFT_ONE_ROUND_NT 320
+#endif
+#define HIPSOXR_PART5_SPECS(X) X(2240, 2058, FFT_ONE_ROUND_NT) X(2058, 2240, FFT_ONE_ROUND_NT) X(3200, 2940, FFT_ONE_ROUND_NT) X(2940, 3200, FFT_ONE_ROUND_NT)
+#define HIPSOXR_INST_F32(NA, NB, NT) HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float>(FftArgs);
 #if defined(FFT_PART) && FFT_PART == 0
 #define HIPSOXR_EXTERN extern
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
 HIPSOXR_PART2_SPECS(HIPSOXR_INST)
 HIPSOXR_PART1_SPECS(HIPSOXR_INST_PCM)
 HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
+HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32)
 #elif defined(FFT_PART) && FFT_PART == 1
 #define HIPSOXR_EXTERN
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
@@ -831,6 +843,9 @@ HIPSOXR_PART1_SPECS(HIPSOXR_INST_PCM)
 #elif defined(FFT_PART) && FFT_PART == 4
 #define HIPSOXR_EXTERN
 HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
+#elif defined(FFT_PART) && FFT_PART == 5
+#define HIPSOXR_EXTERN
+HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32)
 #endif
 
 #if !defined(FFT_PART) || FFT_PART == 0
@@ -988,7 +1003,7 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
 
 // ---- paired-block kernels: compile-time schedules for the common ratios -------------------
 struct PairEntry {
-    int64_t L, M; int k; int small; /* 0: full-size blocks, 1: half-size (small jobs), 2: quarter-size (smaller still) */
+    int64_t L, M; int k; int small; /* 0: full-size blocks, 1: half-size (small jobs), 2: quarter-size (smaller still), 3: one-round float32 jobs only (kern2 alone) */
     unsigned nt;
     void (*kern2)(FftArgs); void (*kern2d)(FftArgs); // unit-stride columns, float32 / float64
     void (*kern2fd)(FftArgs);                        // float32 I/O on float64 arithmetic (HIPSOXR_KERNEL_FFT_F64)
@@ -1004,6 +1019,9 @@ struct PairEntry {
      k_fft_strided2<PairOf<NA, NB, NT>, float, false>, k_fft_strided2<PairOf<NA, NB, NT>, double, false>, \
      k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>, k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>, \
      k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>}
+// ... float32 unit-stride columns only: every other pointer null (taken by the one-round rule of launch_fft_impl alone)
+#define HIPSOXR_PAIR_F32(L, M, k, NA, NB) \
+    {L, M, k, 3, FFT_ONE_ROUND_NT, k_fft_pair2<PairOf<NA, NB, FFT_ONE_ROUND_NT>, float>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
 static const PairEntry *fft_pairs(int *n)
 {
     static const PairEntry pairs[] = {
@@ -1011,6 +1029,8 @@ static const PairEntry *fft_pairs(int *n)
         HIPSOXR_PAIR(147, 160, 32, false, 5120, 4704, 384), HIPSOXR_PAIR(147, 160, 16, true, 2560, 2352, 384),   // 48k -> 44.1k
         HIPSOXR_PAIR(160, 147, 32, false, 4704, 5120, 384), HIPSOXR_PAIR(160, 147, 16, true, 2352, 2560, 384),   // 44.1k -> 48k
         HIPSOXR_PAIR(147, 160, 8, 2, 1280, 1176, 256), HIPSOXR_PAIR(160, 147, 8, 2, 1176, 1280, 256),           // ... quarter-size blocks: jobs of a few hundred pairs
+        HIPSOXR_PAIR_F32(147, 160, 14, 2240, 2058), HIPSOXR_PAIR_F32(160, 147, 14, 2058, 2240),                 // ... 14 and 20 periods: block sizes between those three for
+        HIPSOXR_PAIR_F32(147, 160, 20, 3200, 2940), HIPSOXR_PAIR_F32(160, 147, 20, 2940, 3200),                 //     float32 jobs that run as ONE round of co-resident workgroups
         HIPSOXR_PAIR(160, 441, 16, false, 7056, 2560, 448), HIPSOXR_PAIR(441, 160, 16, false, 2560, 7056, 448),  // 44.1k <-> 16k
         HIPSOXR_PAIR(160, 441, 10, true, 4410, 1600, 320), HIPSOXR_PAIR(441, 160, 10, true, 1600, 4410, 320),    // ... 35 KB blocks: 4 workgroups per CU
         HIPSOXR_PAIR(1, 2, 2048, false, 4096, 2048, 256), HIPSOXR_PAIR(2, 1, 2048, false, 2048, 4096, 256),      // 2:1, 1:2
@@ -1034,6 +1054,60 @@ static const PairEntry *fft_pairs(int *n)
     return pairs;
 }
 #undef HIPSOXR_PAIR
+#undef HIPSOXR_PAIR_F32
+
+// ---- one-round jobs: block size by per-CU load ------------------------------------------------------------
+// A float32 job of unit-stride columns below the throughput rule's size (a clip of 20 s to a few minutes, a few
+// channels) is ONE round: every workgroup is resident from the start, and the launch ends when the most loaded CU does.
+// What a block size k costs there is
+//     chain(k) + queue(k) * (workgroups on the most loaded CU - 1),    the most loaded CU holding ceil(workgroups / CUs):
+// chain = one launch with at most one workgroup per CU (launch + loads + six passes + store), queue = what every further
+// workgroup that shares the CU adds.  Microseconds, least-squares fits per k over the mono and 2-column clips of 10 .. 90 s
+// below the throughput rule's size, k forced (tools/one_round_sweep.py; rows and fit: profiles/NOTES_one_round.md §3,
+// profiles/one_round_forced_k.json).
+// More candidate block sizes of a ratio are more rows here and more entries in fft_pairs — no code.
+struct OneRoundCost { int64_t L, M; int k; float chain_us, queue_us; };
+static const OneRoundCost kOneRoundCost[] = {
+    {147, 160, 8, 6.29f, 0.79f}, {147, 160, 14, 7.70f, 1.26f}, {147, 160, 16, 8.01f, 1.24f}, {147, 160, 20, 8.72f, 1.57f}, {147, 160, 32, 9.72f, 2.85f}, // 48k -> 44.1k
+    {160, 147, 8, 6.81f, 0.89f}, {160, 147, 14, 7.63f, 1.19f}, {160, 147, 16, 8.02f, 1.29f}, {160, 147, 20, 8.56f, 1.48f}, {160, 147, 32, 9.93f, 2.63f}, // 44.1k -> 48k
+};
+// A candidate must beat the size rules' choice by more than this: the run-to-run spread of one row of that sweep (a tie
+// goes to the choice the thresholds make, so that nothing changes where nothing is gained)
+static const double kOneRoundTieUs = 0.10;
+static const OneRoundCost *one_round_cost(const PairEntry &e)
+{
+    for (const OneRoundCost &c : kOneRoundCost)
+        if (c.L == e.L && c.M == e.M && c.k == e.k) return &c;
+    return nullptr;
+}
+// What the rule needs to know about the device, asked once per device: CUs, LDS bytes and threads a CU holds.
+struct CuShape { int cus = 0; int64_t lds = 0, threads = 0; };
+static bool cu_shape(CuShape *out)
+{
+    static std::mutex mu;
+    static std::vector<std::pair<int, CuShape>> seen;
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess) return false;
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto &e : seen)
+        if (e.first == d) { *out = e.second; return e.second.cus > 0; }
+    CuShape c;
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess) c.cus = v;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, d) == hipSuccess) c.lds = v;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxThreadsPerMultiProcessor, d) == hipSuccess) c.threads = v;
+    if (c.lds <= 0 || c.threads <= 0) c.cus = 0; // (no rule without the whole picture: the thresholds' choice stands)
+    seen.push_back({d, c});
+    *out = c;
+    return c.cus > 0;
+}
+// Outputs a block of k periods keeps (fft_geometry's hop_out, arithmetic only); 0: no such block
+static int64_t fft_hop_out(const Plan &p, int k)
+{
+    const int64_t disc = ((int64_t)(p.T / 2 + 2) * p.L + p.M - 1) / p.M;
+    const int64_t hop_periods = ((int64_t)k * p.L - disc - (int64_t)fft_lead_periods(p) * p.L) / p.L;
+    return hop_periods < 1 || 2 * hop_periods * p.L < (int64_t)k * p.L ? 0 : hop_periods * p.L;
+}
 
 // Whole-signal float32 / float64 job (or an int16 / int32 one that names the engine)?  (zero-extended signal starting at absolute index 0, all outputs)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
@@ -1113,8 +1187,11 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
     if (!no_pair && cols_p <= 65535) {
         const PairEntry *big = nullptr, *sml = nullptr, *tiny = nullptr;
         int big_i = 0, sml_i = 0, tiny_i = 0;
+        int cand_i[8], n_cand = 0; // every block size of the ratio: what the one-round rule chooses among
         for (int i = 0; i < n_pairs; ++i)
             if (pairs[i].L == p->L && pairs[i].M == p->M) {
+                if (n_cand < 8) cand_i[n_cand++] = i;
+                if (pairs[i].small == 3) continue; // (one-round float32 jobs only: below)
                 if (pairs[i].small == 2) { tiny = &pairs[i]; tiny_i = i; }
                 else if (pairs[i].small) { sml = &pairs[i]; sml_i = i; }
                 else { big = &pairs[i]; big_i = i; }
@@ -1148,6 +1225,60 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                     FftGeom gt;
                     if (const char *err = get(2 + tiny_i, tiny->k, &gt)) return err;
                     if (gt.ok) { g = gt; use = tiny; }
+                }
+            }
+            // One-round jobs (see kOneRoundCost): float32 unit-stride columns — exactly the jobs that run `kern2` below
+            // (v2ok, not f64, not pcm) — as whole signals, where the throughput rule above left the large blocks.  Every
+            // other element type, layout and the stream path keep the choice made above; so does this one under
+            // HIPSOXR_FFT_LARGE_ONLY / _SMALL_ONLY (they name a block size), and HIPSOXR_FFT_NO_TINY takes k = 8 away.
+            // Ties go to the choice made above.  HIPSOXR_DEBUG_FFT_K (debug builds): k > 0 forces that block size for
+            // every such job, whatever its size; k < 0 turns the rule off.
+            const bool plain_cols = j.in_frame_stride == 1 && j.out_frame_stride == 1 &&
+                                    (j.n_channels == 1 || j.in_chan_stride != 1 || j.out_chan_stride != 1); // (=> no XCD map, no channel pairs)
+            const int force_k1 = switches().dbg_fft_k;
+            if (use && (use != big || force_k1 > 0) && plain_cols && j.elem == HIPSOXR_F32 && !wide32 && !window && force_k1 >= 0 &&
+                ((!switches().fft_large_only && !switches().fft_small_only) || force_k1 > 0)) {
+                CuShape cu;
+                auto wgs_of = [&](int64_t hop) { return ((span + hop - 1) / hop + 1) / 2 * (int64_t)cols_p; };
+                // a candidate's cost; < 0: not a candidate (no figures, no such block, or not co-resident on this device)
+                auto cost_of = [&](const PairEntry &e, const CuShape &cu) -> double {
+                    const OneRoundCost *c = one_round_cost(e);
+                    const int64_t hop = fft_hop_out(*p, e.k);
+                    if (!c || !hop || !e.kern2) return -1.;
+                    const int64_t lds = std::max(e.k * p->L, e.k * p->M) * (int64_t)sizeof(float2);
+                    if (2 * hop * (int64_t)sizeof(float) + 16 > lds) return -1.; // (the staged run must fit the transform buffer: v2ok)
+                    const int64_t slots = std::min(cu.lds / lds, cu.threads / (int64_t)e.nt);
+                    const int64_t per_cu = (wgs_of(hop) + cu.cus - 1) / cu.cus;
+                    if (per_cu > slots) return -1.;
+                    return (double)c->chain_us + (double)c->queue_us * (double)(per_cu - 1);
+                };
+                // (the answer depends on the plan, the job's size and the choice made above alone: the last one is kept per
+                //  thread, so that a loop over one job — 10 us a launch, as long as the kernel runs — pays for the rule once)
+                struct Memo { const Plan *p; int64_t L, M, span; int32_t T; uint64_t cols; const PairEntry *from; bool no_tiny; int dev, pick; };
+                static thread_local Memo memo = {nullptr, 0, 0, 0, 0, 0, nullptr, false, -1, -1};
+                int dev_now = -1;
+                (void)hipGetDevice(&dev_now);
+                const bool memo_hit = force_k1 == 0 && memo.p == p && memo.L == p->L && memo.M == p->M && memo.T == p->T && memo.span == span &&
+                                      memo.cols == cols_p && memo.from == use && memo.dev == dev_now && memo.no_tiny == switches().fft_no_tiny;
+                int pick = memo_hit ? memo.pick : -1;
+                if (memo_hit) {
+                } else if (force_k1 > 0) {
+                    for (int c = 0; c < n_cand; ++c)
+                        if (pairs[cand_i[c]].k == force_k1 && pairs[cand_i[c]].kern2) pick = cand_i[c];
+                } else if (cu_shape(&cu)) {
+                    double best = cost_of(*use, cu);
+                    for (int c = 0; c < n_cand && best >= 0.; ++c) { // (the thresholds' choice outside the model: it stands)
+                        const PairEntry &e = pairs[cand_i[c]];
+                        if (&e == use || (e.small == 2 && switches().fft_no_tiny)) continue;
+                        const double v = cost_of(e, cu);
+                        if (v >= 0. && v < best - (pick < 0 ? kOneRoundTieUs : 0.)) { best = v; pick = cand_i[c]; }
+                    }
+                }
+                if (!memo_hit && force_k1 == 0) memo = {p, p->L, p->M, span, p->T, cols_p, use, switches().fft_no_tiny, dev_now, pick};
+                if (pick >= 0 && &pairs[pick] != use) {
+                    FftGeom gc;
+                    if (const char *err = get(2 + pick, pairs[pick].k, &gc)) return err;
+                    if (gc.ok && gc.hop_out == fft_hop_out(*p, pairs[pick].k)) { g = gc; use = &pairs[pick]; }
                 }
             }
             if (use) {
@@ -1220,12 +1351,14 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                 // (never a window, and never a column with frames missing in FRONT — a.in_lo > 0, data-dependent front
                 //  extension: k_fft_wave's front guard covers the lead-in of block 0 only)
                 if (v2ok && !f64 && !pcm && !window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
-                    FftGeom gw;
-                    if (const char *err = get(1000 + wk.k, wk.k, &gw)) return err;
-                    const int64_t pairs_w = gw.ok ? ((j.out_frames + gw.hop_out - 1) / gw.hop_out + 1) / 2 : 0;
+                    // (the job size first, from the kernel's own constants: its geometry — a host DFT of the filter and two
+                    //  device allocations — is built only for a job that can take it; 48k -> 44.1k never does)
+                    const int64_t pairs_w = ((j.out_frames + wk.hop - 1) / wk.hop + 1) / 2;
                     const int64_t wave_min = switches().dbg_wave_min ? switches().dbg_wave_min : wk.min_pairs;
-                    if (gw.ok && gw.v0 == wk.v0 && gw.hop_out == wk.hop && gw.hop_periods == wk.hop_periods && pairs_w * (int64_t)cols_p >= wave_min &&
-                        pairs_w * (int64_t)cols_p <= 2147483000LL) { // (item numbers are 32-bit; a larger job stays on k_fft_pair2)
+                    FftGeom gw;
+                    if (pairs_w * (int64_t)cols_p >= wave_min && pairs_w * (int64_t)cols_p <= 2147483000LL) // (item numbers are 32-bit; a larger job stays on k_fft_pair2)
+                        if (const char *err = get(1000 + wk.k, wk.k, &gw)) return err;
+                    if (gw.ok && gw.v0 == wk.v0 && gw.hop_out == wk.hop && gw.hop_periods == wk.hop_periods) {
                         set_geom(a, gw);
                         if (const char *e = fft_wave_launch(wk, a, (unsigned)pairs_w, (unsigned)cols_p, stream)) return e;
                         *handled = true;
@@ -1243,6 +1376,7 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                 } else {
                     kern = pcm ? use->kcpi16 : cp2ok ? (f64 ? use->kcpd : use->kcp) : (f64 ? use->kstd : use->kst); // (pcm: cp2ok — st2ok wants floats)
                 }
+                if (!kern) return "internal: a float32-only block size was chosen for another kind of job"; // (cannot happen: plain_cols above)
                 if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
 #ifdef FFT2_TRACE
                 size_t trace_n = 0;
