@@ -1147,6 +1147,21 @@ const char *fft_stream_refusal(const Plan &p, int elem, uint32_t ch, int32_t *le
     return nullptr;
 }
 
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build): one text line per call of launch_fft_impl, appended to that file — what
+// was launched for the job (tests/test_gpu_fft_table.py asserts it).  form: pair2 / strided2_cp / strided2_st (a row of
+// fft_pairs: L M k small are the row's), wave (k_fft_wave: its own k; grid = block pairs x columns, the work items of its
+// persistent waves), block (k_fft_block: the geometry's k), none (nothing launched, *handled == false; the row chosen so
+// far, if any).  small = -1: not a row of the table.
+static void fft_launch_log(const char *form, int64_t L, int64_t M, int k, int small, const char *kind, unsigned nt, size_t lds,
+                           dim3 grid, int64_t hop_out, int64_t n_blocks, bool window)
+{
+    FILE *f = fopen(switches().dbg_launch_log, "a");
+    if (!f) return;
+    fprintf(f, "form=%s L=%lld M=%lld k=%d small=%d kind=%s nt=%u lds=%zu grid=%ux%ux%u hop_out=%lld n_blocks=%lld window=%d\n", form,
+            (long long)L, (long long)M, k, small, kind, nt, lds, grid.x, grid.y, grid.z, (long long)hop_out, (long long)n_blocks, window ? 1 : 0);
+    fclose(f);
+}
+
 // (job.in_abs0 != 0 — in[0] is sample in_abs0 of a column that is zero outside [in_abs0, in_abs0 + in_frames) — is served
 // for the two-stage form's inner calls; the public paths come here through fft_job_eligible, which wants 0.)
 // window (launch_fft_window, stream chunks): the job is outputs [out_k0, out_k0 + out_frames) of the column.  The paired
@@ -1183,6 +1198,16 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
     const bool f64 = io64 || wide32 || pcm32;
     // float64, integer samples: the paired kernels only (unit-stride columns; channel pairs; strided columns) — else the
     // exact engine (integer samples: the caller's error)
+    const char *kind = pcm ? (pcm32 ? "i32" : "i16") : io64 ? "f64" : wide32 ? "f32on64" : "f32"; // (the launch log's name of the instance)
+    const PairEntry *log_row = nullptr;
+    struct LogNone { // leaving without a launch: the log says so
+        const bool *handled; const Plan *p; const PairEntry *const *row; const char *kind; bool window;
+        ~LogNone()
+        {
+            if (switches().dbg_launch_log && !*handled)
+                fft_launch_log("none", p->L, p->M, *row ? (*row)->k : 0, *row ? (*row)->small : -1, kind, 0, 0, dim3(0, 0, 0), 0, 0, window);
+        }
+    } log_none = {handled, p, &log_row, kind, window};
     if ((f64 || pcm) && (no_pair || cols_p > 65535)) return nullptr;
     if (!no_pair && cols_p <= 65535) {
         const PairEntry *big = nullptr, *sml = nullptr, *tiny = nullptr;
@@ -1282,6 +1307,7 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                 }
             }
             if (use) {
+                log_row = use;
                 FftArgs a;
                 // (sample 0 of the columns; window: frame P0 M / P0 L of them.  int16 channel pairs: the shift is a whole
                 //  number of frames, so with the even frame strides cp_pcm_ok asks for, the 4-byte alignment it checks on
@@ -1361,6 +1387,8 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                     if (gw.ok && gw.v0 == wk.v0 && gw.hop_out == wk.hop && gw.hop_periods == wk.hop_periods) {
                         set_geom(a, gw);
                         if (const char *e = fft_wave_launch(wk, a, (unsigned)pairs_w, (unsigned)cols_p, stream)) return e;
+                        if (switches().dbg_launch_log)
+                            fft_launch_log("wave", p->L, p->M, wk.k, -1, kind, 64, 0, dim3((unsigned)pairs_w, (unsigned)cols_p, 1), gw.hop_out, 2 * pairs_w, window);
                         *handled = true;
                         return nullptr;
                     }
@@ -1388,6 +1416,8 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
 #endif
                 hipLaunchKernelGGL(kern, grid, dim3(nt), lds, (hipStream_t)stream, a);
                 HIP_TRY(hipGetLastError());
+                if (switches().dbg_launch_log)
+                    fft_launch_log(v2ok ? "pair2" : cp2ok ? "strided2_cp" : "strided2_st", use->L, use->M, use->k, use->small, kind, nt, lds, grid, g.hop_out, n_blocks, window);
 #ifdef FFT2_TRACE
                 if (a.trace) { // debugging aid only: synchronous dump of the per-wave time stamps
                     std::vector<unsigned long long> h(trace_n);
@@ -1441,6 +1471,8 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
     hipLaunchKernelGGL(k_fft_block, dim3((unsigned)n_blocks, (unsigned)cols, 1), dim3(256), std::max(g.lds_bytes, dbg_lds),
                        (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log)
+        fft_launch_log("block", p->L, p->M, g.k, -1, kind, 256, std::max(g.lds_bytes, dbg_lds), dim3((unsigned)n_blocks, (unsigned)cols, 1), g.hop_out, n_blocks, window);
     *handled = true;
     return nullptr;
 }
