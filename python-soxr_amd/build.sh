@@ -6,9 +6,12 @@
 #     -ffp-contract=off: every fused multiply-add there is written explicitly, so that host design
 #     and device arithmetic are bit-identical to the oracle's;
 #   * the frequency-domain engine (fft.hip) is a 1e-6-class path: contraction is allowed, and the
-#     SLP vectoriser is off — on gfx950 v_pk_{add,mul,fma}_f32 issue at half the rate of their
-#     scalar forms, so "vectorised" complex arithmetic only adds register shuffles
-#     (measured: 5412 -> 3261 VALU issue slots per thread for the 2560/2352-point block).
+#     SLP vectoriser is off — on gfx950 v_pk_add_f32 / v_pk_mul_f32 cost exactly two scalar issues
+#     (4.3 against 2.3 cycles per wave-instruction and SIMD), and v_pk_fma_f32 does two FMAs in the
+#     4.4 cycles that two v_fmac_f32 take 8.0 for (profiles/r06_ab_experiments.txt §6): packing pays
+#     for FMAs alone, and "vectorised" complex arithmetic otherwise only adds register shuffles
+#     (measured: 5412 -> 3261 VALU issue slots per thread for the 2560/2352-point block; hand-packed
+#     FMAs, -DFFT_FORCE_PK, gained nothing on these kernels either: §10 there).
 set -e
 HERE="$(cd "$(dirname "$0")" && pwd)"
 SRC="$HERE/csrc"

@@ -116,12 +116,48 @@ __device__ __forceinline__ void fft_pass(cf *buf, int N, int Ns, const cf *W)
 // <= a+b for the same number of complex products (engine error 3.5e-7 -> 2.2e-7 relative RMS).
 // `tid` = the thread's index among the NT threads that share ONE transform (threadIdx.x; an experiment of round 5 interleaved
 // the transforms of four channel pairs across the lanes of one workgroup: profiles/NOTES_r05.md §3).
-template <int N, int Ns, int R, int SIGN, int NT, bool SYNC_BEFORE_STORE, typename C, typename Load, typename Store>
-__device__ __forceinline__ void fft_pass_ct(const C *W, Load load, Store store, const int tid)
+// Tw (one-round kernels, PassTabs): every factor w^(t k) of the pass comes from a per-pass table laid out [t][k] instead —
+// correctly rounded constants of the plan, R - 1 loads at ONE per-thread offset (k) plus a constant each, issued where
+// w1 / w4 are loaded (in flight during the LDS reads and the barrier); no powers are formed.  `tw_at` = the pass's first
+// entry in the transform's table.
+struct NoTabs { static constexpr bool on = false; };
+struct PassTabs { static constexpr bool on = true; __amdgpu_buffer_rsrc_t r; };
+template <int N, int Ns, int R, int SIGN, int NT, bool SYNC_BEFORE_STORE, int tw_at = 0, typename C, typename Load, typename Store, typename Tw = NoTabs>
+__device__ __forceinline__ void fft_pass_ct(const C *W, Load load, Store store, const int tid, Tw tw = Tw())
 {
     constexpr int nb = N / R, wstep = N / (Ns * R), NB = (nb + NT - 1) / NT;
     typedef real_of<C> T;
     C u[NB][R];
+    if constexpr (Tw::on && Ns > 1) {
+        static_assert(sizeof(C) == 8, "per-pass twiddle tables: float32 kernels");
+        C f[NB][R];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int j = tid + i * NT;
+            if (NB * NT == nb || j < nb) {
+                const int k = j % Ns;
+#pragma unroll
+                for (int t = 1; t < R; ++t)
+                    f[i][t] = __builtin_bit_cast(C, __builtin_amdgcn_raw_buffer_load_b64(tw.r, k * (int)sizeof(C), (tw_at + (t - 1) * Ns) * (int)sizeof(C), 0));
+#pragma unroll
+                for (int t = 0; t < R; ++t) u[i][t] = load(j, t);
+            }
+        }
+        if (SYNC_BEFORE_STORE) __syncthreads(); // in place: every input of the pass is in registers
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            const int j = tid + i * NT;
+            if (NB * NT == nb || j < nb) {
+                const int k = j % Ns, o = (j - k) * R + k;
+#pragma unroll
+                for (int t = 1; t < R; ++t) u[i][t] = cmul(u[i][t], f[i][t]);
+                dft_r<R, SIGN>(u[i]);
+#pragma unroll
+                for (int t = 0; t < R; ++t) store(o, t, u[i][t]);
+            }
+        }
+        return;
+    }
     C w1s[NB], w4s[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
@@ -187,9 +223,12 @@ __device__ __forceinline__ void fft_pass_ct(const C *W, Load load, Store store, 
 #define FFT_STAMP_ARGS
 #endif
 // (last_store_alt / use_alt: a second form of the last pass's consumer behind ONE wave-uniform branch around the whole pass)
-template <int N, int SIGN, int NT, int R0, int R1, int R2, bool SWZ, bool LASTSYNC, typename C, typename Load, typename Store, typename StoreAlt>
+// tw (PassTabs): the twiddled passes named by TABS (bit 0: pass 2, bit 1: pass 3) read their factors from the
+// transform's per-pass tables — pass 2's [t][k] block of (R1 - 1) R0 entries, then pass 3's of (R2 - 1) R0 R1 (host side:
+// pass_tables, which lays out both whatever TABS says) — instead of forming them from W.
+template <int N, int SIGN, int NT, int R0, int R1, int R2, bool SWZ, bool LASTSYNC, int TABS = 3, typename C, typename Load, typename Store, typename StoreAlt, typename Tw = NoTabs>
 __device__ __forceinline__ void fft_ct3(FFT_STAMP_DECL C *buf, const C *W, Load first_load, Store last_store, bool first_in_lds, StoreAlt last_store_alt,
-                                        bool use_alt, const int tid)
+                                        bool use_alt, const int tid, Tw tw = Tw())
 {
     static_assert(R0 * R1 * R2 == N, "radix schedule");
     static_assert(!SWZ || R0 == 16, "the swizzled layout is the radix-16 first pass's");
@@ -213,12 +252,18 @@ __device__ __forceinline__ void fft_ct3(FFT_STAMP_DECL C *buf, const C *W, Load 
     FFT_STAMP();
     __syncthreads();
     FFT_STAMP();
-    fft_pass_ct<N, R0, R1, SIGN, NT, true>(W, swz_load, lds_store1, tid);
+    if constexpr (TABS & 1) fft_pass_ct<N, R0, R1, SIGN, NT, true, 0>(W, swz_load, lds_store1, tid, tw);
+    else fft_pass_ct<N, R0, R1, SIGN, NT, true>(W, swz_load, lds_store1, tid);
     FFT_STAMP();
     __syncthreads();
     FFT_STAMP();
-    if (use_alt) fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC>(W, lds_load2, last_store_alt, tid);
-    else fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC>(W, lds_load2, last_store, tid);
+    if constexpr (TABS & 2) {
+        if (use_alt) fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC, (R1 - 1) * R0>(W, lds_load2, last_store_alt, tid, tw);
+        else fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC, (R1 - 1) * R0>(W, lds_load2, last_store, tid, tw);
+    } else {
+        if (use_alt) fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC>(W, lds_load2, last_store_alt, tid);
+        else fft_pass_ct<N, R0 * R1, R2, SIGN, NT, LASTSYNC>(W, lds_load2, last_store, tid);
+    }
     FFT_STAMP();
 }
 
@@ -340,17 +385,22 @@ __global__ void __launch_bounds__(256, 2) k_fft_block(FftArgs a)
 // Schedules: N_in = A0*A1*A2 (forward), N_out = B0*B1*B2 (inverse); *SWZ = swizzled layout after a power-of-two first
 // radix (see fft_ct3).  NT >= the largest butterfly count of any pass.
 // ---------------------------------------------------------------------------------------------
-template <int NA_, int NB_, int NT_, int A0, int A1, int A2, bool ASWZ, int B0, int B1, int B2, bool BSWZ>
+// TABS_: which twiddled passes of both transforms take their factors from per-pass tables (FftArgs::TWA / TWB, float32;
+// the one-round kernels; bits as FFT_ONE_ROUND_TABS).  fwd / inv_staged then get the transform's PassTabs; everything
+// else leaves the argument out.
+template <int NA_, int NB_, int NT_, int A0, int A1, int A2, bool ASWZ, int B0, int B1, int B2, bool BSWZ, int TABS_ = 0>
 struct PairSpec {
     static constexpr int NA = NA_, NB = NB_, NT = NT_;
     static constexpr int RA0 = A0, RA2 = A2, RB0 = B0, RB2 = B2;
-    template <typename C, typename Ld, typename St> static __device__ __forceinline__ void fwd(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x)
-    { fft_ct3<NA, -1, NT, A0, A1, A2, ASWZ, false>(FFT_STAMP_ARGS b, W, ld, st, false, st, false, tid); }
+    static constexpr int TABS = TABS_; // bit 0: pass 2, bit 1: pass 3
+    static constexpr int TWA_N = (A1 - 1) * A0 + (A2 - 1) * A0 * A1, TWB_N = (B1 - 1) * B0 + (B2 - 1) * B0 * B1; // entries of the per-pass tables
+    template <typename C, typename Ld, typename St, typename Tw = NoTabs> static __device__ __forceinline__ void fwd(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x, Tw tw = Tw())
+    { fft_ct3<NA, -1, NT, A0, A1, A2, ASWZ, false, TABS>(FFT_STAMP_ARGS b, W, ld, st, false, st, false, tid, tw); }
     template <typename C, typename Ld, typename St> static __device__ __forceinline__ void inv(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x)
     { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, false>(FFT_STAMP_ARGS b, W, ld, st, true, st, false, tid); }
     // last pass stores into LDS in another layout (output staging): all its inputs must be in registers first
-    template <typename C, typename Ld, typename St, typename StAlt> static __device__ __forceinline__ void inv_staged(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, StAlt st_alt, bool use_alt)
-    { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, true>(FFT_STAMP_ARGS b, W, ld, st, true, st_alt, use_alt, (int)threadIdx.x); }
+    template <typename C, typename Ld, typename St, typename StAlt, typename Tw = NoTabs> static __device__ __forceinline__ void inv_staged(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, StAlt st_alt, bool use_alt, Tw tw = Tw())
+    { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, true, TABS>(FFT_STAMP_ARGS b, W, ld, st, true, st_alt, use_alt, (int)threadIdx.x, tw); }
 };
 // Three-pass schedule of each transform length in use (first radix 21: conflict-free as it is; first radix 16:
 // swizzled layout between pass 1 and 2).  4410 = 21*14*15 is the order the product runs (configs[2] 47 us, against
@@ -361,15 +411,33 @@ template <int N> struct Sched;
     X(4410, 21, 14, 15, false) X(4096, 16, 16, 16, true) X(3840, 16, 16, 15, true) X(3584, 14, 16, 16, false)        \
     X(3528, 21, 12, 14, false) X(2688, 21, 16, 8, false) X(2560, 16, 16, 10, true) X(2352, 21, 16, 7, false)         \
     X(2048, 16, 16, 8, true) X(1792, 7, 16, 16, false) X(1024, 16, 8, 8, true) X(1600, 16, 10, 10, true)             \
-    X(1280, 5, 16, 16, false) X(1176, 21, 8, 7, false) X(896, 7, 16, 8, false)                                        \
+    X(1280, 5, 16, 16, false) X(1176, 21, 8, 7, false) X(896, 7, 16, 8, false)
+// ... and the lengths of the one-round float32 kernels (HIPSOXR_PART5_SPECS): twiddles from per-pass tables
+#ifndef FFT_ONE_ROUND_TABS
+// Which twiddled passes read the tables: bit 0 = pass 2, bit 1 = pass 3.  Pass 3 alone: its [t][k] rows are Ns = R0 R1
+// consecutive entries, one contiguous run per wave and load; pass 2 has Ns = R0 = 16 or 21 — every load of a wave
+// fetches the same 16 or 21 entries four times over, 13 loads against the 12 products they replace, and the launch gets
+// SLOWER (60 s clip, us per launch: parent 11.04, pass 2 alone 11.52, pass 3 alone 10.82, both 11.70:
+// profiles/NOTES_one_round_chain.md).
+#define FFT_ONE_ROUND_TABS 2
+#endif
+#define HIPSOXR_SCHED_TABS_LIST(X) \
     X(2240, 16, 14, 10, true) X(2058, 21, 14, 7, false) X(3200, 16, 20, 10, true) X(2940, 21, 14, 10, false)
 #define HIPSOXR_SCHED(N, r0, r1, r2, swz) \
-    template <> struct Sched<N> { static constexpr int R0 = r0, R1 = r1, R2 = r2; static constexpr bool SWZ = swz; };
+    template <> struct Sched<N> { static constexpr int R0 = r0, R1 = r1, R2 = r2; static constexpr bool SWZ = swz; static constexpr int TABS = 0; };
 HIPSOXR_SCHED_LIST(HIPSOXR_SCHED)
 #undef HIPSOXR_SCHED
+#define HIPSOXR_SCHED(N, r0, r1, r2, swz) \
+    template <> struct Sched<N> { static constexpr int R0 = r0, R1 = r1, R2 = r2; static constexpr bool SWZ = swz; static constexpr int TABS = FFT_ONE_ROUND_TABS; };
+HIPSOXR_SCHED_TABS_LIST(HIPSOXR_SCHED)
+#undef HIPSOXR_SCHED
+// ... in the kernel where they were measured to gain: 2240 x 2058 (48k -> 44.1k, 14 periods: 60 s mono 10.31 -> 10.12 us,
+// 2 x 30 s 9.95 -> 9.75).  3200 x 2940 is unchanged by them to 0.01 us, and both 44.1k -> 48k kernels get 0.1-0.25 us
+// SLOWER (2 x 20 s 8.62 -> 8.86, 2 x 45 s 11.83 -> 11.96): those three keep forming their powers.
+constexpr int pair_tabs(int NA, int NB, int a, int b) { return NA == 2240 && NB == 2058 ? (a & b) : 0; }
 template <int NA, int NB, int NT>
 using PairOf = PairSpec<NA, NB, NT, Sched<NA>::R0, Sched<NA>::R1, Sched<NA>::R2, Sched<NA>::SWZ, Sched<NB>::R0, Sched<NB>::R1,
-                        Sched<NB>::R2, Sched<NB>::SWZ>;
+                        Sched<NB>::R2, Sched<NB>::SWZ, pair_tabs(NA, NB, Sched<NA>::TABS, Sched<NB>::TABS)>;
 
 
 // Input t of butterfly j of the FIRST INVERSE pass: bin n = j + t * NB/RB0 of the output grid <- bin n (non-negative
@@ -489,6 +557,12 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     if (outa + a.v0 >= out_frames) return;
     const IO *xin = (const IO *)a.in + clip_in + (int64_t)ch * a.ichs;
     auto last_fwd_store = [&](int o, int t, C v) { buf[o + t * (NA / Spec::RA2)] = v; };
+    // per-pass twiddle tables (Spec::TABS): one descriptor per transform, the range check over exactly its entries
+    auto pass_tabs = [](const float2 *p, int n) {
+        if constexpr (Spec::TABS) return PassTabs{__builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)p), 0, n * (int)sizeof(float2), 0x00020000)};
+        else return NoTabs{};
+    };
+    const auto twa = pass_tabs(a.TWA, Spec::TWA_N), twb = pass_tabs(a.TWB, Spec::TWB_N);
 
     // ---- forward: z[n] = x_a[n] + i x_b[n], first pass straight from HBM --------------------------
     if (ina >= a.in_lo) {
@@ -497,12 +571,12 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
             uniform_ptr((void *)(xin + ina)), 0, __builtin_amdgcn_readfirstlane((int)(left < 0 ? 0 : left > 0x40000000 ? 0x40000000 : left)), 0x00020000);
         Spec::fwd(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C { // (the butterfly's own offset: one VGPR for all t)
             return C((Real)buf_load_real<IO>(rs, j * ES, t * nbA * ES), (Real)buf_load_real<IO>(rs, j * ES, (t * nbA + hop_in) * ES));
-        }, last_fwd_store);
+        }, last_fwd_store, (int)threadIdx.x, twa);
     } else { // the first item of a column reaches before its start: explicit zero-extension
         Spec::fwd(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C {
             const int64_t la = ina + j + t * nbA, lb = la + hop_in;
             return C((la >= a.in_lo && la < in_frames) ? (Real)xin[la] : (Real)0, (lb >= a.in_lo && lb < in_frames) ? (Real)xin[lb] : (Real)0);
-        }, last_fwd_store);
+        }, last_fwd_store, (int)threadIdx.x, twa);
     }
     // the filter, |frequency| in bins -> real gain, through a descriptor of its own: Hr[0 .. NB/2]
     const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)PairTabs<Real>::hr(a)), 0,
@@ -532,7 +606,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
         [&](int o, int t, C w) { // any geometry
             ST *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
             if ((unsigned)(o + t * NsL - v0) < (unsigned)hop_out) { *sa = (ST)w.x; *sb = (ST)w.y; }
-        }, !typical);
+        }, !typical, twb);
     __syncthreads();
     FFT_STAMP();
 
@@ -859,7 +933,8 @@ struct FftGeom {
     int32_t radA[8] = {1, 1, 1, 1, 1, 1, 1, 1}, radB[8] = {1, 1, 1, 1, 1, 1, 1, 1}, nA = 0, nB = 0; // (plain arrays: the cached geometry is copied per launch)
     int32_t lead_periods = 0, hop_periods = 0, v0 = 0, hop_out = 0;
     size_t lds_bytes = 0;
-    float2 *dev = nullptr; // [WA: A][WB: B][P: A+1][Q: B][Hs: B+1][WA2: N_in][WB2: N_out][Hr: B+1 floats]
+    float2 *dev = nullptr; // [WA: A][WB: B][P: A+1][Q: B][Hs: B+1][WA2: N_in][WB2: N_out][Hr: B+1 floats][TWA][TWB]
+    size_t twa = 0, twb = 0; // per-pass twiddle tables of the one-round kernels: their places in `dev` (0: none)
     double2 *devd = nullptr; // float64 instance of the paired kernel: [WA2d: N_in][WB2d: N_out][Hrd: B+1 doubles]
 };
 
@@ -941,6 +1016,28 @@ static bool fft_geometry(const Plan &p, FftGeom &g, bool small, int force_k)
     return true;
 }
 
+// Per-pass twiddle tables of a length with a Sched<N>::TABS schedule (the one-round float32 kernels): for pass 2 and
+// pass 3 every factor exp(sign 2 pi i t k / (Ns R)) a butterfly applies, laid out [t][k] (t = 1 .. R - 1, k < Ns) —
+// computed in double and rounded ONCE, where the kernels of the other lengths form w^t from one or two rounded entries.
+// False: N has no such schedule.
+static bool pass_tables(int N, int sign, std::vector<float2> *tw)
+{
+    int r[3] = {0, 0, 0};
+#define HIPSOXR_SCHED(n, r0, r1, r2, swz) if (N == n) { r[0] = r0; r[1] = r1; r[2] = r2; }
+    HIPSOXR_SCHED_TABS_LIST(HIPSOXR_SCHED)
+#undef HIPSOXR_SCHED
+    if (!r[0]) return false;
+    const double PI2 = 6.283185307179586476925286766559;
+    tw->clear();
+    for (int pass = 1, Ns = r[0]; pass < 3; Ns *= r[pass], ++pass)
+        for (int t = 1; t < r[pass]; ++t)
+            for (int k = 0; k < Ns; ++k) {
+                const double ang = PI2 * (double)(t * k) / (double)(Ns * r[pass]);
+                tw->push_back(make_float2((float)std::cos(ang), (float)(sign * std::sin(ang))));
+            }
+    return true;
+}
+
 static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_k = 0)
 {
     FftGeom g;
@@ -949,6 +1046,11 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
     const int32_t T = p.T;
     const int A = g.A, B = g.B;
     std::vector<float2> tab((size_t)A + B + (A + 1) + B + (B + 1) + g.N_in + g.N_out + (B + 2) / 2 + 1);
+    std::vector<float2> twa, twb;
+    if (pass_tables(g.N_in, -1, &twa) && pass_tables(g.N_out, +1, &twb)) { // (behind everything else: 16-byte aligned or not, the loads are 8 bytes)
+        g.twa = tab.size(); g.twb = g.twa + twa.size();
+        tab.resize(g.twb + twb.size());
+    }
     float2 *WA = tab.data(), *WB = WA + A, *P = WB + B, *Q = P + (A + 1), *Hs = Q + B;
     float2 *WA2 = Hs + (B + 1), *WB2 = WA2 + g.N_in;
     const double PI2 = 6.283185307179586476925286766559;
@@ -985,6 +1087,8 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
         reinterpret_cast<float *>(WB2 + g.N_out)[q] = (float)(hr * scale);
         hr64[q] = hr * scale;
     }
+    std::copy(twa.begin(), twa.end(), tab.begin() + g.twa);
+    std::copy(twb.begin(), twb.end(), tab.begin() + g.twb);
     HIP_TRY(hipMalloc((void **)&g.dev, tab.size() * sizeof(float2)));
     HIP_TRY(hipMemcpy(g.dev, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice));
     { // the float64 instance's tables (small: N_in + N_out + B/2 double2)
@@ -1319,6 +1423,7 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
                     a.WA2 = a.Hs + (g.B + 1); a.WB2 = a.WA2 + g.N_in;
                     a.Hr = reinterpret_cast<const float *>(a.WB2 + g.N_out); a.trace = nullptr;
                     a.WA2d = g.devd; a.WB2d = g.devd + g.N_in; a.Hrd = reinterpret_cast<const double *>(g.devd + g.N_in + g.N_out);
+                    a.TWA = g.twa ? g.dev + g.twa : nullptr; a.TWB = g.twb ? g.dev + g.twb : nullptr;
                     a.A = g.A; a.B = g.B; a.nA = a.nB = 0;
                     for (int i = 0; i < 8; ++i) a.radA[i] = a.radB[i] = 1;
                     a.lead_periods = g.lead_periods; a.hop_periods = g.hop_periods; a.v0 = g.v0; a.hop_out = g.hop_out;
@@ -1453,7 +1558,7 @@ static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream
     a.WA2d = a.WB2d = nullptr; a.Hrd = nullptr; a.clip_tab = nullptr;
     a.chpair = 0; a.pairs_per_col = 0; a.xcd_map = 0;
     a.clip_counter = nullptr; a.dither = a.seed = a.ch0 = 0;
-    a.out_lo = a.out_abs0 = 0;
+    a.out_lo = a.out_abs0 = 0; a.TWA = a.TWB = nullptr;
     a.A = g.A; a.B = g.B; a.nA = g.nA; a.nB = g.nB;
     for (int i = 0; i < 8; ++i) { a.radA[i] = g.radA[i]; a.radB[i] = g.radB[i]; }
     a.L = p->L; a.M = p->M;

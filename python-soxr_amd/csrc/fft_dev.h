@@ -295,6 +295,10 @@ struct FftArgs {
     // period boundary P0 of the column, not its start; every index above is relative to it
     int64_t out_lo;          // outputs below out_lo are not part of the job: nothing is stored, nothing counted (0: whole signals)
     int64_t out_abs0;        // absolute output index of the origin, P0 * L (the dither key of integer jobs; 0: whole signals)
+    // one-round float32 kernels (PairSpec::TABS): per-pass twiddle tables of the forward / inverse transform, each pass
+    // laid out [t][k] (t = 1 .. R - 1, k < Ns), pass 2 then pass 3; nullptr for every other geometry.  (Last: the
+    // members above keep their place in the argument block of every other kernel.)
+    const float2 *TWA, *TWB;
 };
 
 // fftwave.hip: the one-wave-per-block-pair kernel of a ratio — block size (periods), the geometry it is compiled for,
