@@ -220,6 +220,15 @@ typedef struct {
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *, const hipsoxr_job_t *job,
                                                void *hip_stream);
+/* gx = A^T gy for the forward job A that hipsoxr_run_device(HIPSOXR_KERNEL_EXACT) computes on the same plan: the transposed
+ * polyphase operator on the same bank (the gradient of a resample; the adjoint an iterative solver needs).  The job is read in
+ * the adjoint's own direction: `in` is gy with in_frames = n_y frames, `out` is gx with out_frames = n_x frames, strides as
+ * usual; in_frames <= hipsoxr_plan_out_len(plan, out_frames) (a truncated forward output has a truncated cotangent).  Every
+ * element of gx is written (0 where no output reads the input), nothing outside it; gather form, no atomics: results are
+ * bitwise reproducible and independent of layout.  HIPSOXR_F32 / HIPSOXR_F64 on exact-bank plans; kernel = HIPSOXR_KERNEL_AUTO
+ * or _EXACT; in_abs0 == 0, out_k0 == 0, clip_table == NULL; anything else is an error that names the reason, never a run of
+ * another path.  Zero frames, clips or channels: success, nothing launched.  Asynchronous on `hip_stream`. */
+HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
 
 /* ---- stream: the soxr_t counterpart (host pointers, state carried across calls) ----------- */
 HIPSOXR_API hipsoxr_error_t hipsoxr_stream_create(double in_rate, double out_rate,

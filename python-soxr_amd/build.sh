@@ -28,6 +28,8 @@ mkdir -p "$OBJ"
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/engine.cpp" -o "$OBJ/engine.o" & P2=$!
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/kernels.hip" -o "$OBJ/kernels.o" & P3=$!
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/soxr_abi.cpp" -o "$OBJ/soxr_abi.o" & P5=$!
+# (adjoint.hip: the transposed operator of the exact engine — explicit fma chains, like kernels.hip)
+"$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/adjoint.hip" -o "$OBJ/adjoint.o" & P14=$!
 # The A/B and timing-experiment switches (device.h `Switches`, everything but four product names) are read from the
 # environment only by a build with -DHIPSOXR_DEBUG_SWITCHES.  The reader lives in kernels.hip alone, so the debug build is
 # that one object compiled a second time and linked with the product's other objects: _variants/dbg/libhipsoxr.so
@@ -47,8 +49,8 @@ FFTFLAGS="${HIPSOXR_FFTFLAGS:--ffp-contract=fast -fno-slp-vectorize}"
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=5 -c "$SRC/fft.hip" -o "$OBJ/fft5.o" & P13=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/twostage.hip" -o "$OBJ/twostage.o" & P9=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/fftwave.hip" -o "$OBJ/fftwave.o" & P10=$!
-wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13   # set -e: any failed compile aborts here
-OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/soxr_abi.o"
+wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13; wait $P14   # set -e: any failed compile aborts here
+OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/adjoint.o $OBJ/soxr_abi.o"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC $OBJS -o "$OUT"
 # The same engine under libsoxr's name: what `find_library(SOXR_LIBRARY NAMES soxr)` of the
 # reference's USE_SYSTEM_LIBSOXR build picks up (reference CMakeLists.txt:83-93).

@@ -1,0 +1,411 @@
+// adjoint.hip — the transposed polyphase operator on CDNA4 (gfx950): gx = A^T gy for the forward job A that the exact
+// engine computes on the same plan (hipsoxr_run_device_adjoint; the gradient of soxr_amd.device.resample_tensor).
+// Hand-written HIP, host and device side in one translation unit, compiled with -ffp-contract=off like the exact engine.
+//
+// Forward, per column (plan.h locate()):   y[k] = sum_{j<T} c[p_k][j] x[n0_k + j],
+//     n0_k = floor(k M / L) - (T/2 - 1),  p_k = (k M) mod L,  x zero outside [0, n_x).
+// Adjoint:   gx[a] = sum over { k in [0, n_y) : 0 <= a - n0_k < T } of c[p_k][a - n0_k] gy[k].
+// It is periodic in a with period M.  With a = q M + s (0 <= s < M) and k = q L + d the terms of phase s are
+//     d_lo(s) = ceil((s - T/2) L / M)  <=  d  <=  d_hi(s) = ceil((s + T/2) L / M) - 1        (d may be negative or >= L)
+//     tap j = s + T/2 - 1 - floor(d M / L),   forward phase (d M) mod L                      (mathematical floor and mod)
+// at most Tt = max_s (d_hi(s) - d_lo(s) + 1) <= ceil(T L / M) + 1 of them.  A TRANSPOSED BANK ct (Tt entries per phase,
+// zero behind a phase's last term) and the start table d_lo[M] turn the adjoint into a gather-form polyphase filter with M
+// phases — no scatter, no atomics:
+//     gx[q M + s] = sum_{i<Tt} ct[s][i] gy[q L + d_lo(s) + i],     gy zero outside [0, n_y).
+//
+// ARITHMETIC: every gx element is ONE fma chain in the element's own width over ascending k, started from +0.  The tables
+// of the tiled kernel hold extra zeros in front of and behind a phase's terms; fma(0, gy, acc) == acc for finite gy, so both
+// kernels below give the same bits and a result does not depend on layout, tiling or launch shape.  The float32 tables
+// are the float64 bank rounded to nearest — the values the float32 forward engine multiplies by: forward and adjoint are
+// transposes of one matrix.
+//
+// Kernels:
+//   k_adj_gather  one lane per gx element; transposed bank tap-major [Tt][M] (lanes of neighbouring phases read
+//                 neighbouring words), gy straight from global memory.  Every exact-bank plan, layout and length; what
+//                 short jobs and plans whose period does not fit LDS run on.
+//   k_adj_tile    the period-tiled form (the k_tile family's shape, kernels_tile.h): a workgroup takes a span of whole input
+//                 periods of one column — or of a group of interleaved channels, read as whole frames — and stages the gy
+//                 slab those periods touch in LDS, zero-filled outside [0, n_y).  A lane owns one (period, channel); a
+//                 wave owns 16 consecutive phases, whose coefficients travel on the scalar path (s_load -> SGPR operands
+//                 of the FMAs) from a per-tile table [I][16] skewed to the tile's first gy sample and zero-padded: one
+//                 LDS read feeds 16 FMAs.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <mutex>
+#include <vector>
+
+#include "device.h"
+
+namespace hipsoxr {
+
+#define HIP_TRY(expr)                                       \
+    do {                                                    \
+        hipError_t e_ = (expr);                             \
+        if (e_ != hipSuccess) return hipGetErrorString(e_); \
+    } while (0)
+
+static constexpr int kAdjRS = 16;        // phases per wave tile of k_adj_tile
+static constexpr int kAdjMinPeriods = 4; // k_adj_tile from this many (replicated) periods of input up
+
+struct AdjArgs {
+    const void *gy;
+    void *gx;
+    const void *ct;       // k_adj_gather: [Tt][M] Real
+    const int32_t *d_lo;  // k_adj_gather: [M]
+    const void *tab;      // k_adj_tile: [n_st][I][16] Real, constant address space
+    const int32_t *e0;    // k_adj_tile: [n_st] first gy sample of a tile's table, relative to the slab's first
+    int64_t L, M;         // out/in = L/M
+    int64_t Lc, Mc;       // k_adj_tile: the period replicated c times (Mc inputs <- Lc cotangent samples)
+    int32_t Tt, n_st, I, dmin;
+    int32_t x_count;      // frames staged per workgroup
+    int32_t pad;          // LDS row padding (frames): rows of Lc + pad frames, an odd number
+    int32_t pb, cg;       // periods and channels per workgroup (pb * cg <= 64 lanes)
+    int32_t cg_shift;     // log2(cg), or -1
+    int32_t n_waves;      // waves that share a workgroup's phase tiles
+    int32_t inter;        // k_adj_gather: channel index fastest (interleaved frames)
+    uint32_t n_clips, n_channels, n_groups;
+    int64_t ics, ifs, ichs, ocs, ofs, ochs;
+    int64_t n_y, n_x;
+};
+
+__device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_r(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// ---------------------------------------------------------------------------------------------
+// k_adj_gather
+// ---------------------------------------------------------------------------------------------
+template <typename Real>
+__global__ void __launch_bounds__(256) k_adj_gather(AdjArgs a)
+{
+    const int64_t per_clip = a.n_x * (int64_t)a.n_channels;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= per_clip) return;
+    int64_t fr, ch;
+    if (a.inter) { fr = idx / a.n_channels; ch = idx - fr * a.n_channels; }
+    else { ch = idx / a.n_x; fr = idx - ch * a.n_x; }
+    const int64_t q = fr / a.M;
+    const int64_t s = fr - q * a.M;
+    const int64_t k0 = q * a.L + a.d_lo[s];
+    const Real *c = (const Real *)a.ct + s;
+    for (uint32_t clip = blockIdx.y; clip < a.n_clips; clip += gridDim.y) {
+        const Real *g = (const Real *)a.gy + (int64_t)clip * a.ics + ch * a.ichs;
+        Real acc = 0;
+        for (int32_t i = 0; i < a.Tt; ++i) {
+            const int64_t k = k0 + i;
+            const Real v = (k >= 0 && k < a.n_y) ? g[k * a.ifs] : (Real)0;
+            acc = fma_r(c[(int64_t)i * a.M], v, acc);
+        }
+        ((Real *)a.gx)[(int64_t)clip * a.ocs + fr * a.ofs + ch * a.ochs] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_adj_tile
+// ---------------------------------------------------------------------------------------------
+// Geometry (host-built, adj_build): "period" is the replicated period, Mc = c M inputs <- Lc = c L cotangent samples, c such
+// that Mc >= 16 and Lc >= 64.  Workgroup x takes periods [x pb, x pb + pb); its slab holds gy frames
+// [x pb Lc + dmin, + x_count) of cg channels, frame n of it at LDS element (n + pad (n / Lc)) cg + channel: rows of
+// Lc + pad frames — an odd count, so that the lanes of a wave (stride one row) fall on different banks.  Phase tile st
+// (phases s = 16 st .. 16 st + 15) reads slab frames e0[st] + ii (ii < I) of its lane's period, coefficient tab[st][ii][s].
+template <typename Real>
+__global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
+{
+    constexpr int RS = kAdjRS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    Real *xs = reinterpret_cast<Real *>(smem_raw);
+    typedef const __attribute__((address_space(4))) Real *CPtr;
+
+    const int32_t Lc = (int32_t)a.Lc, Mc = (int32_t)a.Mc, pad = a.pad, cg = a.cg, pb = a.pb;
+    const int64_t q0 = (int64_t)blockIdx.x * pb; // first period of this workgroup
+    const int64_t g0 = q0 * a.Lc + a.dmin;       // gy frame of slab frame 0
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_all = (int)(blockDim.x >> 6);
+    const int32_t per = a.cg_shift >= 0 ? lane >> a.cg_shift : lane / cg, c = lane - per * cg;
+    const bool live = per < pb;
+    const int32_t rows = (a.x_count + Lc - 1) / Lc;
+    const int32_t row_elems = Lc * cg;
+
+    for (uint32_t y = blockIdx.y; y < a.n_clips * a.n_groups; y += gridDim.y) {
+        // (run-time division goes through the vector ALU; readfirstlane keeps the results on the scalar side)
+        const uint32_t clip = __builtin_amdgcn_readfirstlane(y / a.n_groups);
+        const uint32_t ch0 = __builtin_amdgcn_readfirstlane((y - clip * a.n_groups) * (uint32_t)cg);
+        const int32_t ncg = (int32_t)min((uint32_t)cg, a.n_channels - ch0); // channels of this group that exist
+        const Real *g = (const Real *)a.gy + (int64_t)clip * a.ics + (int64_t)ch0 * a.ichs;
+        if (y != blockIdx.y) __syncthreads(); // the slab of the column before is still being read
+
+        // stage: a wave per slab row, lanes along the row's (frame, channel) elements — whole frames of an interleaved
+        // tensor are read as they lie in memory
+        for (int32_t r = wave; r < rows; r += n_all) {
+            Real *dst = xs + (size_t)r * (size_t)((Lc + pad) * cg);
+            for (int32_t e = lane; e < row_elems; e += 64) {
+                const int32_t j = a.cg_shift >= 0 ? e >> a.cg_shift : e / cg, cc = e - j * cg;
+                const int32_t n = r * Lc + j;
+                if (n < a.x_count) {
+                    const int64_t f = g0 + n;
+                    dst[e] = (cc < ncg && f >= 0 && f < a.n_y) ? g[f * a.ifs + (int64_t)cc * a.ichs] : (Real)0;
+                }
+            }
+        }
+        __syncthreads();
+
+        const Real *xl = xs + (size_t)((live ? per : 0) * (Lc + pad) * cg + c); // this lane's (period, channel)
+        Real *const go = (Real *)a.gx + (int64_t)clip * a.ocs + (int64_t)(ch0 + c) * a.ochs;
+        const int64_t a0 = (q0 + per) * a.Mc; // first input frame of this lane's period
+        const bool store = live && c < ncg;
+
+        // (few workgroups: the phase tiles of a slab are spread over gridDim.z workgroups, each staging the slab)
+        for (int st_ = wave < a.n_waves ? wave + a.n_waves * (int)blockIdx.z : a.n_st; st_ < a.n_st; st_ += a.n_waves * (int)gridDim.z) {
+            // keep the tile index (and everything derived from it) provably wave-uniform: the coefficient loads below
+            // must be scalar (s_load), not per-lane
+            const int st = __builtin_amdgcn_readfirstlane(st_);
+            const int32_t e0 = __builtin_amdgcn_readfirstlane(a.e0[st]);
+            CPtr t = (CPtr)((const Real *)a.tab + (size_t)st * a.I * RS);
+            Real acc[RS];
+#pragma unroll
+            for (int rr = 0; rr < RS; ++rr) acc[rr] = 0;
+            // slab frame m of this lane's period lies at element (m + pad * (m / Lc)) * cg of its row: m walks upwards, the
+            // row crossings are counted on the scalar side
+            const int32_t row0 = __builtin_amdgcn_readfirstlane(e0 / Lc);
+            int32_t m = e0, next = (row0 + 1) * Lc, off = (e0 + pad * row0) * cg;
+            for (int32_t qd = 0; qd < a.I; qd += 4) {
+                Real x[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    x[u] = xl[off];
+                    ++m; off += cg;
+                    if (m == next) { off += pad * cg; next += Lc; }
+                }
+                CPtr tq = t + (size_t)qd * RS;
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int rr = 0; rr < RS; ++rr) acc[rr] = fma_r(tq[u * RS + rr], x[u], acc[rr]);
+            }
+            const int32_t s0 = st * RS;
+#pragma unroll
+            for (int rr = 0; rr < RS; ++rr) {
+                const int64_t fr = a0 + s0 + rr;
+                if (store && s0 + rr < Mc && fr < a.n_x) go[fr * a.ofs] = acc[rr];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// host: transposed bank, cache, launch
+// ---------------------------------------------------------------------------------------------
+static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; } // b > 0
+static inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+
+struct AdjBank {
+    const Plan *plan = nullptr;
+    int device = -1;
+    int64_t L = 1, M = 1, Lc = 1, Mc = 1;
+    int32_t Tt = 0, dmin = 0;
+    void *ct[2] = {nullptr, nullptr}; // [Tt][M], 0 = f32, 1 = f64
+    int32_t *d_lo = nullptr;          // [M]
+    bool tile = false;                // the period fits LDS: tables of k_adj_tile
+    int32_t n_st = 0, I = 0, wmax = 0, pad = 0;
+    void *tab[2] = {nullptr, nullptr}; // [n_st][I][16]
+    int32_t *e0 = nullptr;             // [n_st]
+};
+
+static std::mutex g_adj_mu;
+static std::vector<AdjBank *> g_adj; // one per plan (a plan's device tables live on one device)
+
+static void adj_free(AdjBank *b)
+{
+    for (int i = 0; i < 2; ++i) {
+        if (b->ct[i]) (void)hipFree(b->ct[i]);
+        if (b->tab[i]) (void)hipFree(b->tab[i]);
+    }
+    if (b->d_lo) (void)hipFree(b->d_lo);
+    if (b->e0) (void)hipFree(b->e0);
+    delete b;
+}
+
+void adjoint_release(const Plan *p)
+{
+    std::lock_guard<std::mutex> lk(g_adj_mu);
+    for (size_t i = 0; i < g_adj.size();)
+        if (g_adj[i]->plan == p) {
+            adj_free(g_adj[i]);
+            g_adj.erase(g_adj.begin() + i);
+        } else ++i;
+}
+
+template <typename Real>
+static const char *adj_upload(void **dst, const std::vector<double> &src)
+{
+    std::vector<Real> v(src.size());
+    for (size_t i = 0; i < src.size(); ++i) v[i] = (Real)src[i]; // float32: the float64 bank rounded to nearest
+    HIP_TRY(hipMalloc(dst, std::max<size_t>(v.size(), 1) * sizeof(Real)));
+    HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(Real), hipMemcpyHostToDevice));
+    return nullptr;
+}
+
+static const char *adj_build(const Plan &p, AdjBank *b)
+{
+    const int64_t L = p.L, M = p.M, H = p.T / 2;
+    const int32_t T = p.T;
+    b->L = L; b->M = M;
+    auto d_lo = [&](int64_t s) { return ceil_div((s - H) * L, M); };
+    auto d_hi = [&](int64_t s) { return ceil_div((s + H) * L, M) - 1; };
+    // coefficient of gy[q L + d] in gx[q M + s]: c[(d M) mod L][s + T/2 - 1 - floor(d M / L)], 0 outside the phase's terms
+    auto coef = [&](int64_t s, int64_t d) -> double {
+        if (d < d_lo(s) || d > d_hi(s)) return 0.0;
+        const int64_t nfl = floor_div(d * M, L), ph = d * M - nfl * L, j = s + H - 1 - nfl;
+        return (j >= 0 && j < T) ? p.bank[(size_t)(ph * T + j)] : 0.0;
+    };
+    int64_t Tt = 0;
+    std::vector<int32_t> lo((size_t)M);
+    for (int64_t s = 0; s < M; ++s) {
+        lo[(size_t)s] = (int32_t)d_lo(s);
+        Tt = std::max(Tt, d_hi(s) - d_lo(s) + 1);
+    }
+    b->Tt = (int32_t)Tt;
+    b->dmin = lo[0]; // d_lo is non-decreasing in s
+    {
+        std::vector<double> ct((size_t)(Tt * M));
+        for (int64_t s = 0; s < M; ++s)
+            for (int64_t i = 0; i < Tt; ++i) ct[(size_t)(i * M + s)] = coef(s, lo[(size_t)s] + i);
+        if (const char *e = adj_upload<float>(&b->ct[0], ct)) return e;
+        if (const char *e = adj_upload<double>(&b->ct[1], ct)) return e;
+        HIP_TRY(hipMalloc((void **)&b->d_lo, (size_t)M * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(b->d_lo, lo.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    // k_adj_tile: the period replicated until a wave tile (16 phases) and a slab row (64 frames) are filled
+    const int64_t c = std::max((kAdjRS + M - 1) / M, (64 + L - 1) / L);
+    b->Lc = c * L; b->Mc = c * M;
+    b->pad = (b->Lc & 1) ? 0 : 1;
+    if (b->Lc > 8192 || b->Mc > 65536) return nullptr; // (16 periods of float32 would not fit LDS: k_adj_gather serves the plan)
+    const int32_t n_st = (int32_t)((b->Mc + kAdjRS - 1) / kAdjRS);
+    int64_t I = 0;
+    for (int32_t st = 0; st < n_st; ++st) {
+        const int64_t s0 = (int64_t)st * kAdjRS, s1 = std::min<int64_t>(s0 + kAdjRS, b->Mc) - 1;
+        I = std::max(I, d_hi(s1) - d_lo(s0) + 1);
+    }
+    I = (I + 3) / 4 * 4;
+    std::vector<int32_t> e0((size_t)n_st);
+    std::vector<double> tab((size_t)n_st * (size_t)I * kAdjRS, 0.0);
+    int64_t wmax = 0;
+    for (int32_t st = 0; st < n_st; ++st) {
+        const int64_t s0 = (int64_t)st * kAdjRS, first = d_lo(s0);
+        e0[(size_t)st] = (int32_t)(first - b->dmin);
+        wmax = std::max(wmax, first - b->dmin + I);
+        for (int64_t ii = 0; ii < I; ++ii)
+            for (int rr = 0; rr < kAdjRS; ++rr)
+                if (s0 + rr < b->Mc) tab[((size_t)st * (size_t)I + (size_t)ii) * kAdjRS + rr] = coef(s0 + rr, first + ii);
+    }
+    b->n_st = n_st; b->I = (int32_t)I; b->wmax = (int32_t)wmax;
+    if (const char *e = adj_upload<float>(&b->tab[0], tab)) return e;
+    if (const char *e = adj_upload<double>(&b->tab[1], tab)) return e;
+    HIP_TRY(hipMalloc((void **)&b->e0, (size_t)n_st * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(b->e0, e0.data(), (size_t)n_st * sizeof(int32_t), hipMemcpyHostToDevice));
+    b->tile = true;
+    return nullptr;
+}
+
+// The plan's transposed tables, built on first use (exact-bank plans; the caller has checked).
+static const char *adj_ensure(Plan *p, AdjBank **out)
+{
+    int cur = -1;
+    HIP_TRY(hipGetDevice(&cur));
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (p->device >= 0 && cur != p->device) return "this plan's device tables live on another device (one plan per device)";
+        if (p->device < 0) p->device = cur;
+    }
+    std::lock_guard<std::mutex> lk(g_adj_mu);
+    for (AdjBank *b : g_adj)
+        if (b->plan == p) { *out = b; return nullptr; }
+    AdjBank *b = new AdjBank();
+    b->plan = p; b->device = cur;
+    if (const char *e = adj_build(*p, b)) { adj_free(b); return e; }
+    g_adj.push_back(b);
+    *out = b;
+    return nullptr;
+}
+
+template <typename Real>
+static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st)
+{
+    const int prec = sizeof(Real) == 4 ? 0 : 1;
+    AdjArgs a{};
+    a.gy = j.in; a.gx = j.out;
+    a.ct = b.ct[prec]; a.d_lo = b.d_lo; a.tab = b.tab[prec]; a.e0 = b.e0;
+    a.L = b.L; a.M = b.M; a.Lc = b.Lc; a.Mc = b.Mc;
+    a.Tt = b.Tt; a.n_st = b.n_st; a.I = b.I; a.dmin = b.dmin; a.pad = b.pad;
+    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
+    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
+    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.n_y = j.in_frames; a.n_x = j.out_frames;
+    const bool inter = j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1; // frames of interleaved channels
+    a.inter = inter ? 1 : 0;
+
+    if (b.tile && j.out_frames >= kAdjMinPeriods * b.Mc) {
+        // lanes per workgroup slab: 64 (32, 16 where LDS demands); two workgroups per CU where that is possible
+        size_t lds = 0;
+        int lanes = 0;
+        for (size_t limit : {(size_t)80 * 1024, (size_t)160 * 1024}) {
+            for (int ln : {64, 32, 16}) {
+                const int32_t cg = inter ? (int32_t)std::min<uint32_t>(j.n_channels, (uint32_t)ln) : 1, pb = ln / cg;
+                const int64_t xc = (int64_t)(pb - 1) * b.Lc + b.wmax, rows = (xc + b.Lc - 1) / b.Lc;
+                const size_t need = (size_t)(rows * (b.Lc + b.pad)) * (size_t)cg * sizeof(Real);
+                if (need <= limit) { lanes = ln; lds = need; a.cg = cg; a.pb = pb; a.x_count = (int32_t)xc; break; }
+            }
+            if (lanes) break;
+        }
+        const int64_t n_per = (j.out_frames + b.Mc - 1) / b.Mc;
+        const int64_t gx = lanes ? (n_per + a.pb - 1) / a.pb : 0;
+        if (lanes && gx <= 2147483647LL) {
+            a.cg_shift = -1;
+            for (int sh = 0; sh < 7; ++sh)
+                if ((1 << sh) == a.cg) a.cg_shift = sh;
+            a.n_groups = (j.n_channels + (uint32_t)a.cg - 1) / (uint32_t)a.cg;
+            const uint64_t cols = (uint64_t)j.n_clips * a.n_groups;
+            const uint32_t gy = (uint32_t)std::min<uint64_t>(cols, 65535);
+            // few workgroups: spread a slab's phase tiles over z workgroups until the chip has ~4 per CU
+            const int64_t wgs = gx * (int64_t)gy;
+            int z = (int)std::min<int64_t>(b.n_st, std::max<int64_t>(1, 1024 / wgs));
+            int nw = std::min(16, (b.n_st + z - 1) / z);
+            z = std::min(z, (b.n_st + nw - 1) / nw);
+            a.n_waves = nw;
+            if (const char *e = ensure_dyn_lds((const void *)k_adj_tile<Real>, lds)) return e;
+            hipLaunchKernelGGL(k_adj_tile<Real>, dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, a);
+            HIP_TRY(hipGetLastError());
+            return nullptr;
+        }
+    }
+    const int64_t per_clip = j.out_frames * (int64_t)j.n_channels;
+    const int64_t gx = (per_clip + 255) / 256;
+    if (gx > 2147483647LL) return "adjoint job: too long for one launch";
+    hipLaunchKernelGGL(k_adj_gather<Real>, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
+    if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
+    if (p->phases) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
+    if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
+    if (j.clip_table) return "adjoint job: ragged batches (clip_table) are not served";
+    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT)
+        return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
+    if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
+    if ((uint64_t)j.in_frames > plan_out_len(*p, (uint64_t)j.out_frames))
+        return "adjoint job: in_frames (cotangent frames) exceeds the plan's output length for out_frames";
+    if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+    if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    AdjBank *b = nullptr;
+    if (const char *e = adj_ensure(p, &b)) return e;
+    return j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, (hipStream_t)stream) : adj_launch<double>(*b, j, (hipStream_t)stream);
+}
+
+} // namespace hipsoxr

@@ -182,5 +182,9 @@ const char *launch_fft_window(Plan *p, const hipsoxr_job_t &job, void *stream, b
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+// transposed operator of the exact engine (adjoint.hip; hipsoxr_run_device_adjoint): job.in = gy (in_frames of it), job.out = gx
+// (out_frames of it); validates the job itself.  adjoint_release drops the plan's transposed tables (rebuilt on next use).
+const char *launch_adjoint(Plan *p, const hipsoxr_job_t &job, void *stream);
+void adjoint_release(const Plan *p);
 
 } // namespace hipsoxr

@@ -36,7 +36,7 @@ struct hipsoxr_plan {
 };
 
 namespace hipsoxr {
-Plan::~Plan() { twostage_release(this); device_bank_release(this); fft_release(this); }
+Plan::~Plan() { twostage_release(this); device_bank_release(this); fft_release(this); adjoint_release(this); }
 } // namespace hipsoxr
 
 // Variable-rate state (SOXR_VR streams; reference: src/soxr_ext.cpp:74, :200-204).  Time is kept in
@@ -415,6 +415,7 @@ hipsoxr_error_t hipsoxr_plan_set_bank(hipsoxr_plan_t *h, const double *src, size
     device_bank_release(&h->p);
     fft_release(&h->p);
     twostage_release(&h->p);
+    adjoint_release(&h->p);
     note_bank_change(h->p, src, n);
     std::memcpy(h->p.bank.data(), src, n * sizeof(double));
     return nullptr;
@@ -459,6 +460,7 @@ hipsoxr_error_t hipsoxr_plan_broadcast(hipsoxr_plan_t *h, void *nccl_comm, int r
                 device_bank_release(&h->p);
                 fft_release(&h->p);
                 twostage_release(&h->p);
+                adjoint_release(&h->p);
                 note_bank_change(h->p, got.data(), n);
                 h->p.bank.swap(got);
             }
@@ -483,6 +485,12 @@ hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, 
     if ((job->out_frames > 0 && !job->out) || (job->out_frames > 0 && job->in_frames > 0 && !job->in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;
     return launch_job(&h->p, *job, hip_stream);
+}
+
+hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *h, const hipsoxr_job_t *job, void *hip_stream)
+{
+    if (!h || !job) return "null argument";
+    return launch_adjoint(&h->p, *job, hip_stream); // (refusals, by name, and the empty job: there)
 }
 
 } // extern "C"

@@ -73,6 +73,20 @@ class Plan:
         j.dither, j.dither_seed = int(bool(dither)), dither_seed
         _n.check(_n.lib.hipsoxr_run_device(self._h, _C.byref(j), stream))
 
+    def run_adjoint(self, gy_ptr, gx_ptr, elem, n_clips, n_channels, gy_frames, gx_frames, gy_strides, gx_strides,
+                    stream=None, kernel=_n.KERNEL_AUTO, clip_table=None):
+        """Raw launch of the transposed operator (hipsoxr_run_device_adjoint): gx = A^T gy for the forward job A that
+        `run(..., kernel=KERNEL_EXACT)` computes — gy has gy_frames <= out_len(gx_frames) frames, gx has gx_frames.
+        Device pointers (ints), strides = (clip, frame, channel) in elements.  float32 / float64, exact-bank plans."""
+        j = _n.Job()
+        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
+        j.n_clips, j.n_channels = n_clips, n_channels
+        j.in_clip_stride, j.in_frame_stride, j.in_chan_stride = gy_strides
+        j.out_clip_stride, j.out_frame_stride, j.out_chan_stride = gx_strides
+        j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, gy_frames, 0, gx_frames
+        j.clip_table = clip_table
+        _n.check(_n.lib.hipsoxr_run_device_adjoint(self._h, _C.byref(j), stream))
+
 
 class PreparedJob:
     """A device job whose descriptor is built once: `launch()` is a single C call
@@ -121,6 +135,106 @@ def _torch_elem(dtype):
         raise TypeError(f"Data type must be one of [float32, float64, int16, int32], not {dtype}")
 
 
+def _as3(t):
+    if t.ndim == 1:
+        return t[None, :, None]
+    if t.ndim == 2:
+        return t[None]
+    if t.ndim != 3:
+        raise ValueError("Input must be 1-D, 2-D or 3-D")
+    return t
+
+
+def _like_rank(t3, ndim):
+    return t3[0, :, 0] if ndim == 1 else (t3[0] if ndim == 2 else t3)
+
+
+def _adjoint_refusal(plan, elem):
+    """The C entry's own refusal of (plan, element type) for an adjoint job, or None: asked with an empty job, so that a
+    forward that could not be differentiated fails when it is called, not in the middle of backward."""
+    try:
+        plan.run_adjoint(None, None, elem, 0, 0, 0, 0, (0, 0, 0), (0, 0, 0))
+    except RuntimeError as e:
+        return str(e)
+    return None
+
+
+def resample_tensor_adjoint(plan, gy, in_frames, out=None):
+    """The transposed operator as a function: gx = A^T gy, where A is the resample of `in_frames` input frames that
+    `resample_tensor(plan, x, kernel=KERNEL_EXACT)` computes (what its backward pass runs; the adjoint an iterative
+    solver needs).  On the current torch stream, asynchronously.
+
+    gy : [frames] | [frames, channels] | [clips, frames, channels] float32 / float64 device tensor, any strides, with at
+         most plan.out_len(in_frames) frames (a truncated forward output has a truncated cotangent).
+    Returns a tensor of the same rank with in_frames frames (`out` may be supplied); every element is written.
+    Gather form on the transposed bank, no atomics: bitwise reproducible, independent of layout.  Differentiable (its
+    backward is the forward on the exact engine).  Exact-bank plans only: interpolated-phase plans (and their two-stage
+    form), variable rate, streams, ragged batches, dist.py and integer types are not served."""
+    if not gy.is_cuda:
+        raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
+    import torch
+    if out is None and gy.requires_grad and torch.is_grad_enabled():
+        return _autograd_fns()[1].apply(gy, plan, int(in_frames))
+    if out is not None and gy.requires_grad and torch.is_grad_enabled():
+        raise ValueError("out= cannot be combined with a tensor that requires grad")
+    return _adjoint_plain(plan, gy, int(in_frames), out)
+
+
+def _adjoint_plain(plan, gy, in_frames, out=None):
+    import torch
+    elem = _torch_elem(gy.dtype)
+    g3 = _as3(gy)
+    clips, n_y, ch = g3.shape
+    if out is None:
+        o3 = torch.empty((clips, in_frames, ch), dtype=gy.dtype, device=gy.device)
+    else:
+        o3 = _as3(out)
+        if tuple(o3.shape) != (clips, in_frames, ch) or out.dtype != gy.dtype:
+            raise ValueError(f"out has shape {tuple(out.shape)}, expected frames={in_frames}")
+    stream = torch.cuda.current_stream(gy.device).cuda_stream
+    # (an empty job still goes to the C entry: it is what refuses an integer type or an interpolated-phase plan)
+    plan.run_adjoint(g3.data_ptr(), o3.data_ptr(), elem, clips, ch, n_y, in_frames, tuple(g3.stride()),
+                     tuple(o3.stride()), stream=stream)
+    return _like_rank(o3, gy.ndim)
+
+
+_AUTOGRAD = None
+
+
+def _autograd_fns():
+    """The torch.autograd.Function pair (built on first use: torch is imported lazily everywhere in this module).
+    Resampling is linear: the forward's backward is the adjoint, the adjoint's backward is the forward on the exact
+    engine — so double backward works and both functions are differentiable to any order."""
+    global _AUTOGRAD
+    if _AUTOGRAD is not None:
+        return _AUTOGRAD
+    import torch
+
+    class ResampleFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, plan, kernel):
+            ctx.plan, ctx.frames = plan, _as3(x).shape[1]
+            return _resample_plain(plan, x.detach(), kernel=kernel)
+
+        @staticmethod
+        def backward(ctx, gy):
+            return resample_tensor_adjoint(ctx.plan, gy, ctx.frames), None, None
+
+    class AdjointFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, gy, plan, in_frames):
+            ctx.plan, ctx.n_y = plan, _as3(gy).shape[1]
+            return _adjoint_plain(plan, gy.detach(), in_frames)
+
+        @staticmethod
+        def backward(ctx, ggx):
+            y = resample_tensor(ctx.plan, ggx, kernel=_n.KERNEL_EXACT)
+            return y.narrow(y.ndim - 2 if y.ndim > 1 else 0, 0, ctx.n_y), None, None
+
+    _AUTOGRAD = (ResampleFn, AdjointFn)
+    return _AUTOGRAD
+
+
 def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
     """Resample a device tensor on the current torch stream, asynchronously.
 
@@ -131,7 +245,28 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     clip_counter = a one-element int64 / uint64 device tensor that counts saturated outputs.  AUTO keeps them on the
     canonical-order engine; kernel=KERNEL_FFT_PCM asks for the frequency-domain engine (int16 in float32, int32 in
     float64 arithmetic, the same output stage: within 1 LSB of the canonical order, not bit-identical to it).
+
+    Differentiable: when x.requires_grad (and grad mode is on) the result carries a grad_fn whose backward is the
+    transposed operator (`resample_tensor_adjoint`), so gradients — and gradients of gradients — flow through a
+    resample.  `kernel` is honoured for the forward; `out=` is then a ValueError; plans the adjoint does not serve
+    (interpolated-phase plans, integer tensors) raise when the forward is called.  The gradient is the EXACT engine's
+    adjoint: where AUTO sends a large forward to the frequency-domain engine, forward and gradient agree in that engine's
+    1e-6 class, not to rounding (kernel=KERNEL_EXACT: to rounding).  Without requires_grad nothing changes.
     """
+    if x.is_cuda and x.requires_grad:
+        import torch
+        if torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("out= cannot be combined with a tensor that requires grad")
+            why = _adjoint_refusal(plan, _torch_elem(x.dtype))
+            if why:
+                raise RuntimeError(why)
+            return _autograd_fns()[0].apply(x, plan, kernel)
+    return _resample_plain(plan, x, out, kernel, dither, clip_counter, dither_seed)
+
+
+def _resample_plain(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
+    """`resample_tensor` proper: the launch, without autograd."""
     import torch
     if not x.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
