@@ -14,10 +14,24 @@
 //     gx[q M + s] = sum_{i<Tt} ct[s][i] gy[q L + d_lo(s) + i],     gy zero outside [0, n_y).
 //
 // ARITHMETIC: every gx element is ONE fma chain in the element's own width over ascending k, started from +0.  The tables
-// of the tiled kernel hold extra zeros in front of and behind a phase's terms; fma(0, gy, acc) == acc for finite gy, so both
-// kernels below give the same bits and a result does not depend on layout, tiling or launch shape.  The float32 tables
-// are the float64 bank rounded to nearest — the values the float32 forward engine multiplies by: forward and adjoint are
-// transposes of one matrix.
+// of the tiled kernel hold extra zeros in front of and behind a phase's terms; fma(0, gy, acc) == acc for finite gy, so FOR
+// FINITE COTANGENTS both kernels below give the same bits and a result does not depend on layout, tiling or launch shape.
+// The float32 tables are the float64 bank rounded to nearest — the values the float32 forward engine multiplies by: forward
+// and adjoint are transposes of one matrix.
+//
+// REACH of a non-finite cotangent sample: 0 * inf = NaN, so an infinite or NaN gy[k] makes every gx[a] non-finite whose
+// chain multiplies it, by a table zero or not.  The true support of gy[k] is 0 <= a - n0_k < T, i.e. |a - k M/L| <= T/2.
+//   k_adj_gather  gx[a] reads gy[lo(a) .. lo(a) + Tt - 1], lo(a) = ceil((a - T/2) L / M): Tt is the maximum over phases,
+//                 so a phase with fewer terms reads on behind its last one.  k >= lo(a) gives a <= k M/L + T/2, and
+//                 k <= lo(a) + Tt - 1 with Tt <= ceil(T L/M) + 1 < T L/M + 2 gives a > k M/L + T/2 - Tt M/L:
+//                     -(T/2 + 2 M/L) < a - k M/L <= T/2.
+//   k_adj_tile    all 16 phases of a wave tile read gy[lo(a0) .. lo(a0) + I - 1], a0 <= a <= a0 + 15 the tile's first frame;
+//                 I is the maximum over tiles of the span from the first term of the tile's first phase to the last term
+//                 of its last, rounded up to a multiple of 4: I < (T + 15) L/M + 4.  The same two steps on a0 give
+//                     -(T/2 + 15 + 4 M/L) < a - k M/L <= T/2 + 15.
+// Every gx[a] outside these intervals (and every other column) never reads gy[k]: it has the bits it would have with any
+// finite value there.  Which elements inside them turn non-finite depends on the kernel, hence on the launch form
+// (tests/test_gpu_adjoint_forms.py pins both sides).
 //
 // Kernels:
 //   k_adj_gather  one lane per gx element; transposed bank tap-major [Tt][M] (lanes of neighbouring phases read
@@ -33,6 +47,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <mutex>
 #include <vector>
 
@@ -330,6 +345,17 @@ static const char *adj_ensure(Plan *p, AdjBank **out)
     return nullptr;
 }
 
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per launch, in the style of fft.hip's fft_launch_log — what
+// tests/test_gpu_adjoint_forms.py reads the launch form from.
+static void adj_launch_log(const char *kernel, size_t width, const AdjBank &b, int lanes, size_t lds, const AdjArgs &a, dim3 grid, unsigned nt)
+{
+    FILE *f = fopen(switches().dbg_launch_log, "a");
+    if (!f) return;
+    fprintf(f, "kernel=%s width=%zu L=%lld M=%lld lanes=%d lds=%zu cg=%d pb=%d grid=%ux%ux%u block=%u n_st=%d\n", kernel, width,
+            (long long)b.L, (long long)b.M, lanes, lds, a.cg, a.pb, grid.x, grid.y, grid.z, nt, b.n_st);
+    fclose(f);
+}
+
 template <typename Real>
 static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st)
 {
@@ -377,6 +403,7 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
             if (const char *e = ensure_dyn_lds((const void *)k_adj_tile<Real>, lds)) return e;
             hipLaunchKernelGGL(k_adj_tile<Real>, dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, a);
             HIP_TRY(hipGetLastError());
+            if (switches().dbg_launch_log) adj_launch_log("adj_tile", sizeof(Real), b, lanes, lds, a, dim3((uint32_t)gx, gy, (uint32_t)z), (unsigned)nw * 64);
             return nullptr;
         }
     }
@@ -385,6 +412,7 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
     if (gx > 2147483647LL) return "adjoint job: too long for one launch";
     hipLaunchKernelGGL(k_adj_gather<Real>, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) adj_launch_log("adj_gather", sizeof(Real), b, 0, 0, a, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535), 1), 256);
     return nullptr;
 }
 
