@@ -130,6 +130,17 @@ typedef enum {
                                   (ragged batches included) and int16 interleaved channel pairs; float jobs and
                                   anything else it cannot serve are an error, never a run of another engine. */
 } hipsoxr_kernel_t;
+/* Selector of hipsoxr_run_device_adjoint alone (job.kernel there; the forward entries refuse it by name), numbered on from
+ * hipsoxr_kernel_t. */
+typedef enum {
+    HIPSOXR_KERNEL_ADJOINT = 10 /* hipsoxr_run_device_adjoint only: the exact engine's transposed operator for EVERY
+                                  constant-rate plan.  On an exact-bank plan it runs what AUTO runs there, bit for bit; on an
+                                  interpolated-phase plan (hipsoxr_plan_info_t::interpolated != 0, which AUTO and EXACT
+                                  refuse) the gather-form adjoint on the plan's own interpolation table — the coefficients
+                                  the forward's HIPSOXR_KERNEL_EXACT multiplies by, to the bit.  float32 / float64, whole
+                                  signals, no clip_table, constant-rate plans (not hipsoxr_plan_create_vr's); refused by
+                                  name otherwise, and on hipsoxr_run_device. */
+} hipsoxr_adjoint_kernel_t;
 
 typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase bank (host + device) */
 typedef struct hipsoxr_stream hipsoxr_stream_t; /* stateful converter: the `soxr_t` counterpart */
@@ -214,7 +225,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
@@ -227,7 +238,8 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *, const hipsoxr_j
  * element of gx is written (0 where no output reads the input), nothing outside it; gather form, no atomics: results are
  * bitwise reproducible and independent of layout.  HIPSOXR_F32 / HIPSOXR_F64 on exact-bank plans; kernel = HIPSOXR_KERNEL_AUTO
  * or _EXACT; in_abs0 == 0, out_k0 == 0, clip_table == NULL; anything else is an error that names the reason, never a run of
- * another path.  Zero frames, clips or channels: success, nothing launched.  Asynchronous on `hip_stream`. */
+ * another path.  kernel = HIPSOXR_KERNEL_ADJOINT: the same on every constant-rate plan, interpolated-phase plans included
+ * (A is then the forward HIPSOXR_KERNEL_EXACT computes from the plan's interpolation table).  Zero frames, clips or channels: success, nothing launched.  Asynchronous on `hip_stream`. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
 
 /* ---- stream: the soxr_t counterpart (host pointers, state carried across calls) ----------- */

@@ -43,6 +43,24 @@
 //                 wave owns 16 consecutive phases, whose coefficients travel on the scalar path (s_load -> SGPR operands
 //                 of the FMAs) from a per-tile table [I][16] skewed to the tile's first gy sample and zero-padded: one
 //                 LDS read feeds 16 FMAs.
+//   k_adj_interp  interpolated-phase plans (Plan.phases != 0), asked for by name: HIPSOXR_KERNEL_ADJOINT.  There is no bank
+//                 to transpose: the coefficient of gy[k] in gx[a] is tap j = a - q_k + T/2 - 1 of the cubic the forward
+//                 evaluates for output k (kernels_interp.h k_interp: t = k M, q_k = t div L, r = t mod L, iv = (r P) div L,
+//                 xx = (((r P) mod L) << SH) div L * 2^-SH, c_j = fma(fma(fma(a3, xx, a2), xx, a1), xx, a0) from the plan's
+//                 device table [P][T]) — the same table, the same integer arithmetic, the same fma nesting, so the very bits
+//                 the forward multiplies by.  Gather form:
+//                     gx[a] = sum_{k = k_lo(a)}^{k_hi(a)} c_{a - q_k + T/2 - 1}(k) gy[k],
+//                     k_lo(a) = max(0, ceil((a - T/2) L / M)),   k_hi(a) = min(n_y, ceil((a + T/2) L / M)) - 1,
+//                 at most ceil(T L / M) + 1 terms, one fma chain over ascending k from +0.  A workgroup takes a tile of
+//                 kAdjIW consecutive frames of one column and walks the tile's contiguous k range in chunks of kAdjIC: per
+//                 chunk every thread locates ONE k (the 64-bit divisions are per k, not per (a, k)) and stages its record
+//                 (q_k - a0, iv T, xx, gy[k]) in LDS — constant LDS whatever L / M.  Then each wave walks the UNION of its
+//                 64 lanes' k ranges inside the chunk: at one k all lanes sit in ONE table row and lane a reads tap
+//                 j(a) — 64 neighbouring 16- / 32-byte records, whole lines — and a lane whose j falls outside [0, T) keeps
+//                 its sum (a select, not a multiplication by zero).
+//                 REACH: 0 <= j < T is exactly a - T/2 <= q_k <= a + T/2 - 1, the true support of gy[k]: a lane never
+//                 multiplies outside its own [k_lo, k_hi], there is no padding and no 0 * inf.  A non-finite gy[k] reaches
+//                 the gx[a] of its true support and nothing else — tighter than the two exact-bank kernels above.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -84,6 +102,9 @@ struct AdjArgs {
     int64_t ics, ifs, ichs, ocs, ofs, ochs;
     int64_t n_y, n_x;
 };
+
+__host__ __device__ static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; } // b > 0
+__host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 
 __device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_r(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -210,11 +231,92 @@ __global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
 }
 
 // ---------------------------------------------------------------------------------------------
+// k_adj_interp
+// ---------------------------------------------------------------------------------------------
+static constexpr int kAdjIW = 256; // gx frames per workgroup tile (one per thread)
+static constexpr int kAdjIC = 256; // cotangent samples located and staged per chunk (one per thread)
+
+struct AdjInterpArgs {
+    const void *gy;
+    void *gx;
+    const void *tab; // the plan's device table [P][T] of Vec4<Real> (a0..a3), the forward's own
+    int64_t L, M;
+    int32_t T, P;
+    uint64_t n_cols; // clips x channels
+    uint32_t n_channels;
+    int64_t ics, ifs, ichs, ocs, ofs, ochs;
+    int64_t n_y, n_x;
+};
+
+template <typename Real> struct AdjVec4;
+template <> struct AdjVec4<float> { typedef float4 type; };
+template <> struct AdjVec4<double> { typedef double4 type; };
+// what the forward knows about output k, relative to the tile: q_k - a0, the row offset iv_k T, the cubic's argument, gy[k]
+template <typename Real> struct AdjRec { int32_t dq, row; Real xx, g; };
+
+// UNION: a wave walks the union of its lanes' k ranges (wave-uniform k: one table row per step, neighbouring records);
+// else every lane walks its own [k_lo, k_hi] (no idle steps, 64 rows per step).  Same terms in the same order either way.
+template <typename Real, bool UNION>
+__global__ void __launch_bounds__(kAdjIW) k_adj_interp(AdjInterpArgs a)
+{
+    typedef typename AdjVec4<Real>::type V4;
+    constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
+    __shared__ AdjRec<Real> rec[kAdjIC];
+    const int32_t T = a.T, H = T / 2;
+    const int tid = (int)threadIdx.x;
+    const int64_t a0 = (int64_t)blockIdx.x * kAdjIW, fr = a0 + tid;
+    const int64_t a_end = a0 + kAdjIW < a.n_x ? a0 + kAdjIW : a.n_x; // the tile's frames: [a0, a_end), never empty
+    auto k_lo = [&](int64_t f) { const int64_t k = ceil_div((f - H) * a.L, a.M); return k > 0 ? k : (int64_t)0; };
+    auto k_hi = [&](int64_t f) { const int64_t k = ceil_div((f + H) * a.L, a.M); return (k < a.n_y ? k : a.n_y) - 1; };
+    const int64_t k_first = k_lo(a0), k_end = k_hi(a_end - 1) + 1; // the tile reads gy[k_first, k_end)
+    // this wave's (UNION) or this lane's walk, relative to k_first: [wl, wh], empty behind the signal's end
+    const int64_t f0 = UNION ? a0 + (tid & ~63) : fr, f1 = UNION ? (f0 + 63 < a_end ? f0 + 63 : a_end - 1) : fr;
+    int32_t wl = 0, wh = -1;
+    if (f0 < a_end) { wl = (int32_t)(k_lo(f0) - k_first); wh = (int32_t)(k_hi(f1) - k_first); }
+    if (UNION) { wl = __builtin_amdgcn_readfirstlane(wl); wh = __builtin_amdgcn_readfirstlane(wh); }
+    const int32_t jb = tid + H - 1; // tap of gy[k] in this lane's frame: fr - q_k + H - 1 = jb - (q_k - a0)
+    const V4 *tab = (const V4 *)a.tab;
+
+    for (uint64_t col = blockIdx.y; col < a.n_cols; col += gridDim.y) {
+        const int64_t clip = (int64_t)(col / a.n_channels), ch = (int64_t)(col - (uint64_t)clip * a.n_channels);
+        const Real *g = (const Real *)a.gy + clip * a.ics + ch * a.ichs;
+        Real acc = 0;
+        for (int64_t kc = k_first; kc < k_end; kc += kAdjIC) {
+            __syncthreads(); // the chunk before is still being read
+            const int64_t k = kc + tid;
+            if (k < k_end) { // k_interp's own arithmetic (kernels_interp.h, the constant-rate branch with p0 = d0 = 0)
+                const int64_t t = k * a.M, q = t / a.L;
+                const uint64_t r = (uint64_t)(t - q * a.L);
+                const uint64_t tp = r * (uint64_t)a.P, rem = tp % (uint64_t)a.L, iv = tp / (uint64_t)a.L;
+                const uint64_t xq = (rem << SH) / (uint64_t)a.L;
+                AdjRec<Real> rc;
+                rc.dq = (int32_t)(q - a0);
+                rc.row = (int32_t)iv * T;
+                rc.xx = (Real)xq * (Real)(1. / (double)(1ULL << SH));
+                rc.g = g[k * a.ifs];
+                rec[tid] = rc;
+            }
+            __syncthreads();
+            const int64_t c0 = kc - k_first;
+            const int32_t i0 = (int32_t)((wl > c0 ? wl : c0) - c0), i1 = (int32_t)((wh < c0 + kAdjIC - 1 ? wh : c0 + kAdjIC - 1) - c0);
+#pragma unroll 4
+            for (int32_t i = i0; i <= i1; ++i) {
+                const AdjRec<Real> rc = rec[i];
+                const int32_t j = jb - rc.dq;
+                const bool mine = (uint32_t)j < (uint32_t)T; // a - H <= q_k <= a + H - 1: k in this lane's own [k_lo, k_hi]
+                // (the load is unconditional, clamped into the row: a load under a condition is waited for at once)
+                const V4 v = tab[rc.row + (j < 0 ? 0 : j < T ? j : T - 1)];
+                const Real c = fma_r(fma_r(fma_r(v.w, rc.xx, v.z), rc.xx, v.y), rc.xx, v.x);
+                acc = mine ? fma_r(c, rc.g, acc) : acc;
+            }
+        }
+        if (fr < a.n_x) ((Real *)a.gx)[clip * a.ocs + fr * a.ofs + ch * a.ochs] = acc;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // host: transposed bank, cache, launch
 // ---------------------------------------------------------------------------------------------
-static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; } // b > 0
-static inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
-
 struct AdjBank {
     const Plan *plan = nullptr;
     int device = -1;
@@ -416,14 +518,48 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
     return nullptr;
 }
 
+// k_adj_interp on the plan's own interpolation table (uploaded by device_bank_ensure, as for the forward).
+template <typename Real>
+static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st)
+{
+    const int prec = sizeof(Real) == 4 ? 0 : 1;
+    AdjInterpArgs a{};
+    a.gy = j.in; a.gx = j.out; a.tab = p.dev[prec].interp_tab;
+    a.L = p.L; a.M = p.M; a.T = p.T; a.P = p.phases;
+    a.n_cols = (uint64_t)j.n_clips * j.n_channels; a.n_channels = j.n_channels;
+    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
+    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.n_y = j.in_frames; a.n_x = j.out_frames;
+    // positions are 64-bit products, as in the forward: (frame + T/2) L and k M
+    const __int128 lim = (__int128)1 << 62;
+    if ((__int128)(j.out_frames + p.T) * p.L >= lim || (__int128)j.in_frames * p.M >= lim) return "adjoint job: too long for one launch";
+    const int64_t gx = (j.out_frames + kAdjIW - 1) / kAdjIW;
+    if (gx > 2147483647LL) return "adjoint job: too long for one launch";
+    const dim3 grid((uint32_t)gx, (uint32_t)std::min<uint64_t>(a.n_cols, 65535));
+    const bool per_lane = switches().adj_interp_per_lane;
+    if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false>), grid, dim3(kAdjIW), 0, st, a);
+    else hipLaunchKernelGGL((k_adj_interp<Real, true>), grid, dim3(kAdjIW), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log)
+        if (FILE *f = fopen(switches().dbg_launch_log, "a")) {
+            fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u\n", sizeof(Real),
+                    (long long)p.L, (long long)p.M, p.T, p.phases, kAdjIW, kAdjIC, sizeof(AdjRec<Real>) * kAdjIC, per_lane ? "lane" : "union",
+                    grid.x, grid.y, grid.z, (unsigned)kAdjIW);
+            fclose(f);
+        }
+    return nullptr;
+}
+
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
+    const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT; // every constant-rate plan: k_adj_interp where there is no exact bank
     if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
-    if (p->phases) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
+    if (by_name && p->vr) return "adjoint job: variable-rate plans are not served (HIPSOXR_KERNEL_ADJOINT takes constant-rate plans)";
+    if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
     if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
     if (j.clip_table) return "adjoint job: ragged batches (clip_table) are not served";
-    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT)
+    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && !by_name)
         return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
     if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
     if ((uint64_t)j.in_frames > plan_out_len(*p, (uint64_t)j.out_frames))
@@ -431,6 +567,10 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
     if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
     if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
     if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
+        if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+        return j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, (hipStream_t)stream) : adj_interp_launch<double>(*p, j, (hipStream_t)stream);
+    }
     AdjBank *b = nullptr;
     if (const char *e = adj_ensure(p, &b)) return e;
     return j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, (hipStream_t)stream) : adj_launch<double>(*b, j, (hipStream_t)stream);

@@ -127,10 +127,11 @@ struct Switches {
     bool no_interp_pair = false;  // HIPSOXR_NO_INTERP_PAIR   k_interp_tile: one output per lane (A/B)
     bool dbg_interp_no_twin = false;     // HIPSOXR_DEBUG_INTERP_NO_TWIN      ... float pairs on ONE copy of the staged span (8-byte reads) always (A/B, tests)
     bool dbg_interp_pair_always = false; // HIPSOXR_DEBUG_INTERP_PAIR_ALWAYS  ... two per lane wherever a pair exists, whatever the cost model says (tests)
+    bool adj_interp_per_lane = false; // HIPSOXR_DEBUG_ADJ_INTERP_PER_LANE  k_adj_interp: every lane walks its own k range instead of the wave's union (A/B; same bits)
     bool poly_no_pair = false;    // HIPSOXR_POLY_NO_PAIR     interleaved channel pairs on k_poly (one channel per pass) instead of k_poly2 (A/B)
     int dbg_tile_form = 0;        // HIPSOXR_DEBUG_TILE_FORM  k_tile_mfma_p: force launch form 1..4 (slab 64 whole / 64 split / 32 whole / 32 split)
     const char *dbg_trace = nullptr; // HIPSOXR_DEBUG_TRACE   path for per-wave s_memtime stamps (k_tile_mfma_p; k_fft_pair2 with -DFFT2_TRACE)
-    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape; adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape
+    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape; adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape; adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape
 };
 const Switches &switches();
 
@@ -183,7 +184,8 @@ void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
 // transposed operator of the exact engine (adjoint.hip; hipsoxr_run_device_adjoint): job.in = gy (in_frames of it), job.out = gx
-// (out_frames of it); validates the job itself.  adjoint_release drops the plan's transposed tables (rebuilt on next use).
+// (out_frames of it); validates the job itself.  HIPSOXR_KERNEL_ADJOINT: interpolated-phase plans too (k_adj_interp on the
+// forward's own table, device_bank_ensure).  adjoint_release drops the plan's transposed tables (rebuilt on next use).
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &job, void *stream);
 void adjoint_release(const Plan *p);
 

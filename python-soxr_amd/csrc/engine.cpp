@@ -266,6 +266,7 @@ static const char *plan_acquire(double in_rate, double out_rate, unsigned long r
     hipsoxr_plan *h = new (std::nothrow) hipsoxr_plan();
     if (!h) return "out of memory";
     if (const char *e = plan_design(in_rate, out_rate, recipe, &h->p, vr)) { delete h; return e; }
+    h->p.vr = vr;
     std::lock_guard<std::mutex> lk(g_cache_mu);
     if ((*out = cache_find(in_rate, out_rate, recipe, vr, dev))) { delete h; return nullptr; }
     h->cached = true; h->key_in = in_rate; h->key_out = out_rate; h->key_recipe = recipe; h->key_vr = vr;
@@ -358,6 +359,7 @@ hipsoxr_error_t hipsoxr_plan_create_vr(double in_rate, double out_rate, unsigned
         delete h;
         return e;
     }
+    h->p.vr = true;
     *out = h;
     return nullptr;
 }
@@ -481,6 +483,8 @@ hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, 
 {
     if (!h || !job) return "null argument";
     if (job->elem < 0 || job->elem > 3) return "invalid element type";
+    if (job->kernel == HIPSOXR_KERNEL_ADJOINT)
+        return "HIPSOXR_KERNEL_ADJOINT selects the transposed operator: it is valid on hipsoxr_run_device_adjoint only (forward jobs have AUTO, EXACT and the engines' own names)";
     if (job->out_frames < 0 || job->in_frames < 0 || job->out_k0 < 0) return "invalid job extent";
     if ((job->out_frames > 0 && !job->out) || (job->out_frames > 0 && job->in_frames > 0 && !job->in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;

@@ -42,6 +42,7 @@ struct Plan {
     // phases == 0: exact rational bank [L][T].  phases == P > 0: interpolated-phase plan, bank holds
     // the cubic coefficient table [P][T][4] (see plan.cpp, "interpolated-phase plans").
     int32_t phases = 0;
+    bool vr = false; // designed for a variable-rate stream (hipsoxr_plan_create_vr, HIPSOXR_VR): positions are not tied to L / M
     std::vector<double> bank; // float64
     double proto_scale = 0; // interpolated-phase plans: DC normalisation of the continuous-time prototype (plan_proto)
     // A bank installed from outside (hipsoxr_plan_set_bank / hipsoxr_plan_broadcast) that DIFFERS from the designed one:

@@ -12,7 +12,7 @@ import numpy as np
 from . import _native as _n
 from . import _quality_to_enum
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
-                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM)
+                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT)
 
 
 class Plan:
@@ -77,7 +77,8 @@ class Plan:
                     stream=None, kernel=_n.KERNEL_AUTO, clip_table=None):
         """Raw launch of the transposed operator (hipsoxr_run_device_adjoint): gx = A^T gy for the forward job A that
         `run(..., kernel=KERNEL_EXACT)` computes — gy has gy_frames <= out_len(gx_frames) frames, gx has gx_frames.
-        Device pointers (ints), strides = (clip, frame, channel) in elements.  float32 / float64, exact-bank plans."""
+        Device pointers (ints), strides = (clip, frame, channel) in elements.  float32 / float64, exact-bank plans;
+        kernel=KERNEL_ADJOINT: every constant-rate plan, interpolated-phase plans included."""
         j = _n.Job()
         j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
         j.n_clips, j.n_channels = n_clips, n_channels
@@ -149,17 +150,17 @@ def _like_rank(t3, ndim):
     return t3[0, :, 0] if ndim == 1 else (t3[0] if ndim == 2 else t3)
 
 
-def _adjoint_refusal(plan, elem):
-    """The C entry's own refusal of (plan, element type) for an adjoint job, or None: asked with an empty job, so that a
-    forward that could not be differentiated fails when it is called, not in the middle of backward."""
+def _adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
+    """The C entry's own refusal of (plan, element type, selector) for an adjoint job, or None: asked with an empty job, so
+    that a forward that could not be differentiated fails when it is called, not in the middle of backward."""
     try:
-        plan.run_adjoint(None, None, elem, 0, 0, 0, 0, (0, 0, 0), (0, 0, 0))
+        plan.run_adjoint(None, None, elem, 0, 0, 0, 0, (0, 0, 0), (0, 0, 0), kernel=kernel)
     except RuntimeError as e:
         return str(e)
     return None
 
 
-def resample_tensor_adjoint(plan, gy, in_frames, out=None):
+def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO):
     """The transposed operator as a function: gx = A^T gy, where A is the resample of `in_frames` input frames that
     `resample_tensor(plan, x, kernel=KERNEL_EXACT)` computes (what its backward pass runs; the adjoint an iterative
     solver needs).  On the current torch stream, asynchronously.
@@ -168,19 +169,23 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None):
          most plan.out_len(in_frames) frames (a truncated forward output has a truncated cotangent).
     Returns a tensor of the same rank with in_frames frames (`out` may be supplied); every element is written.
     Gather form on the transposed bank, no atomics: bitwise reproducible, independent of layout.  Differentiable (its
-    backward is the forward on the exact engine).  Exact-bank plans only: interpolated-phase plans (and their two-stage
-    form), variable rate, streams, ragged batches, dist.py and integer types are not served."""
+    backward is the forward on the exact engine).  kernel=KERNEL_AUTO / KERNEL_EXACT: exact-bank plans only (an
+    interpolated-phase plan is refused by name).  kernel=KERNEL_ADJOINT: every constant-rate plan — on an exact-bank plan
+    the same launch and the same bits, on an interpolated-phase plan (`plan.phases != 0`: 48000 -> 44101, non-integral
+    rates) the gather-form adjoint on the plan's interpolation table, whose coefficients are the very bits the forward
+    with kernel=KERNEL_EXACT multiplies by.  There a non-finite gy[k] reaches exactly the frames of its true support.
+    The two-stage form's adjoint, variable rate, streams, ragged batches, dist.py and integer types are not served."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch
     if out is None and gy.requires_grad and torch.is_grad_enabled():
-        return _autograd_fns()[1].apply(gy, plan, int(in_frames))
+        return _autograd_fns()[1].apply(gy, plan, int(in_frames), kernel)
     if out is not None and gy.requires_grad and torch.is_grad_enabled():
         raise ValueError("out= cannot be combined with a tensor that requires grad")
-    return _adjoint_plain(plan, gy, int(in_frames), out)
+    return _adjoint_plain(plan, gy, int(in_frames), out, kernel)
 
 
-def _adjoint_plain(plan, gy, in_frames, out=None):
+def _adjoint_plain(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO):
     import torch
     elem = _torch_elem(gy.dtype)
     g3 = _as3(gy)
@@ -194,7 +199,7 @@ def _adjoint_plain(plan, gy, in_frames, out=None):
     stream = torch.cuda.current_stream(gy.device).cuda_stream
     # (an empty job still goes to the C entry: it is what refuses an integer type or an interpolated-phase plan)
     plan.run_adjoint(g3.data_ptr(), o3.data_ptr(), elem, clips, ch, n_y, in_frames, tuple(g3.stride()),
-                     tuple(o3.stride()), stream=stream)
+                     tuple(o3.stride()), stream=stream, kernel=kernel)
     return _like_rank(o3, gy.ndim)
 
 
@@ -212,30 +217,31 @@ def _autograd_fns():
 
     class ResampleFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, x, plan, kernel):
-            ctx.plan, ctx.frames = plan, _as3(x).shape[1]
+        def forward(ctx, x, plan, kernel, grad_kernel):
+            ctx.plan, ctx.frames, ctx.grad_kernel = plan, _as3(x).shape[1], grad_kernel
             return _resample_plain(plan, x.detach(), kernel=kernel)
 
         @staticmethod
         def backward(ctx, gy):
-            return resample_tensor_adjoint(ctx.plan, gy, ctx.frames), None, None
+            return resample_tensor_adjoint(ctx.plan, gy, ctx.frames, kernel=ctx.grad_kernel), None, None, None
 
     class AdjointFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, gy, plan, in_frames):
-            ctx.plan, ctx.n_y = plan, _as3(gy).shape[1]
-            return _adjoint_plain(plan, gy.detach(), in_frames)
+        def forward(ctx, gy, plan, in_frames, kernel):
+            ctx.plan, ctx.n_y, ctx.kernel = plan, _as3(gy).shape[1], kernel
+            return _adjoint_plain(plan, gy.detach(), in_frames, kernel=kernel)
 
         @staticmethod
-        def backward(ctx, ggx):
-            y = resample_tensor(ctx.plan, ggx, kernel=_n.KERNEL_EXACT)
-            return y.narrow(y.ndim - 2 if y.ndim > 1 else 0, 0, ctx.n_y), None, None
+        def backward(ctx, ggx):  # (the forward on the exact engine; its own gradient is this adjoint again, same selector)
+            y = resample_tensor(ctx.plan, ggx, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
+            return y.narrow(y.ndim - 2 if y.ndim > 1 else 0, 0, ctx.n_y), None, None, None
 
     _AUTOGRAD = (ResampleFn, AdjointFn)
     return _AUTOGRAD
 
 
-def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
+def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0,
+                    grad_kernel=_n.KERNEL_AUTO):
     """Resample a device tensor on the current torch stream, asynchronously.
 
     x : [frames] | [frames, channels] | [clips, frames, channels] torch tensor on a HIP device
@@ -252,16 +258,22 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     (interpolated-phase plans, integer tensors) raise when the forward is called.  The gradient is the EXACT engine's
     adjoint: where AUTO sends a large forward to the frequency-domain engine, forward and gradient agree in that engine's
     1e-6 class, not to rounding (kernel=KERNEL_EXACT: to rounding).  Without requires_grad nothing changes.
+
+    grad_kernel is the selector the backward's adjoint runs with.  The default refuses an interpolated-phase plan
+    (`plan.phases != 0`) as before; grad_kernel=KERNEL_ADJOINT admits it — the check is still made when the forward is
+    called — and the gradient is then the adjoint of the forward the exact engine computes on that plan.  Under
+    kernel=KERNEL_AUTO a float job of an interpolated-phase plan runs the two-stage form, so forward and gradient agree in
+    that form's class, 1e-6 (float32) / 2e-9 (float64); with kernel=KERNEL_EXACT they agree to rounding.
     """
     if x.is_cuda and x.requires_grad:
         import torch
         if torch.is_grad_enabled():
             if out is not None:
                 raise ValueError("out= cannot be combined with a tensor that requires grad")
-            why = _adjoint_refusal(plan, _torch_elem(x.dtype))
+            why = _adjoint_refusal(plan, _torch_elem(x.dtype), grad_kernel)
             if why:
                 raise RuntimeError(why)
-            return _autograd_fns()[0].apply(x, plan, kernel)
+            return _autograd_fns()[0].apply(x, plan, kernel, grad_kernel)
     return _resample_plain(plan, x, out, kernel, dither, clip_counter, dither_seed)
 
 

@@ -3,7 +3,9 @@
 equal multiply-add count: n_out * taps per column either way.
 
 Rows: 60 s mono 48k -> 44.1k VHQ float32; the same in float64; 128 clips x 10 s float32; 10 s x 8 channels interleaved
-44.1k -> 16k float32.  Per row the forward job (kernel=KERNEL_EXACT) and the adjoint job run on the same tensors (x -> y,
+44.1k -> 16k float32; then the interpolated-phase plans (kernel=KERNEL_ADJOINT, k_adj_interp): 60 s mono and stereo
+48000 -> 44101 VHQ and 10 s x 8 channels 44100 -> 16000.5 VHQ, each in float32 and float64, against the forward exact engine
+on the same plan and shape (k_interp_tile / k_interp_wave / k_interp).  Per row the forward job (kernel=KERNEL_EXACT) and the adjoint job run on the same tensors (x -> y,
 y -> gx): HIP-event time over blocks of launches, the two kinds alternated, median of the blocks; tensors are warmed first.
 Prints a markdown table (also to --out).  GPU only.
 
@@ -22,7 +24,13 @@ for p in (ROOT, os.path.join(ROOT, "python-soxr_amd")):
 ROWS = [("60 s mono 48k->44.1k VHQ f32", 48000, 44100, "VHQ", "float32", (60 * 48000,)),
         ("60 s mono 48k->44.1k VHQ f64", 48000, 44100, "VHQ", "float64", (60 * 48000,)),
         ("128 clips x 10 s 48k->44.1k VHQ f32", 48000, 44100, "VHQ", "float32", (128, 10 * 48000, 1)),
-        ("10 s x 8 ch interleaved 44.1k->16k VHQ f32", 44100, 16000, "VHQ", "float32", (10 * 44100, 8))]
+        ("10 s x 8 ch interleaved 44.1k->16k VHQ f32", 44100, 16000, "VHQ", "float32", (10 * 44100, 8)),
+        ("interp 60 s mono 48000->44101 VHQ f32", 48000, 44101, "VHQ", "float32", (60 * 48000,)),
+        ("interp 60 s mono 48000->44101 VHQ f64", 48000, 44101, "VHQ", "float64", (60 * 48000,)),
+        ("interp 60 s stereo 48000->44101 VHQ f32", 48000, 44101, "VHQ", "float32", (60 * 48000, 2)),
+        ("interp 60 s stereo 48000->44101 VHQ f64", 48000, 44101, "VHQ", "float64", (60 * 48000, 2)),
+        ("interp 10 s x 8 ch 44100->16000.5 VHQ f32", 44100, 16000.5, "VHQ", "float32", (10 * 44100, 8)),
+        ("interp 10 s x 8 ch 44100->16000.5 VHQ f64", 44100, 16000.5, "VHQ", "float64", (10 * 44100, 8))]
 
 
 def main():
@@ -55,7 +63,8 @@ def main():
         y = dev.resample_tensor(plan, x, kernel=dev.KERNEL_EXACT)
         gx = torch.empty_like(x)
         fwd = lambda: dev.resample_tensor(plan, x, out=y, kernel=dev.KERNEL_EXACT)
-        adj = lambda: dev.resample_tensor_adjoint(plan, y, frames, out=gx)
+        sel = dev.KERNEL_ADJOINT if plan.phases else dev.KERNEL_AUTO  # (interpolated-phase plans: by name)
+        adj = lambda: dev.resample_tensor_adjoint(plan, y, frames, out=gx, kernel=sel)
         for _ in range(3):
             fwd(), adj()
         torch.cuda.synchronize()
