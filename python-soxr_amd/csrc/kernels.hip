@@ -499,6 +499,15 @@ static TileGeom build_tile_tables(const Plan &p, std::vector<Real> *tab, int var
     return g;
 }
 
+// a host table into device memory of its own
+template <typename T>
+static const char *upload(void **dst, const std::vector<T> &v)
+{
+    HIP_TRY(hipMalloc(dst, v.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return nullptr;
+}
+
 template <typename Real>
 static const char *bank_upload(Plan *p, DeviceBank &d, TileGeom *geom_out, TileGeom *geom_m_out)
 {
@@ -507,48 +516,31 @@ static const char *bank_upload(Plan *p, DeviceBank &d, TileGeom *geom_out, TileG
     if (p->phases) { // interpolated-phase plan: the cubic table in the engine precision, nothing else
         std::vector<Real> tb(p->bank.size());
         for (size_t i = 0; i < tb.size(); ++i) tb[i] = (Real)p->bank[i];
-        HIP_TRY(hipMalloc(&d.interp_tab, tb.size() * sizeof(Real)));
-        HIP_TRY(hipMemcpy(d.interp_tab, tb.data(), tb.size() * sizeof(Real), hipMemcpyHostToDevice));
-        return nullptr;
+        return upload(&d.interp_tab, tb);
     }
     d.Lpad = (L + 15) / 16 * 16;
     std::vector<Real> tm((size_t)T * d.Lpad, (Real)0);
     for (int64_t ph = 0; ph < L; ++ph)
         for (int j = 0; j < T; ++j) tm[(size_t)j * d.Lpad + ph] = (Real)p->bank[(size_t)(ph * T + j)];
-    HIP_TRY(hipMalloc(&d.tap_major, tm.size() * sizeof(Real)));
-    HIP_TRY(hipMemcpy(d.tap_major, tm.data(), tm.size() * sizeof(Real), hipMemcpyHostToDevice));
+    if (const char *e = upload(&d.tap_major, tm)) return e;
 
     std::vector<Real> tab;
     TileGeom g = build_tile_tables<Real>(*p, &tab);
     if (g.ok) {
-        HIP_TRY(hipMalloc(&d.tile_tab, tab.size() * sizeof(Real)));
-        HIP_TRY(hipMemcpy(d.tile_tab, tab.data(), tab.size() * sizeof(Real), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void **)&d.tile_i0, g.e0.size() * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(d.tile_i0, g.e0.data(), g.e0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        if (const char *e = upload(&d.tile_tab, tab)) return e;
+        if (const char *e = upload((void **)&d.tile_i0, g.e0)) return e;
         d.RT = g.RT; d.n_rt = g.n_rt; d.I_h = g.I_h;
     }
     *geom_out = g;
-    if (sizeof(Real) == 8 && geom_m_out && !switches().no_mfma64) { // float64 engine on v_mfma_f64_16x16x4_f64 (k_tile_mfma<IO, double, NG>)
+    // the MFMA tiles — float32: k_tile_mfma_p where the period admits planes, else k_tile_mfma; the float64 engine on
+    // v_mfma_f64_16x16x4_f64: k_tile_mfma64_p, else k_tile_mfma<IO, double, NG>
+    if (geom_m_out && !(sizeof(Real) == 8 && switches().no_mfma64)) {
         std::vector<Real> tabm;
-        TileGeom gm = build_mfma_planes<Real>(*p, &tabm); // k_tile_mfma64_p where the period admits planes, else k_tile_mfma<IO, double, NG>
+        TileGeom gm = build_mfma_planes<Real>(*p, &tabm);
         if (!gm.ok || switches().no_planes) gm = build_tile_tables<Real>(*p, &tabm, 1);
         if (gm.ok) {
-            HIP_TRY(hipMalloc(&d.tile_tab_m, tabm.size() * sizeof(Real)));
-            HIP_TRY(hipMemcpy(d.tile_tab_m, tabm.data(), tabm.size() * sizeof(Real), hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc((void **)&d.tile_i0_m, gm.e0.size() * sizeof(int32_t)));
-            HIP_TRY(hipMemcpy(d.tile_i0_m, gm.e0.data(), gm.e0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
-        *geom_m_out = gm;
-    }
-    if (sizeof(Real) == 4 && geom_m_out) {
-        std::vector<float> tabm;
-        TileGeom gm = build_mfma_planes<float>(*p, &tabm);
-        if (!gm.ok || switches().no_planes) gm = build_tile_tables<float>(*p, &tabm, 1);
-        if (gm.ok) {
-            HIP_TRY(hipMalloc(&d.tile_tab_m, tabm.size() * sizeof(Real)));
-            HIP_TRY(hipMemcpy(d.tile_tab_m, tabm.data(), tabm.size() * sizeof(Real), hipMemcpyHostToDevice));
-            HIP_TRY(hipMalloc((void **)&d.tile_i0_m, gm.e0.size() * sizeof(int32_t)));
-            HIP_TRY(hipMemcpy(d.tile_i0_m, gm.e0.data(), gm.e0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            if (const char *e = upload(&d.tile_tab_m, tabm)) return e;
+            if (const char *e = upload((void **)&d.tile_i0_m, gm.e0)) return e;
         }
         *geom_m_out = gm;
     }
@@ -608,346 +600,388 @@ void device_bank_release(Plan *p)
 }
 
 // ---------------------------------------------------------------------------------------------
-// launch
+// launch: what the launchers share
 // ---------------------------------------------------------------------------------------------
+template <typename Real> static DeviceBank &bank_of(Plan *p) { return p->dev[sizeof(Real) == 4 ? 0 : 1]; }
+
+static inline int32_t log2_phases(int32_t P) { int32_t lg = 0; while ((1 << lg) < P) ++lg; return lg; }
+
+// Outputs [k0, k0 + nf) of job j, the first of them out_offset elements behind j.out.
+template <typename IO>
+static GatherArgs make_gather_args(const Plan &p, const DeviceBank &d, const hipsoxr_job_t &j, int64_t k0, int64_t nf, int64_t out_offset)
+{
+    GatherArgs a;
+    a.in = j.in;
+    a.out = (char *)j.out + (size_t)out_offset * sizeof(IO);
+    a.bank = d.tap_major; a.Lpad = d.Lpad; a.L = p.L; a.M = p.M; a.T = p.T;
+    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
+    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
+    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.in_abs0 = j.in_abs0; a.in_frames = j.in_frames;
+    a.out_k0 = k0; a.out_frames = nf;
+    __int128 kM = (__int128)k0 * p.M;
+    a.d0 = (int64_t)(kM / p.L); a.p0 = (int64_t)(kM % p.L);
+    a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
+    a.ch_fast = (j.n_channels > 1 && j.in_chan_stride == 1) ? 1 : 0;
+    return a;
+}
+
+static void set_interp_table(InterpArgs &x, const Plan &p, const DeviceBank &d) { x.tab = d.interp_tab; x.P = p.phases; x.lgP = log2_phases(p.phases); }
+
+// The exact bank phase-major ([L][T], DeviceBank::phase_major), uploaded on first use.
+template <typename Real>
+static const char *ensure_phase_major(Plan *p)
+{
+    DeviceBank &d = bank_of<Real>(p);
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (d.phase_major) return nullptr;
+    std::vector<Real> pm(p->bank.size());
+    for (size_t i = 0; i < pm.size(); ++i) pm[i] = (Real)p->bank[i];
+    if (hipMalloc(&d.phase_major, pm.size() * sizeof(Real)) != hipSuccess) return "hipMalloc failed";
+    if (hipMemcpy(d.phase_major, pm.data(), pm.size() * sizeof(Real), hipMemcpyHostToDevice) != hipSuccess) return "hipMemcpy failed";
+    return nullptr;
+}
+
+// Variable rate: the clock at a launch's first output — (T0, S0) advanced by the `done` outputs in front of it.
+static void vr_advance(const VrPos &vr, int64_t done, InterpArgs &x)
+{
+    typedef unsigned __int128 u128;
+    const u128 T0 = ((u128)vr.t_hi << 64) | vr.t_lo, S0 = ((u128)vr.s_hi << 64) | vr.s_lo, D = ((u128)vr.d_hi << 64) | vr.d_lo;
+    const u128 n = (u128)(uint64_t)done, m = n * (n - 1) / 2;
+    const u128 T1 = T0 + n * S0 + D * (done ? m : 0), S1 = S0 + D * n;
+    x.t_hi = (uint64_t)(T1 >> 64); x.t_lo = (uint64_t)T1;
+    x.s_hi = (uint64_t)(S1 >> 64); x.s_lo = (uint64_t)S1;
+    x.d_hi = vr.d_hi; x.d_lo = vr.d_lo;
+}
+// ... and the largest step (input samples per output) among the clock's first `upto` outputs
+static double vr_max_step(const VrPos &vr, int64_t upto)
+{
+    const double two64 = 18446744073709551616.;
+    const double s0 = (double)vr.s_hi + (double)vr.s_lo / two64;
+    const double dd = (double)(int64_t)vr.d_hi + (double)vr.d_lo / two64;
+    return std::max(s0, s0 + dd * (double)upto) * (1. + 1e-9);
+}
+
+// Geometry of k_chain / k_chain_multi for launches of at most n_out outputs per column: outputs per workgroup, LDS room for
+// the shared input span (samples), LDS bytes.
+struct ChainGeom { int NO; int32_t span_cap; size_t lds; bool ok; };
+template <typename Real>
+static ChainGeom chain_geom(const Plan &p, int64_t n_out)
+{
+    ChainGeom g;
+    // few outputs per workgroup: the staging loop is then two or three trips of 16 loads per
+    // thread (its latency is the kernel's latency), and there are enough workgroups anyway
+    // (above 512 outputs 32 per workgroup: at most 64 workgroups then read their span over PCIe, poll the mailbox
+    //  of the resident form, or report through completion words — 4410-frame chunks 25.3 -> 22.7 us per call)
+    g.NO = n_out <= 512 ? 8 : 32;
+    if (switches().dbg_chain_no) g.NO = switches().dbg_chain_no;
+    // LDS: NO coefficient rows of T + V words, the shared input span (T + what NO-1 window shifts of at
+    // most ceil(M/L) + 1 samples add; variable rate: the plan's ratio is the largest step), bookkeeping
+    const int64_t shift = (p.M + p.L - 1) / p.L + 2;
+    auto chain_lds = [&](int no) {
+        const int64_t sc = (int64_t)p.T + (int64_t)no * shift + 4;
+        g.span_cap = (int32_t)sc;
+        return (size_t)no * (p.T + 16 / sizeof(Real)) * sizeof(Real) + (size_t)((sc + 3) & ~3) * sizeof(Real) + (size_t)no * 16;
+    };
+    while (g.NO > 2 && chain_lds(g.NO) > 150 * 1024) g.NO /= 2;
+    g.lds = chain_lds(g.NO);
+    g.ok = g.lds <= 150 * 1024 && shift < (1 << 20);
+    return g;
+}
+
+// Geometry of the half-chain-per-quad kernels (k_gather_wave, k_interp_wave): a workgroup's 32 consecutive outputs reach over
+// T inputs plus `reach`, what the 31 window shifts between them add.
+struct WaveGeom { int64_t span = 0; size_t lds = 0; bool ok = false; };
+template <typename Real>
+static WaveGeom wave_geom(int64_t reach, int32_t T)
+{
+    WaveGeom g;
+    g.span = (reach + T + 4 + 3) & ~(int64_t)3;
+    g.lds = (size_t)(g.span + 32) * sizeof(Real);
+    g.ok = g.lds <= 64 * 1024;
+    return g;
+}
+
+// Completion words (ChainDone): a launch that is the whole job, of at most cd->cap workgroups, takes them.
+static inline void claim_done_words(ChainDone *cd, bool whole_job, uint64_t wgs, uint32_t **words, uint32_t *seq)
+{
+    if (!cd || !whole_job || wgs > cd->cap) return;
+    *words = cd->words; *seq = cd->seq;
+    cd->n_wgs = (uint32_t)wgs;
+}
+
+// One launch's share of a job, as launch_gather hands it to the launcher of the form it chose.
+struct GatherLaunch {
+    const hipsoxr_job_t &j;
+    hipStream_t st;
+    const VrPos *vr;  // variable rate: the clock at the JOB's first output
+    ChainDone *cd;    // completion words on offer, or nullptr
+    int64_t done, nf; // outputs [done, done + nf) of the job
+    uint64_t cols;    // (clip, channel) columns
+    GatherArgs a;
+    bool whole_job() const { return done == 0 && nf == j.out_frames; }
+    // per_wg outputs of one column per workgroup
+    dim3 grid(int per_wg) const { return dim3((unsigned)((nf + per_wg - 1) / per_wg), (unsigned)cols, 1); }
+};
+
+// ---- launch: one function per kernel form ----
+template <typename IO, typename Real>
+static const char *launch_gather_wave(Plan *p, const GatherLaunch &c, const WaveGeom &g)
+{
+    if (const char *e = ensure_phase_major<Real>(p)) return e;
+    GatherWaveArgs ga;
+    ga.g = c.a; ga.phase_major = bank_of<Real>(p).phase_major; ga.span_cap = (int32_t)g.span; ga.done_words = nullptr; ga.done_seq = 0;
+    const dim3 grid = c.grid(32);
+    claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ga.done_words, &ga.done_seq);
+    hipLaunchKernelGGL((k_gather_wave<IO, Real>), grid, dim3(256), g.lds, c.st, ga);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// the resident form of k_chain: same staging, same chains, fed by messages (k_chain_resident)
+template <typename IO, typename Real>
+static const char *launch_chain_resident(Plan *p, const GatherLaunch &c, const ChainGeom &g, const ChainArgs &ca, ResidentLaunch *res)
+{
+    if (p->L >= (1 << 24) && !c.vr) return "resident kernel: ratio numerator too large";
+    void (*rk)(ResidentArgs) = c.vr ? k_chain_resident<IO, Real, 2> : p->phases ? k_chain_resident<IO, Real, 1> : k_chain_resident<IO, Real, 0>;
+    const dim3 grid = c.grid(g.NO);
+    const int64_t wgs = (int64_t)grid.x * grid.y;
+    // every workgroup must be on the chip at once (they wait for each other): a quarter of the slots at most
+    int occ = 0, dev = 0, cus = 0;
+    if (const char *e = ensure_dyn_lds((const void *)rk, g.lds)) return e;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)rk, 256, g.lds));
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    if (occ < 1 || wgs > (int64_t)occ * cus / 4 || wgs > (int64_t)kResidentMaxWgs) return "resident kernel: message too large";
+    // process-wide budget in CU capacity (engine.cpp): all resident instances together hold at most half the chip
+    res->cost_mcu = (uint32_t)((wgs * 1024 + occ - 1) / occ);
+    if (res->used_mcu + (int64_t)res->cost_mcu > ((int64_t)cus * 1024) >> res->budget_shift) { res->over_budget = true; return "resident kernel: over the budget"; }
+    ResidentArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.ca = ca; ra.box = res->box; ra.words = res->words; ra.ctl = res->ctl; ra.base_seq = res->base_seq; ra.epoch = res->epoch;
+    ra.idle_ticks = res->idle_us * 100; // wall_clock64: 100 MHz
+    ra.n_wgs = (uint32_t)wgs;
+    res->n_wgs = ra.n_wgs; res->max_out = (int64_t)grid.x * g.NO;
+    hipLaunchKernelGGL(rk, grid, dim3(256), g.lds, c.st, ra);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// k_chain — exact, interpolated and variable-rate plans; res: as the resident kernel instead
+template <typename IO, typename Real>
+static const char *launch_chain(Plan *p, const GatherLaunch &c, const ChainGeom &g, ResidentLaunch *res)
+{
+    ChainArgs ca;
+    std::memset(&ca, 0, sizeof ca);
+    ca.ia.g = c.a; ca.NO = g.NO; ca.span_cap = g.span_cap;
+    void (*ck)(ChainArgs) = nullptr;
+    if (p->phases) {
+        set_interp_table(ca.ia, *p, bank_of<Real>(p));
+        if (c.vr && (1 << ca.ia.lgP) != ca.ia.P) return "variable-rate needs a power-of-two phase count";
+        if (c.vr) vr_advance(*c.vr, c.done, ca.ia);
+        ck = c.vr ? k_chain<IO, Real, 2> : k_chain<IO, Real, 1>;
+    } else {
+        if (const char *e = ensure_phase_major<Real>(p)) return e;
+        ca.phase_major = bank_of<Real>(p).phase_major;
+        ck = k_chain<IO, Real, 0>;
+    }
+    if (res) return launch_chain_resident<IO, Real>(p, c, g, ca, res);
+    if (const char *e = ensure_dyn_lds((const void *)ck, g.lds)) return e;
+    const dim3 grid = c.grid(g.NO);
+    claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ca.done_words, &ca.done_seq);
+    hipLaunchKernelGGL(ck, grid, dim3(256), g.lds, c.st, ca);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// a half-chain per quad of lanes (k_interp_wave)
+template <typename IO, typename Real>
+static const char *launch_interp_wave(const GatherLaunch &c, const InterpArgs &ia, const WaveGeom &g)
+{
+    InterpWaveArgs wa;
+    wa.ia = ia; wa.span_cap = (int32_t)g.span; wa.done_words = nullptr; wa.done_seq = 0;
+    const dim3 grid = c.grid(32);
+    claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &wa.done_words, &wa.done_seq);
+    void (*wk)(InterpWaveArgs) = c.vr ? k_interp_wave<IO, Real, true> : k_interp_wave<IO, Real, false>;
+    hipLaunchKernelGGL(wk, grid, dim3(256), g.lds, c.st, wa);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// k_interp_tile, the throughput kernel for large interpolated launches: KO outputs per workgroup, as many as LDS allows
+// (input span + 2 bytes of bookkeeping per output), at least ~32 outputs per interval.  KO == 0: not this kernel.
+struct InterpTileForm {
+    int64_t KO = 0, span_cap = 0;
+    int pair_mode = 0;           // 0 one output per lane, 1 channel pairs, 2 the column's two halves
+    bool twin = false;           // ... pairs with the span staged twice (float: 16-byte aligned reads)
+    int64_t split_h = 0, nf_t = 0; // (outputs the tiles are counted over: member 1's)
+};
+// The form for nf outputs per column at `step` input samples per output, against the lane-per-output kernels' cost
+// (wave_ok: k_interp_wave is the alternative, else k_interp).
+template <typename Real>
+static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, int64_t nf, double step, bool vr, bool wave_ok)
+{
+    InterpTileForm f;
+    f.nf_t = nf;
+    // a bucket (outputs of one interval) is served 64 at a time: aim at a mean of 60 per
+    // interval (30, 15 when LDS cannot hold that many outputs and their input span)
+    // (round 3: among the sizes that fit, the one that leaves the fewest workgroup-layers x outputs per
+    //  workgroup on the 256 CUs — 48000 -> 44101 stereo 60 s: 60 per interval are 346 workgroups, two layers
+    //  of which the second is a third full; 41 per interval are 506)
+    // two outputs per lane (InterpTileArgs): neighbouring channels of an even channel count, else — constant rate —
+    // the column's own second half, split h periods of L outputs in when that half has >= 0.7 of the first's outputs
+    // — taken when the launch's workgroup layers x outputs per workgroup come out cheaper than with one output
+    // per lane (a pair workgroup takes ~1.7x a single one: 60 s stereo 393 -> 348 us, 8 channels 1622 -> 1120,
+    // mono 232 -> 190; a 10 s stereo job has too few workgroups to halve them)
+    constexpr double kPairWg = 1.7, kTwinWg = 1.4; // (... 1.4 with the span staged twice for 16-byte reads: stereo 348 -> 296, mono 190 -> 145)
+    int cand_mode = 0;
+    int64_t cand_h = 0, cand_nf = nf;
+    if (!switches().no_interp_pair) {
+        if (j.n_channels % 2 == 0) cand_mode = 1;
+        else if (!vr) {
+            const int64_t h = (nf + 2 * p.L - 1) / (2 * p.L), n1 = h * p.L;
+            if (h >= 1 && n1 < nf && 10 * (nf - n1) >= 7 * n1 && h * p.M < ((int64_t)1 << 40)) { cand_mode = 2; cand_h = h; cand_nf = n1; }
+        }
+    }
+    double best_cost = 1e300, cols_ = (double)j.n_clips * j.n_channels;
+    for (int mode : {0, cand_mode}) {
+        if (mode == 0 && cand_mode && switches().dbg_interp_pair_always) continue;
+        const int nm = mode ? 2 : 1;
+        const int64_t nft = mode == 2 ? cand_nf : nf;
+        const double cols_m = (double)j.n_clips * j.n_channels / (mode == 1 ? 2 : 1);
+        for (int tw = 0; tw <= (mode && sizeof(Real) == 4 && !switches().dbg_interp_no_twin ? 1 : 0); ++tw) // float pairs: one or two copies of the span
+            for (int per = 64; per >= 15; --per) {
+                const int64_t k = (int64_t)per * p.phases;
+                if (k > 16384 || k > nft) continue;
+                const int64_t sc = (int64_t)std::ceil((double)k * step) + p.T + 8;
+                const int64_t bytes = (tw ? 2 * (sc + 4) : sc) * nm * (int64_t)sizeof(Real) + k * 2 + (2 * p.phases + 2) * 4 + 64;
+                if (bytes > 150 * 1024) continue;
+                const double wgs_ = std::ceil((double)nft / (double)k) * cols_m;
+                const double cost = std::ceil(wgs_ / 256.) * (double)k * (per >= 30 ? 1. : 30. / per) * (tw ? kTwinWg : mode ? kPairWg : 1.); // (thin buckets: idle lanes)
+                if (cost < best_cost) { best_cost = cost; f.KO = k; f.span_cap = sc; f.pair_mode = mode; f.twin = tw != 0; f.split_h = mode == 2 ? cand_h : 0; f.nf_t = nft; cols_ = cols_m; }
+            }
+        if (!cand_mode) break;
+    }
+    // ... which pays off once the launch fills the chip.  A workgroup of it is long (KO outputs x T taps one
+    // interval at a time: ~130 us at VHQ, 1.5 ms with the variable-rate clock), so a launch of a few of them
+    // loses to lane-per-output k_interp, whose time grows with the work instead (measured, us per output x tap:
+    // k_interp 2.5e-6; a k_interp_tile workgroup 6.3e-5 constant rate, 2.9e-4 variable rate; 256 CUs):
+    // 96 000-frame variable-rate chunk 1.5 ms -> 0.1 ms on k_interp; 10 s stereo constant rate 134 us on
+    // the tile kernel (503 on k_interp); 1 s stereo 75 us on k_interp (127 on the tile kernel).
+    constexpr double kWaveUsPerTap = 1.0e-6; // k_interp_wave: us per output x tap, 256 CUs
+    if (f.KO) {
+        const double wgs = (double)((f.nf_t + f.KO - 1) / f.KO) * cols_;
+        const double t_tile = std::ceil(wgs / 256.) * (double)f.KO * p.T * (vr ? 2.9e-4 : 6.3e-5) * (f.twin ? kTwinWg : f.pair_mode ? kPairWg : 1.);
+        const double t_lane = (wave_ok ? kWaveUsPerTap : 2.5e-6) * (double)nf * ((double)j.n_clips * j.n_channels) * p.T;
+        if (t_lane < t_tile) f.KO = 0;
+    }
+    return f;
+}
+
+template <typename IO, typename Real>
+static const char *launch_interp_tile(const Plan &p, const GatherLaunch &c, const InterpArgs &ia, const InterpTileForm &f)
+{
+    const hipsoxr_job_t &j = c.j;
+    InterpTileArgs ta;
+    ta.ia = ia; ta.KO = (int32_t)f.KO; ta.span_cap = (int32_t)((f.span_cap + 1) / 2 * 2);
+    ta.cols_per_clip = f.pair_mode == 1 ? j.n_channels / 2 : j.n_channels; ta.ch_step = f.pair_mode == 1 ? 2 : 1;
+    ta.m2_in = ta.m2_out = ta.m2_l = ta.m2_k = 0; ta.m2_n = c.nf; ta.m2_dch = 0;
+    if (f.pair_mode == 1) { ta.m2_in = j.in_chan_stride; ta.m2_out = j.out_chan_stride; ta.m2_dch = 1; }
+    if (f.pair_mode == 2) {
+        ta.m2_l = f.split_h * p.M; ta.m2_k = f.split_h * p.L; ta.m2_in = ta.m2_l * j.in_frame_stride; ta.m2_out = ta.m2_k * j.out_frame_stride;
+        ta.m2_n = c.nf - f.nf_t; ta.ia.g.out_frames = f.nf_t;
+    }
+    const size_t lds = (size_t)(f.twin ? 2 * (ta.span_cap + 2) : ta.span_cap) * (f.pair_mode ? 2 : 1) * sizeof(Real) + (size_t)f.KO * 2 + (size_t)(2 * p.phases + 2) * 4 + 64;
+    const dim3 tgrid((unsigned)((f.nf_t + f.KO - 1) / f.KO), (unsigned)((uint64_t)j.n_clips * ta.cols_per_clip), 1);
+    void (*tk)(InterpTileArgs) = f.pair_mode ? (c.vr ? k_interp_tile<IO, Real, true, true> : k_interp_tile<IO, Real, false, true>)
+                                             : (c.vr ? k_interp_tile<IO, Real, true, false> : k_interp_tile<IO, Real, false, false>);
+    if constexpr (sizeof(Real) == 4)
+        if (f.twin) tk = c.vr ? k_interp_tile<IO, Real, true, true, true> : k_interp_tile<IO, Real, false, true, true>;
+    if (const char *e = ensure_dyn_lds((const void *)tk, lds)) return e;
+    hipLaunchKernelGGL(tk, tgrid, dim3(1024), lds, c.st, ta);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// one lane per output: k_interp (ia: interpolated-phase plans and variable rate), else k_gather — every ratio, layout and length
+template <typename IO, typename Real>
+static const char *launch_lane(const GatherLaunch &c, const InterpArgs *ia)
+{
+    const dim3 block(256), grid = c.a.ch_fast ? dim3((unsigned)((c.nf * (int64_t)c.j.n_channels + 255) / 256), c.j.n_clips, 1) : c.grid(256);
+    if (ia && c.vr) hipLaunchKernelGGL((k_interp<IO, Real, true>), grid, block, 0, c.st, *ia);
+    else if (ia) hipLaunchKernelGGL((k_interp<IO, Real, false>), grid, block, 0, c.st, *ia);
+    else hipLaunchKernelGGL((k_gather<IO, Real>), grid, block, 0, c.st, c.a);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+
+// ---- launch: the dispatcher of everything but the period tiles.  Decision order, per launch of at most 2^30 outputs:
+//   k_gather_wave -> k_chain (res: k_chain_resident) -> interpolated plans: k_interp_wave / k_interp_tile / k_interp -> k_gather
 template <typename IO, typename Real>
 static const char *launch_gather(Plan *p, const hipsoxr_job_t &j, hipStream_t st, const VrPos *vr = nullptr, ResidentLaunch *res = nullptr,
                                  ChainDone *cd = nullptr)
 {
     if (cd) cd->n_wgs = 0;
-    const DeviceBank &d = p->dev[sizeof(Real) == 4 ? 0 : 1];
+    const DeviceBank &d = bank_of<Real>(p);
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    const bool cols_fit = cols <= 65535; // (every kernel but the lane-per-output ones on channel-fast data has the columns in grid.y)
     // split so that idx*M stays far below 2^63 and grid.x below 2^31
     const int64_t max_chunk = (int64_t)1 << 30;
     for (int64_t done = 0; done < j.out_frames; done += max_chunk) {
-        GatherArgs a;
-        const int64_t k0 = j.out_k0 + done;
         const int64_t nf = std::min<int64_t>(max_chunk, j.out_frames - done);
-        a.in = j.in;
-        a.out = (char *)j.out + (size_t)(done * j.out_frame_stride) * sizeof(IO);
-        a.bank = d.tap_major; a.Lpad = d.Lpad; a.L = p->L; a.M = p->M; a.T = p->T;
-        a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-        a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
-        a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-        a.in_abs0 = j.in_abs0; a.in_frames = j.in_frames;
-        a.out_k0 = k0; a.out_frames = nf;
-        __int128 kM = (__int128)k0 * p->M;
-        a.d0 = (int64_t)(kM / p->L); a.p0 = (int64_t)(kM % p->L);
-        a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
-        a.ch_fast = (j.n_channels > 1 && j.in_chan_stride == 1) ? 1 : 0;
-        dim3 grid, block(256);
-        if (a.ch_fast) {
-            int64_t e = nf * (int64_t)j.n_channels;
-            grid = dim3((unsigned)((e + 255) / 256), j.n_clips, 1);
-            if (j.n_clips > 65535) return "too many clips for one launch (max 65535)";
-        } else {
-            uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-            if (cols > 65535) {
-                // fold: launch per clip group
-                return "too many (clip, channel) columns for one launch (max 65535)";
-            }
-            grid = dim3((unsigned)((nf + 255) / 256), (unsigned)cols, 1);
-        }
-        // k_interp_wave (in place of lane-per-output k_interp): needs a (clip, channel) grid dimension and LDS for the
-        // span of 32 consecutive outputs at the launch's largest step
-        constexpr double kWaveUsPerTap = 1.0e-6; // us per output x tap, 256 CUs
-        bool wave_ok = false;
-        int64_t wave_span = 0;
-        size_t wave_lds = 0;
-        if (p->phases && !switches().no_interp_wave && (uint64_t)j.n_clips * j.n_channels <= 65535) {
-            double step = (double)p->M / (double)p->L;
-            if (vr) {
-                const double two64 = 18446744073709551616.;
-                const double s0 = (double)vr->s_hi + (double)vr->s_lo / two64;
-                const double dd = (double)(int64_t)vr->d_hi + (double)vr->d_lo / two64;
-                step = std::max(s0, s0 + dd * (double)(done + nf)) * (1. + 1e-9);
-            }
-            if (step < 1e6) {
-                wave_span = ((int64_t)std::ceil(31. * step) + p->T + 4 + 3) & ~(int64_t)3;
-                wave_lds = (size_t)(wave_span + 32) * sizeof(Real);
-                wave_ok = wave_lds <= 64 * 1024;
-            }
-        }
+        const GatherLaunch c{j, st, vr, cd, done, nf, cols, make_gather_args<IO>(*p, d, j, j.out_k0 + done, nf, done * j.out_frame_stride)};
+        if (c.a.ch_fast && j.n_clips > 65535) return "too many clips for one launch (max 65535)";
+        if (!c.a.ch_fast && !cols_fit) return "too many (clip, channel) columns for one launch (max 65535)";
+        const char *err = nullptr;
+
         // exact-bank launches of 4096 outputs and more that come here (launch_typed: periods too few for a slab, or a
         // stream chunk whose result goes straight to host memory): k_gather_wave instead of lane-per-output k_gather
-        if (!p->phases && !res && !vr && !switches().no_gather_wave && nf >= 4096 && p->T >= 32 && (uint64_t)j.n_clips * j.n_channels <= 65535) {
-            const int64_t gspan = ((int64_t)(31 * ((p->M + p->L - 1) / p->L + 1)) + p->T + 4 + 3) & ~(int64_t)3; // 31 window shifts of at most ceil(M/L) + T
-            const size_t glds = (size_t)(gspan + 32) * sizeof(Real);
-            if (glds <= 64 * 1024) {
-                DeviceBank &dm = p->dev[sizeof(Real) == 4 ? 0 : 1];
-                const char *err = nullptr;
-                {
-                    std::lock_guard<std::mutex> lk(p->mu);
-                    if (!dm.phase_major) {
-                        std::vector<Real> pm(p->bank.size());
-                        for (size_t i = 0; i < pm.size(); ++i) pm[i] = (Real)p->bank[i];
-                        if (hipMalloc(&dm.phase_major, pm.size() * sizeof(Real)) != hipSuccess) err = "hipMalloc failed";
-                        else if (hipMemcpy(dm.phase_major, pm.data(), pm.size() * sizeof(Real), hipMemcpyHostToDevice) != hipSuccess)
-                            err = "hipMemcpy failed";
-                    }
-                }
-                if (err) return err;
-                GatherWaveArgs ga;
-                ga.g = a; ga.phase_major = dm.phase_major; ga.span_cap = (int32_t)gspan; ga.done_words = nullptr; ga.done_seq = 0;
-                const uint64_t wgs = (uint64_t)((nf + 31) / 32) * ((uint64_t)j.n_clips * j.n_channels);
-                if (cd && done == 0 && nf == j.out_frames && wgs <= cd->cap) { // the whole job is this launch
-                    ga.done_words = cd->words; ga.done_seq = cd->seq;
-                    cd->n_wgs = (uint32_t)wgs;
-                }
-                hipLaunchKernelGGL((k_gather_wave<IO, Real>), dim3((unsigned)((nf + 31) / 32), (unsigned)((uint64_t)j.n_clips * j.n_channels), 1),
-                                   dim3(256), glds, st, ga);
-                HIP_TRY(hipGetLastError());
+        if (!p->phases && !res && !vr && !switches().no_gather_wave && nf >= 4096 && p->T >= 32 && cols_fit) {
+            const WaveGeom gw = wave_geom<Real>(31 * ((p->M + p->L - 1) / p->L + 1), p->T); // 31 window shifts of at most ceil(M/L) + T
+            if (gw.ok) {
+                if ((err = launch_gather_wave<IO, Real>(p, c, gw))) return err;
                 continue;
             }
         }
+
+        // interpolated plans: the launch's largest step, and whether k_interp_wave can take it (in place of lane-per-output
+        // k_interp): it needs a (clip, channel) grid dimension and LDS for the span of 32 consecutive outputs at that step
+        double step = 0;
+        WaveGeom iw;
+        if (p->phases) {
+            step = vr ? vr_max_step(*vr, done + nf) : (double)p->M / (double)p->L; // input samples per output
+            if (!switches().no_interp_wave && cols_fit && step < 1e6) iw = wave_geom<Real>((int64_t)std::ceil(31. * step), p->T);
+        }
+
         // small launches (streaming chunks): the low-latency chain kernel (interpolated plans above 512 outputs: k_interp_wave —
         // 4410-frame variable-rate calls 29.0 -> 27.0 us; 441-frame calls are 2.5 us faster here: 20 short workgroups against 5)
-        const bool no_chain = switches().no_chain;
-        if (!no_chain && nf < 4096 && (uint64_t)j.n_clips * j.n_channels <= 65535 && !(wave_ok && !res && nf > 512)) {
-            // few outputs per workgroup: the staging loop is then two or three trips of 16 loads per
-            // thread (its latency is the kernel's latency), and there are enough workgroups anyway
-            // (above 512 outputs 32 per workgroup: at most 64 workgroups then read their span over PCIe, poll the mailbox
-            //  of the resident form, or report through completion words — 4410-frame chunks 25.3 -> 22.7 us per call)
-            int NO = nf <= 512 ? 8 : 32;
-            if (switches().dbg_chain_no) NO = switches().dbg_chain_no;
-            // LDS: NO coefficient rows of T + V words, the shared input span (T + what NO-1 window shifts of at
-            // most ceil(M/L) + 1 samples add; variable rate: the plan's ratio is the largest step), bookkeeping
-            const int64_t shift = (p->M + p->L - 1) / p->L + 2;
-            auto chain_lds = [&](int no, int32_t *span_cap) {
-                const int64_t sc = (int64_t)p->T + (int64_t)no * shift + 4;
-                *span_cap = (int32_t)sc;
-                return (size_t)no * (p->T + 16 / sizeof(Real)) * sizeof(Real) + (size_t)((sc + 3) & ~3) * sizeof(Real) + (size_t)no * 16;
-            };
-            int32_t span_cap = 0;
-            while (NO > 2 && chain_lds(NO, &span_cap) > 150 * 1024) NO /= 2;
-            const size_t lds = chain_lds(NO, &span_cap);
-            if (lds <= 150 * 1024 && shift < (1 << 20)) {
-                ChainArgs ca;
-                std::memset(&ca, 0, sizeof ca);
-                ca.ia.g = a; ca.NO = NO; ca.span_cap = span_cap;
-                const char *err = nullptr;
-                void (*ck)(ChainArgs) = nullptr;
-                if (p->phases) {
-                    ca.ia.tab = d.interp_tab; ca.ia.P = p->phases;
-                    while ((1 << ca.ia.lgP) < ca.ia.P) ++ca.ia.lgP;
-                    if (vr) {
-                        if ((1 << ca.ia.lgP) != ca.ia.P) return "variable-rate needs a power-of-two phase count";
-                        typedef unsigned __int128 u128;
-                        const u128 T0 = ((u128)vr->t_hi << 64) | vr->t_lo, S0 = ((u128)vr->s_hi << 64) | vr->s_lo,
-                                   D = ((u128)vr->d_hi << 64) | vr->d_lo;
-                        const u128 n = (u128)(uint64_t)done, m = n * (n - 1) / 2;
-                        const u128 T1 = T0 + n * S0 + D * (done ? m : 0), S1 = S0 + D * n;
-                        ca.ia.t_hi = (uint64_t)(T1 >> 64); ca.ia.t_lo = (uint64_t)T1;
-                        ca.ia.s_hi = (uint64_t)(S1 >> 64); ca.ia.s_lo = (uint64_t)S1;
-                        ca.ia.d_hi = vr->d_hi; ca.ia.d_lo = vr->d_lo;
-                        ck = k_chain<IO, Real, 2>;
-                    } else {
-                        ck = k_chain<IO, Real, 1>;
-                    }
-                } else {
-                    DeviceBank &dm = p->dev[sizeof(Real) == 4 ? 0 : 1];
-                    {
-                        std::lock_guard<std::mutex> lk(p->mu);
-                        if (!dm.phase_major) {
-                            std::vector<Real> pm(p->bank.size());
-                            for (size_t i = 0; i < pm.size(); ++i) pm[i] = (Real)p->bank[i];
-                            if (hipMalloc(&dm.phase_major, pm.size() * sizeof(Real)) != hipSuccess) err = "hipMalloc failed";
-                            else if (hipMemcpy(dm.phase_major, pm.data(), pm.size() * sizeof(Real), hipMemcpyHostToDevice) != hipSuccess)
-                                err = "hipMemcpy failed";
-                        }
-                    }
-                    if (err) return err;
-                    ca.phase_major = dm.phase_major;
-                    ck = k_chain<IO, Real, 0>;
-                }
-                if (res) { // the resident form: same staging, same chains, fed by messages (k_chain_resident)
-                    if (p->L >= (1 << 24) && !vr) return "resident kernel: ratio numerator too large";
-                    void (*rk)(ResidentArgs) = vr ? k_chain_resident<IO, Real, 2> : p->phases ? k_chain_resident<IO, Real, 1> : k_chain_resident<IO, Real, 0>;
-                    const unsigned gx = (unsigned)((nf + NO - 1) / NO), gy = (unsigned)((uint64_t)j.n_clips * j.n_channels);
-                    // every workgroup must be on the chip at once (they wait for each other): a quarter of the slots at most
-                    int occ = 0, dev = 0, cus = 0;
-                    if (const char *e = ensure_dyn_lds((const void *)rk, lds)) return e;
-                    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)rk, 256, lds));
-                    HIP_TRY(hipGetDevice(&dev));
-                    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-                    if (occ < 1 || (int64_t)gx * gy > (int64_t)occ * cus / 4 || (int64_t)gx * gy > (int64_t)kResidentMaxWgs) return "resident kernel: message too large";
-                    // process-wide budget in CU capacity (engine.cpp): all resident instances together hold at most half the chip
-                    res->cost_mcu = (uint32_t)(((int64_t)gx * gy * 1024 + occ - 1) / occ);
-                    if (res->used_mcu + (int64_t)res->cost_mcu > ((int64_t)cus * 1024) >> res->budget_shift) { res->over_budget = true; return "resident kernel: over the budget"; }
-                    ResidentArgs ra;
-                    std::memset(&ra, 0, sizeof ra);
-                    ra.ca = ca; ra.box = res->box; ra.words = res->words; ra.ctl = res->ctl; ra.base_seq = res->base_seq; ra.epoch = res->epoch;
-                    ra.idle_ticks = res->idle_us * 100; // wall_clock64: 100 MHz
-                    ra.n_wgs = gx * gy;
-                    res->n_wgs = ra.n_wgs; res->max_out = (int64_t)gx * NO;
-                    hipLaunchKernelGGL(rk, dim3(gx, gy, 1), dim3(256), lds, st, ra);
-                    HIP_TRY(hipGetLastError());
-                    return nullptr;
-                }
-                if (const char *e = ensure_dyn_lds((const void *)ck, lds)) return e;
-                {
-                    const uint64_t wgs = (uint64_t)((nf + NO - 1) / NO) * ((uint64_t)j.n_clips * j.n_channels);
-                    if (cd && done == 0 && nf == j.out_frames && wgs <= cd->cap) { // the whole job is this launch
-                        ca.done_words = cd->words; ca.done_seq = cd->seq;
-                        cd->n_wgs = (uint32_t)wgs;
-                    }
-                }
-                hipLaunchKernelGGL(ck, dim3((unsigned)((nf + NO - 1) / NO), (unsigned)((uint64_t)j.n_clips * j.n_channels), 1),
-                                   dim3(256), lds, st, ca);
-                HIP_TRY(hipGetLastError());
-                continue;
+        if (!switches().no_chain && nf < 4096 && cols_fit && !(iw.ok && !res && nf > 512)) {
+            const ChainGeom cg = chain_geom<Real>(*p, nf);
+            if (cg.ok) {
+                if ((err = launch_chain<IO, Real>(p, c, cg, res))) return err;
+                continue; // (the resident kernel is up: a launch this small is the job's only one)
             }
         }
         if (res) return "resident kernel: unavailable for this job";
+
         if (p->phases) {
             InterpArgs ia;
             std::memset(&ia, 0, sizeof ia);
-            ia.g = a; ia.tab = d.interp_tab; ia.P = p->phases;
-            while ((1 << ia.lgP) < ia.P) ++ia.lgP;
-            // throughput kernel for large launches: KO outputs per workgroup, as many as LDS allows
-            // (input span + 2 bytes of bookkeeping per output), at least ~32 outputs per interval
-            const bool no_itile = switches().no_interp_tile;
-            int64_t KO = 0, span_cap = 0;
-            int pair_mode = 0;          // k_interp_tile: 0 one output per lane, 1 channel pairs, 2 the column's two halves
-            bool twin = false;          // ... pairs with the span staged twice (float: 16-byte aligned reads)
-            int64_t split_h = 0, nf_t = nf; // (outputs the tiles are counted over: member 1's)
-            // position of this launch's first output on the variable-rate clock: (T0, S0) advanced by `done` outputs
-            auto vr_advance = [&](InterpArgs &x) {
-                typedef unsigned __int128 u128;
-                const u128 T0 = ((u128)vr->t_hi << 64) | vr->t_lo, S0 = ((u128)vr->s_hi << 64) | vr->s_lo,
-                           D = ((u128)vr->d_hi << 64) | vr->d_lo;
-                const u128 n = (u128)(uint64_t)done, m = n * (n - 1) / 2;
-                const u128 T1 = T0 + n * S0 + D * (done ? m : 0), S1 = S0 + D * n;
-                x.t_hi = (uint64_t)(T1 >> 64); x.t_lo = (uint64_t)T1;
-                x.s_hi = (uint64_t)(S1 >> 64); x.s_lo = (uint64_t)S1;
-                x.d_hi = vr->d_hi; x.d_lo = vr->d_lo;
-            };
-            if (vr && (1 << ia.lgP) != ia.P) return "variable-rate needs a power-of-two phase count";
-            if (!no_itile && nf >= 4096 && (uint64_t)j.n_clips * j.n_channels <= 65535) {
-                double step = (double)p->M / (double)p->L; // input samples per output
-                if (vr) {
-                    const double two64 = 18446744073709551616.;
-                    const double s0 = (double)vr->s_hi + (double)vr->s_lo / two64;
-                    const double dd = (double)(int64_t)vr->d_hi + (double)vr->d_lo / two64;
-                    step = std::max(s0, s0 + dd * (double)(done + nf)) * (1. + 1e-9);
-                }
-                // a bucket (outputs of one interval) is served 64 at a time: aim at a mean of 60 per
-                // interval (30, 15 when LDS cannot hold that many outputs and their input span)
-                // (round 3: among the sizes that fit, the one that leaves the fewest workgroup-layers x outputs per
-                //  workgroup on the 256 CUs — 48000 -> 44101 stereo 60 s: 60 per interval are 346 workgroups, two layers
-                //  of which the second is a third full; 41 per interval are 506)
-                // two outputs per lane (InterpTileArgs): neighbouring channels of an even channel count, else — constant rate —
-                // the column's own second half, split h periods of L outputs in when that half has >= 0.7 of the first's outputs
-                // — taken when the launch's workgroup layers x outputs per workgroup come out cheaper than with one output
-                // per lane (a pair workgroup takes ~1.7x a single one: 60 s stereo 393 -> 348 us, 8 channels 1622 -> 1120,
-                // mono 232 -> 190; a 10 s stereo job has too few workgroups to halve them)
-                constexpr double kPairWg = 1.7, kTwinWg = 1.4; // (... 1.4 with the span staged twice for 16-byte reads: stereo 348 -> 296, mono 190 -> 145)
-                int cand_mode = 0;
-                int64_t cand_h = 0, cand_nf = nf;
-                if (!switches().no_interp_pair) {
-                    if (j.n_channels % 2 == 0) cand_mode = 1;
-                    else if (!vr) {
-                        const int64_t h = (nf + 2 * p->L - 1) / (2 * p->L), n1 = h * p->L;
-                        if (h >= 1 && n1 < nf && 10 * (nf - n1) >= 7 * n1 && h * p->M < ((int64_t)1 << 40)) { cand_mode = 2; cand_h = h; cand_nf = n1; }
-                    }
-                }
-                double best_cost = 1e300, cols_ = (double)j.n_clips * j.n_channels;
-                for (int mode : {0, cand_mode}) {
-                    if (mode == 0 && cand_mode && switches().dbg_interp_pair_always) continue;
-                    const int nm = mode ? 2 : 1;
-                    const int64_t nft = mode == 2 ? cand_nf : nf;
-                    const double cols_m = (double)j.n_clips * j.n_channels / (mode == 1 ? 2 : 1);
-                    for (int tw = 0; tw <= (mode && sizeof(Real) == 4 && !switches().dbg_interp_no_twin ? 1 : 0); ++tw) // float pairs: one or two copies of the span
-                        for (int per = 64; per >= 15; --per) {
-                            const int64_t k = (int64_t)per * p->phases;
-                            if (k > 16384 || k > nft) continue;
-                            const int64_t sc = (int64_t)std::ceil((double)k * step) + p->T + 8;
-                            const int64_t bytes = (tw ? 2 * (sc + 4) : sc) * nm * (int64_t)sizeof(Real) + k * 2 + (2 * p->phases + 2) * 4 + 64;
-                            if (bytes > 150 * 1024) continue;
-                            const double wgs_ = std::ceil((double)nft / (double)k) * cols_m;
-                            const double cost = std::ceil(wgs_ / 256.) * (double)k * (per >= 30 ? 1. : 30. / per) * (tw ? kTwinWg : mode ? kPairWg : 1.); // (thin buckets: idle lanes)
-                            if (cost < best_cost) { best_cost = cost; KO = k; span_cap = sc; pair_mode = mode; twin = tw != 0; split_h = mode == 2 ? cand_h : 0; nf_t = nft; cols_ = cols_m; }
-                        }
-                    if (!cand_mode) break;
-                }
-                // ... which pays off once the launch fills the chip.  A workgroup of it is long (KO outputs x T taps one
-                // interval at a time: ~130 us at VHQ, 1.5 ms with the variable-rate clock), so a launch of a few of them
-                // loses to lane-per-output k_interp, whose time grows with the work instead (measured, us per output x tap:
-                // k_interp 2.5e-6; a k_interp_tile workgroup 6.3e-5 constant rate, 2.9e-4 variable rate; 256 CUs):
-                // 96 000-frame variable-rate chunk 1.5 ms -> 0.1 ms on k_interp; 10 s stereo constant rate 134 us on
-                // the tile kernel (503 on k_interp); 1 s stereo 75 us on k_interp (127 on the tile kernel).
-                if (KO) {
-                    const double wgs = (double)((nf_t + KO - 1) / KO) * cols_;
-                    const double t_tile = std::ceil(wgs / 256.) * (double)KO * p->T * (vr ? 2.9e-4 : 6.3e-5) * (twin ? kTwinWg : pair_mode ? kPairWg : 1.);
-                    const double t_lane = (wave_ok ? kWaveUsPerTap : 2.5e-6) * (double)nf * ((double)j.n_clips * j.n_channels) * p->T;
-                    if (t_lane < t_tile) KO = 0;
-                }
-            }
-            if (!KO && wave_ok) { // a half-chain per quad of lanes (k_interp_wave)
-                InterpWaveArgs wa;
-                wa.ia = ia; wa.span_cap = (int32_t)wave_span; wa.done_words = nullptr; wa.done_seq = 0;
-                if (vr) vr_advance(wa.ia);
-                {
-                    const uint64_t wgs = (uint64_t)((nf + 31) / 32) * ((uint64_t)j.n_clips * j.n_channels);
-                    if (cd && done == 0 && nf == j.out_frames && wgs <= cd->cap) { // the whole job is this launch
-                        wa.done_words = cd->words; wa.done_seq = cd->seq;
-                        cd->n_wgs = (uint32_t)wgs;
-                    }
-                }
-                void (*wk)(InterpWaveArgs) = vr ? k_interp_wave<IO, Real, true> : k_interp_wave<IO, Real, false>;
-                hipLaunchKernelGGL(wk, dim3((unsigned)((nf + 31) / 32), (unsigned)((uint64_t)j.n_clips * j.n_channels), 1), dim3(256), wave_lds, st, wa);
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
-            if (KO) {
-                InterpTileArgs ta;
-                ta.ia = ia; ta.KO = (int32_t)KO; ta.span_cap = (int32_t)((span_cap + 1) / 2 * 2);
-                if (vr) { // positions relative to the first output of this chunk
-                    typedef unsigned __int128 u128;
-                    const u128 T0 = ((u128)vr->t_hi << 64) | vr->t_lo, S0 = ((u128)vr->s_hi << 64) | vr->s_lo,
-                               D = ((u128)vr->d_hi << 64) | vr->d_lo;
-                    const u128 n = (u128)(uint64_t)done, m = n * (n - 1) / 2;
-                    const u128 T1 = T0 + n * S0 + D * (done ? m : 0), S1 = S0 + D * n;
-                    ta.ia.t_hi = (uint64_t)(T1 >> 64); ta.ia.t_lo = (uint64_t)T1;
-                    ta.ia.s_hi = (uint64_t)(S1 >> 64); ta.ia.s_lo = (uint64_t)S1;
-                    ta.ia.d_hi = vr->d_hi; ta.ia.d_lo = vr->d_lo;
-                }
-                ta.cols_per_clip = pair_mode == 1 ? j.n_channels / 2 : j.n_channels; ta.ch_step = pair_mode == 1 ? 2 : 1;
-                ta.m2_in = ta.m2_out = ta.m2_l = ta.m2_k = 0; ta.m2_n = nf; ta.m2_dch = 0;
-                if (pair_mode == 1) { ta.m2_in = j.in_chan_stride; ta.m2_out = j.out_chan_stride; ta.m2_dch = 1; }
-                if (pair_mode == 2) {
-                    ta.m2_l = split_h * p->M; ta.m2_k = split_h * p->L; ta.m2_in = ta.m2_l * j.in_frame_stride; ta.m2_out = ta.m2_k * j.out_frame_stride;
-                    ta.m2_n = nf - nf_t; ta.ia.g.out_frames = nf_t;
-                }
-                const size_t lds = (size_t)(twin ? 2 * (ta.span_cap + 2) : ta.span_cap) * (pair_mode ? 2 : 1) * sizeof(Real) + (size_t)KO * 2 + (size_t)(2 * p->phases + 2) * 4 + 64;
-                const dim3 tgrid((unsigned)((nf_t + KO - 1) / KO), (unsigned)((uint64_t)j.n_clips * ta.cols_per_clip), 1);
-                void (*tk)(InterpTileArgs) = pair_mode ? (vr ? k_interp_tile<IO, Real, true, true> : k_interp_tile<IO, Real, false, true>)
-                                                       : (vr ? k_interp_tile<IO, Real, true, false> : k_interp_tile<IO, Real, false, false>);
-                if constexpr (sizeof(Real) == 4)
-                    if (twin) tk = vr ? k_interp_tile<IO, Real, true, true, true> : k_interp_tile<IO, Real, false, true, true>;
-                if (const char *e = ensure_dyn_lds((const void *)tk, lds)) return e;
-                hipLaunchKernelGGL(tk, tgrid, dim3(1024), lds, st, ta);
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
+            ia.g = c.a;
+            set_interp_table(ia, *p, d);
             if (vr) {
                 if ((1 << ia.lgP) != ia.P) return "variable-rate needs a power-of-two phase count";
-                // position of the first output of this launch: advance (T0, S0) by `done` outputs
-                typedef unsigned __int128 u128;
-                const u128 T0 = ((u128)vr->t_hi << 64) | vr->t_lo, S0 = ((u128)vr->s_hi << 64) | vr->s_lo,
-                           D = ((u128)vr->d_hi << 64) | vr->d_lo;
-                const u128 n = (u128)(uint64_t)done, m = n * (n - 1) / 2;
-                const u128 T1 = T0 + n * S0 + D * (done ? m : 0), S1 = S0 + D * n;
-                ia.t_hi = (uint64_t)(T1 >> 64); ia.t_lo = (uint64_t)T1;
-                ia.s_hi = (uint64_t)(S1 >> 64); ia.s_lo = (uint64_t)S1;
-                ia.d_hi = vr->d_hi; ia.d_lo = vr->d_lo;
-                hipLaunchKernelGGL((k_interp<IO, Real, true>), grid, block, 0, st, ia);
-            } else {
-                hipLaunchKernelGGL((k_interp<IO, Real, false>), grid, block, 0, st, ia);
+                vr_advance(*vr, done, ia);
             }
+            InterpTileForm tf; // large launches: k_interp_tile where its cost model beats the lane-per-output kernels
+            if (!switches().no_interp_tile && nf >= 4096 && cols_fit) tf = interp_tile_form<Real>(*p, j, nf, step, vr != nullptr, iw.ok);
+            if (!tf.KO && iw.ok) err = launch_interp_wave<IO, Real>(c, ia, iw);
+            else if (tf.KO) err = launch_interp_tile<IO, Real>(*p, c, ia, tf);
+            else err = launch_lane<IO, Real>(c, &ia);
         } else {
-            hipLaunchKernelGGL((k_gather<IO, Real>), grid, block, 0, st, a);
+            err = launch_lane<IO, Real>(c, nullptr);
         }
-        HIP_TRY(hipGetLastError());
+        if (err) return err;
     }
     return nullptr;
 }
@@ -1178,30 +1212,14 @@ static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, 
 template <typename IO, typename Real>
 static const char *launch_wave_dot(Plan *p, const hipsoxr_job_t &j, hipStream_t st)
 {
-    DeviceBank &d = p->dev[sizeof(Real) == 4 ? 0 : 1];
+    const DeviceBank &d = bank_of<Real>(p);
     if (p->phases) return "wave-dot kernel needs an exact-bank plan";
-    {
-        std::lock_guard<std::mutex> lk(p->mu);
-        if (!d.phase_major) {
-            std::vector<Real> pm(p->bank.size());
-            for (size_t i = 0; i < pm.size(); ++i) pm[i] = (Real)p->bank[i];
-            HIP_TRY(hipMalloc(&d.phase_major, pm.size() * sizeof(Real)));
-            HIP_TRY(hipMemcpy(d.phase_major, pm.data(), pm.size() * sizeof(Real), hipMemcpyHostToDevice));
-        }
-    }
+    if (const char *e = ensure_phase_major<Real>(p)) return e;
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
     if (cols > 65535) return "too many (clip, channel) columns for one launch (max 65535)";
     if (j.out_frames > ((int64_t)1 << 30)) return "job too long for the wave-dot kernel";
-    GatherArgs a;
-    a.in = j.in; a.out = j.out; a.bank = nullptr; a.Lpad = 0; a.L = p->L; a.M = p->M; a.T = p->T;
-    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
-    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-    a.in_abs0 = j.in_abs0; a.in_frames = j.in_frames; a.out_k0 = j.out_k0; a.out_frames = j.out_frames;
-    __int128 kM = (__int128)j.out_k0 * p->M;
-    a.d0 = (int64_t)(kM / p->L); a.p0 = (int64_t)(kM % p->L);
-    a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
-    a.ch_fast = 0;
+    GatherArgs a = make_gather_args<IO>(*p, d, j, j.out_k0, j.out_frames, 0);
+    a.bank = nullptr; a.Lpad = 0; a.ch_fast = 0; // (the phase-major bank travels beside the arguments; columns always in grid.y)
     const int32_t per_wave = 16;
     const int64_t waves = (j.out_frames + per_wave - 1) / per_wave;
     hipLaunchKernelGGL((k_wave_dot<IO, Real>), dim3((unsigned)((waves + 3) / 4), (unsigned)cols, 1), dim3(256), 0, st, a,
@@ -1329,57 +1347,35 @@ static const char *launch_chain_items_typed(Plan *p, uint32_t nch, bool dither, 
     int64_t max_out = 0;
     for (uint32_t i = 0; i < n_items; ++i) max_out = std::max(max_out, items[i].out_frames);
     if (max_out >= 4096 || (uint64_t)n_items * nch > 65535 || switches().no_chain) return nullptr;
-    const DeviceBank &d = p->dev[sizeof(Real) == 4 ? 0 : 1];
-    // geometry of k_chain as launch_gather sets it up: few outputs per workgroup for short chunks, LDS = NO coefficient rows + the span
-    int NO = max_out <= 512 ? 8 : 32;
-    if (switches().dbg_chain_no) NO = switches().dbg_chain_no;
-    const int64_t shift = (p->M + p->L - 1) / p->L + 2;
-    auto chain_lds = [&](int no, int32_t *span_cap) {
-        const int64_t sc = (int64_t)p->T + (int64_t)no * shift + 4;
-        *span_cap = (int32_t)sc;
-        return (size_t)no * (p->T + 16 / sizeof(Real)) * sizeof(Real) + (size_t)((sc + 3) & ~3) * sizeof(Real) + (size_t)no * 16;
-    };
-    int32_t span_cap = 0;
-    while (NO > 2 && chain_lds(NO, &span_cap) > 150 * 1024) NO /= 2;
-    const size_t lds = chain_lds(NO, &span_cap);
-    if (lds > 150 * 1024 || shift >= (1 << 20)) return nullptr;
+    const DeviceBank &d = bank_of<Real>(p);
+    const ChainGeom g = chain_geom<Real>(*p, max_out);
+    if (!g.ok) return nullptr;
     ChainMultiArgs m;
     std::memset(&m, 0, sizeof m);
+    // a stream's own layout: interleaved frames; pointers, positions and seeds are the items'
+    hipsoxr_job_t lay{};
+    lay.n_clips = 1; lay.n_channels = nch; lay.dither = dither ? 1u : 0u;
+    lay.in_frame_stride = lay.out_frame_stride = nch; lay.in_chan_stride = lay.out_chan_stride = 1;
     GatherArgs &a = m.ca.ia.g;
-    a.bank = d.tap_major; a.Lpad = d.Lpad; a.L = p->L; a.M = p->M; a.T = p->T;
-    a.n_clips = 1; a.n_channels = nch;
-    a.ics = 0; a.ifs = nch; a.ichs = 1; a.ocs = 0; a.ofs = nch; a.ochs = 1; // a stream's own layout: interleaved frames
-    a.oc.dither = dither ? 1u : 0u; a.oc.ch0 = 0;
-    a.ch_fast = 0;
-    m.ca.NO = NO; m.ca.span_cap = span_cap;
+    a = make_gather_args<IO>(*p, d, lay, 0, 0, 0);
+    a.oc.ch0 = 0; a.ch_fast = 0;
+    m.ca.NO = g.NO; m.ca.span_cap = g.span_cap;
     m.n_channels = nch;
     void (*ck)(ChainMultiArgs) = nullptr;
     if (p->phases) {
-        m.ca.ia.tab = d.interp_tab; m.ca.ia.P = p->phases;
-        while ((1 << m.ca.ia.lgP) < m.ca.ia.P) ++m.ca.ia.lgP;
+        set_interp_table(m.ca.ia, *p, d);
         ck = k_chain_multi<IO, Real, 1>;
     } else {
-        DeviceBank &dm = p->dev[sizeof(Real) == 4 ? 0 : 1];
-        const char *err = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(p->mu);
-            if (!dm.phase_major) {
-                std::vector<Real> pm(p->bank.size());
-                for (size_t i = 0; i < pm.size(); ++i) pm[i] = (Real)p->bank[i];
-                if (hipMalloc(&dm.phase_major, pm.size() * sizeof(Real)) != hipSuccess) err = "hipMalloc failed";
-                else if (hipMemcpy(dm.phase_major, pm.data(), pm.size() * sizeof(Real), hipMemcpyHostToDevice) != hipSuccess) err = "hipMemcpy failed";
-            }
-        }
-        if (err) return err;
-        m.ca.phase_major = dm.phase_major;
+        if (const char *e = ensure_phase_major<Real>(p)) return e;
+        m.ca.phase_major = d.phase_major;
         ck = k_chain_multi<IO, Real, 0>;
     }
     if (n_items == 1) m.one = items[0];
     else if (!items_dev) return "internal: a many-streams launch needs a device-readable item table";
     else m.items = items_dev;
-    if (const char *e = ensure_dyn_lds((const void *)ck, lds)) return e;
-    const unsigned gx = (unsigned)std::max<int64_t>(1, (max_out + NO - 1) / NO);
-    hipLaunchKernelGGL(ck, dim3(gx, (unsigned)(n_items * nch), 1), dim3(256), lds, st, m);
+    if (const char *e = ensure_dyn_lds((const void *)ck, g.lds)) return e;
+    const unsigned gx = (unsigned)std::max<int64_t>(1, (max_out + g.NO - 1) / g.NO);
+    hipLaunchKernelGGL(ck, dim3(gx, (unsigned)(n_items * nch), 1), dim3(256), g.lds, st, m);
     HIP_TRY(hipGetLastError());
     *handled = true;
     return nullptr;
@@ -1417,7 +1413,8 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
 {
     if (cd) cd->n_wgs = 0;
     if (j.out_frames <= 0 || j.n_clips == 0 || j.n_channels == 0) return res ? "resident kernel: empty job" : nullptr;
-    if (res && (uint64_t)j.n_clips * j.n_channels > 65535) return "resident kernel: too many columns";
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (res && cols > 65535) return "resident kernel: too many columns";
     const bool want_pcm = j.kernel == HIPSOXR_KERNEL_FFT_PCM;
     if (want_pcm)
         if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
@@ -1439,7 +1436,7 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         const bool want_fft = j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64 || want_pcm;
         const bool big = total_out * (int64_t)j.n_channels >= (1 << 13);
         if ((want_fft || (j.kernel == HIPSOXR_KERNEL_AUTO && big && !switches().no_fft)) &&
-            (uint64_t)j.n_clips * j.n_channels <= 65535 && fft_job_eligible(*p, j)) {
+            cols <= 65535 && fft_job_eligible(*p, j)) {
             if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
             // The kernel reads the DEVICE copy of the table.  Without one (clip_table_dev == NULL) the host table — the
             // one validated above — is uploaded here, in stream order (stream-ordered allocation: the buffer lives until
@@ -1480,40 +1477,30 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     // Kernels index (clip, channel) columns through grid.y (<= 65535).  Wider jobs — the Python surface
     // admits 65536 channels like the reference, src/soxr/__init__.py:22 — are folded into several
     // launches over channel (or clip) ranges; columns are independent, so the result is the same.
-    if ((uint64_t)j.n_clips * j.n_channels > 65535) {
+    if (cols > 65535) {
         const size_t es = elem_size(j.elem);
         hipsoxr_job_t part = j;
-        if (j.n_channels > 1) {
-            const uint32_t step = j.n_clips > 65535 ? 1 : 65535 / j.n_clips;
-            if (j.n_clips > 65535) { // both wide: one clip range at a time, channels folded below it
-                for (uint32_t c0 = 0; c0 < j.n_clips; c0 += 65535) {
-                    part = j;
-                    part.n_clips = std::min<uint32_t>(65535, j.n_clips - c0);
-                    part.in = (const char *)j.in + (int64_t)c0 * j.in_clip_stride * (int64_t)es;
-                    part.out = (char *)j.out + (int64_t)c0 * j.out_clip_stride * (int64_t)es;
-                    if (const char *e = launch_job(p, part, stream, vr)) return e;
-                }
-                return nullptr;
-            }
-            for (uint32_t h0 = 0; h0 < j.n_channels; h0 += step) {
+        if (j.n_channels == 1 || j.n_clips > 65535) { // one clip range at a time (clips and channels both wide: the channels are folded below it)
+            for (uint32_t c0 = 0; c0 < j.n_clips; c0 += 65535) {
                 part = j;
-                part.n_channels = std::min<uint32_t>(step, j.n_channels - h0);
-                part.in = (const char *)j.in + (int64_t)h0 * j.in_chan_stride * (int64_t)es;
-                part.out = (char *)j.out + (int64_t)h0 * j.out_chan_stride * (int64_t)es;
-                const uint32_t saved = t_ch_base;
-                t_ch_base = saved + h0;
-                const char *e = launch_job(p, part, stream, vr);
-                t_ch_base = saved;
-                if (e) return e;
+                part.n_clips = std::min<uint32_t>(65535, j.n_clips - c0);
+                part.in = (const char *)j.in + (int64_t)c0 * j.in_clip_stride * (int64_t)es;
+                part.out = (char *)j.out + (int64_t)c0 * j.out_clip_stride * (int64_t)es;
+                if (const char *e = launch_job(p, part, stream, vr)) return e;
             }
             return nullptr;
         }
-        for (uint32_t c0 = 0; c0 < j.n_clips; c0 += 65535) {
+        const uint32_t step = 65535 / j.n_clips;
+        for (uint32_t h0 = 0; h0 < j.n_channels; h0 += step) {
             part = j;
-            part.n_clips = std::min<uint32_t>(65535, j.n_clips - c0);
-            part.in = (const char *)j.in + (int64_t)c0 * j.in_clip_stride * (int64_t)es;
-            part.out = (char *)j.out + (int64_t)c0 * j.out_clip_stride * (int64_t)es;
-            if (const char *e = launch_job(p, part, stream, vr)) return e;
+            part.n_channels = std::min<uint32_t>(step, j.n_channels - h0);
+            part.in = (const char *)j.in + (int64_t)h0 * j.in_chan_stride * (int64_t)es;
+            part.out = (char *)j.out + (int64_t)h0 * j.out_chan_stride * (int64_t)es;
+            const uint32_t saved = t_ch_base;
+            t_ch_base = saved + h0;
+            const char *e = launch_job(p, part, stream, vr);
+            t_ch_base = saved;
+            if (e) return e;
         }
         return nullptr;
     }
