@@ -933,9 +933,9 @@ struct FftGeom {
     int32_t radA[8] = {1, 1, 1, 1, 1, 1, 1, 1}, radB[8] = {1, 1, 1, 1, 1, 1, 1, 1}, nA = 0, nB = 0; // (plain arrays: the cached geometry is copied per launch)
     int32_t lead_periods = 0, hop_periods = 0, v0 = 0, hop_out = 0;
     size_t lds_bytes = 0;
-    float2 *dev = nullptr; // [WA: A][WB: B][P: A+1][Q: B][Hs: B+1][WA2: N_in][WB2: N_out][Hr: B+1 floats][TWA][TWB]
+    float2 *dev = nullptr; // the float32 tables, laid out as fft_tabs says, then the per-pass tables
     size_t twa = 0, twb = 0; // per-pass twiddle tables of the one-round kernels: their places in `dev` (0: none)
-    double2 *devd = nullptr; // float64 instance of the paired kernel: [WA2d: N_in][WB2d: N_out][Hrd: B+1 doubles]
+    double2 *devd = nullptr; // float64 instance of the paired kernel: WA2d, WB2d, Hrd (fft_tabs)
 };
 
 static bool factor_radices(int n, std::vector<int> &rad)
@@ -969,12 +969,41 @@ void fft_release(const Plan *p)
         } else ++i;
 }
 
-// Outputs a block discards at either end, in whole periods at its front: the filter support [n_k, n_k + T) of a kept
-// output lies inside the block.  A function of the plan alone — the same for every block size of a ratio.
-static int32_t fft_lead_periods(const Plan &p)
+// Where each table lies in FftGeom::dev (float2 units; Hr: B + 1 floats) and FftGeom::devd (double2 units; Hrd: B + 1
+// doubles): fft_build fills through it, fft_args_geom points through it.  Per-pass tables follow behind `n` (twa / twb).
+struct FftTabs {
+    size_t WA, WB, P, Q, Hs, WA2, WB2, Hr, n; // dev
+    size_t WA2d, WB2d, Hrd, nd;               // devd
+};
+static FftTabs fft_tabs(const FftGeom &g)
+{
+    FftTabs t;
+    const size_t A = (size_t)g.A, B = (size_t)g.B, h = (B + 2) / 2 + 1; // (h: B + 1 real values in complex units, rounded up)
+    t.WA = 0; t.WB = t.WA + A; t.P = t.WB + B; t.Q = t.P + (A + 1); t.Hs = t.Q + B;
+    t.WA2 = t.Hs + (B + 1); t.WB2 = t.WA2 + (size_t)g.N_in; t.Hr = t.WB2 + (size_t)g.N_out; t.n = t.Hr + h;
+    t.WA2d = 0; t.WB2d = t.WA2d + (size_t)g.N_in; t.Hrd = t.WB2d + (size_t)g.N_out; t.nd = t.Hrd + h;
+    return t;
+}
+
+// The kept run of a block of k periods.  A block discards ceil((T/2+2) L/M) outputs at either end — the filter support
+// [n_k, n_k + T) of a kept output lies inside the block — in whole periods at its front (lead_periods: a function of the
+// plan alone, the same for every block size of a ratio), and keeps a whole number of periods (hop_periods).  False: no
+// period is kept — or, with need_half, fewer than half of the block's outputs are (long filters on short blocks).
+struct KeptRun { int32_t lead_periods = 0, hop_periods = 0; };
+static bool fft_kept_run(const Plan &p, int64_t k, bool need_half, KeptRun *r)
 {
     const int64_t disc = ((int64_t)(p.T / 2 + 2) * p.L + p.M - 1) / p.M;
-    return (int32_t)((disc + p.L - 1) / p.L);
+    r->lead_periods = (int32_t)((disc + p.L - 1) / p.L);
+    r->hop_periods = (int32_t)((k * p.L - disc - (int64_t)r->lead_periods * p.L) / p.L);
+    if (r->hop_periods < 1) return false;
+    return !need_half || 2 * (int64_t)r->hop_periods * p.L >= k * p.L;
+}
+// Outputs a block of k periods keeps (fft_geometry's hop_out for a forced k, arithmetic only); 0: no such block.
+// (The half-kept refusal holds here whatever the caller: this is asked about forced block sizes alone.)
+static int64_t fft_hop_out(const Plan &p, int k)
+{
+    KeptRun r;
+    return fft_kept_run(p, k, true, &r) ? (int64_t)r.hop_periods * p.L : 0;
 }
 
 // Block geometry (arithmetic only; fft_build adds the device tables).  False: no admissible block.
@@ -1001,19 +1030,15 @@ static bool fft_geometry(const Plan &p, FftGeom &g, bool small, int force_k)
         for (int i = 0; i < 8; ++i) { g.radA[i] = i < g.nA ? ra[i] : 1; g.radB[i] = i < g.nB ? rb[i] : 1; }
     }
     if (!g.k) return false;
-    // outputs whose filter support [n_k, n_k + T) lies inside the block: discard ceil((T/2+2)*L/M)
-    // outputs at either end, keep a whole number of periods
-    const int64_t disc = ((int64_t)(T / 2 + 2) * L + M - 1) / M;
-    g.lead_periods = fft_lead_periods(p);
-    g.hop_periods = (int32_t)((g.N_out - disc - (int64_t)g.lead_periods * L) / L);
-    if (g.hop_periods < 1) return false;
+    // a block must keep a worthwhile share of its outputs — asked of a FORCED block size only: the search above takes
+    // what it finds
+    KeptRun r;
+    if (!fft_kept_run(p, g.k, force_k != 0, &r)) return false;
+    g.lead_periods = r.lead_periods; g.hop_periods = r.hop_periods;
     g.v0 = (int32_t)(g.lead_periods * L);
     g.hop_out = (int32_t)(g.hop_periods * L);
     g.lds_bytes = (size_t)(std::max(g.A, g.B) + 8) * sizeof(float2);
-    if (g.lds_bytes > 150 * 1024) return false;
-    // a block must keep a worthwhile share of its outputs (long filters on short blocks do not)
-    if (force_k && 2 * (int64_t)g.hop_out < g.N_out) return false;
-    return true;
+    return g.lds_bytes <= 150 * 1024;
 }
 
 // Per-pass twiddle tables of a length with a Sched<N>::TABS schedule (the one-round float32 kernels): for pass 2 and
@@ -1038,6 +1063,15 @@ static bool pass_tables(int N, int sign, std::vector<float2> *tw)
     return true;
 }
 
+// w[m] = exp(sign 2 pi i m / N), m < n: computed in double, rounded once to the table's type
+template <typename C>
+static void fill_twiddles(C *w, int n, int N, int sign)
+{
+    typedef decltype(w->x) T;
+    const double PI2 = 6.283185307179586476925286766559;
+    for (int m = 0; m < n; ++m) { w[m].x = (T)std::cos(PI2 * m / N); w[m].y = (T)(sign * std::sin(PI2 * m / N)); }
+}
+
 static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_k = 0)
 {
     FftGeom g;
@@ -1045,25 +1079,27 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
     const int64_t L = p.L;
     const int32_t T = p.T;
     const int A = g.A, B = g.B;
-    std::vector<float2> tab((size_t)A + B + (A + 1) + B + (B + 1) + g.N_in + g.N_out + (B + 2) / 2 + 1);
+    const FftTabs at = fft_tabs(g);
+    std::vector<float2> tab(at.n);
     std::vector<float2> twa, twb;
     if (pass_tables(g.N_in, -1, &twa) && pass_tables(g.N_out, +1, &twb)) { // (behind everything else: 16-byte aligned or not, the loads are 8 bytes)
         g.twa = tab.size(); g.twb = g.twa + twa.size();
         tab.resize(g.twb + twb.size());
     }
-    float2 *WA = tab.data(), *WB = WA + A, *P = WB + B, *Q = P + (A + 1), *Hs = Q + B;
-    float2 *WA2 = Hs + (B + 1), *WB2 = WA2 + g.N_in;
-    const double PI2 = 6.283185307179586476925286766559;
-    for (int m = 0; m < g.N_in; ++m) WA2[m] = make_float2((float)std::cos(PI2 * m / g.N_in), (float)-std::sin(PI2 * m / g.N_in));
-    for (int m = 0; m < g.N_out; ++m) WB2[m] = make_float2((float)std::cos(PI2 * m / g.N_out), (float)std::sin(PI2 * m / g.N_out));
-    for (int m = 0; m < A; ++m) WA[m] = make_float2((float)std::cos(PI2 * m / A), (float)-std::sin(PI2 * m / A));
-    for (int m = 0; m < B; ++m) WB[m] = make_float2((float)std::cos(PI2 * m / B), (float)std::sin(PI2 * m / B));
-    for (int q = 0; q <= A; ++q) P[q] = make_float2((float)std::cos(PI2 * q / g.N_in), (float)-std::sin(PI2 * q / g.N_in));
-    for (int q = 0; q < B; ++q) Q[q] = make_float2((float)std::cos(PI2 * q / g.N_out), (float)std::sin(PI2 * q / g.N_out));
+    float2 *Hs = tab.data() + at.Hs;
+    float *Hr = reinterpret_cast<float *>(tab.data() + at.Hr);
+    fill_twiddles(tab.data() + at.WA2, g.N_in, g.N_in, -1);
+    fill_twiddles(tab.data() + at.WB2, g.N_out, g.N_out, +1);
+    fill_twiddles(tab.data() + at.WA, A, A, -1);
+    fill_twiddles(tab.data() + at.WB, B, B, +1);
+    fill_twiddles(tab.data() + at.P, A + 1, g.N_in, -1);
+    fill_twiddles(tab.data() + at.Q, B, g.N_out, +1);
     // H[q] = sum_p sum_j bank[p][j] exp(-2 pi i q (L*(T/2-1-j) + p) / (L*N_in)), scaled by 1/(N_in*L)
+    const double PI2 = 6.283185307179586476925286766559;
     const double scale = 1.0 / ((double)g.N_in * (double)L);
     const int qmax = std::min(A, B);
-    std::vector<double> hr64((size_t)B + 1, 0.); // Re H in float64 (float64 instance of the paired kernel)
+    std::vector<double2> td(at.nd); // the float64 instance's tables (small: N_in + N_out + B/2 double2)
+    double *Hrd = reinterpret_cast<double *>(td.data() + at.Hrd); // Re H in float64
     for (int q = 0; q <= B; ++q) {
         if (q > qmax) { Hs[q] = make_float2(0.f, 0.f); continue; }
         double hr = 0., hi = 0.;
@@ -1084,24 +1120,31 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
         // boundaries, so H is real: |Im H| <= 2e-13 |Re H| in the pass band (the one unpaired sample of the
         // even-length support, g[-L T/2], is a window-edge value ~1e-11).  The paired kernels use Re H alone:
         // half the table reads and a real x complex product per bin.
-        reinterpret_cast<float *>(WB2 + g.N_out)[q] = (float)(hr * scale);
-        hr64[q] = hr * scale;
+        Hr[q] = (float)(hr * scale);
+        Hrd[q] = hr * scale;
     }
     std::copy(twa.begin(), twa.end(), tab.begin() + g.twa);
     std::copy(twb.begin(), twb.end(), tab.begin() + g.twb);
     HIP_TRY(hipMalloc((void **)&g.dev, tab.size() * sizeof(float2)));
     HIP_TRY(hipMemcpy(g.dev, tab.data(), tab.size() * sizeof(float2), hipMemcpyHostToDevice));
-    { // the float64 instance's tables (small: N_in + N_out + B/2 double2)
-        std::vector<double2> td((size_t)g.N_in + g.N_out + (B + 2) / 2 + 1);
-        for (int m = 0; m < g.N_in; ++m) td[m] = make_double2(std::cos(PI2 * m / g.N_in), -std::sin(PI2 * m / g.N_in));
-        for (int m = 0; m < g.N_out; ++m) td[(size_t)g.N_in + m] = make_double2(std::cos(PI2 * m / g.N_out), std::sin(PI2 * m / g.N_out));
-        double *hrd = reinterpret_cast<double *>(td.data() + g.N_in + g.N_out);
-        for (int q = 0; q <= B; ++q) hrd[q] = q < (int)hr64.size() ? hr64[q] : 0.;
-        HIP_TRY(hipMalloc((void **)&g.devd, td.size() * sizeof(double2)));
-        HIP_TRY(hipMemcpy(g.devd, td.data(), td.size() * sizeof(double2), hipMemcpyHostToDevice));
-    }
+    fill_twiddles(td.data() + at.WA2d, g.N_in, g.N_in, -1);
+    fill_twiddles(td.data() + at.WB2d, g.N_out, g.N_out, +1);
+    HIP_TRY(hipMalloc((void **)&g.devd, td.size() * sizeof(double2)));
+    HIP_TRY(hipMemcpy(g.devd, td.data(), td.size() * sizeof(double2), hipMemcpyHostToDevice));
     g.ok = true;
     *out = g;
+    return nullptr;
+}
+
+// geometry cache, key (plan, variant): 0 = default search, 1 = small-block search, 2 + i = forced k of row i of fft_pairs,
+// 1000 + k = k_fft_wave's forced k
+static const char *fft_geom_cached(Plan *p, int variant, int force_k, FftGeom *g)
+{
+    std::lock_guard<std::mutex> lk(g_fft_mu);
+    for (auto &e : g_fft)
+        if (e.first.first == p && e.first.second == variant) { *g = e.second; return nullptr; }
+    if (const char *err = fft_build(*p, g, variant == 1, force_k)) return err;
+    g_fft.push_back({{p, variant}, *g});
     return nullptr;
 }
 
@@ -1123,7 +1166,7 @@ struct PairEntry {
      k_fft_strided2<PairOf<NA, NB, NT>, float, false>, k_fft_strided2<PairOf<NA, NB, NT>, double, false>, \
      k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>, k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>, \
      k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>}
-// ... float32 unit-stride columns only: every other pointer null (taken by the one-round rule of launch_fft_impl alone)
+// ... float32 unit-stride columns only: every other pointer null (taken by the one-round rule, fft_one_round_pick, alone)
 #define HIPSOXR_PAIR_F32(L, M, k, NA, NB) \
     {L, M, k, 3, FFT_ONE_ROUND_NT, k_fft_pair2<PairOf<NA, NB, FFT_ONE_ROUND_NT>, float>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
 static const PairEntry *fft_pairs(int *n)
@@ -1205,13 +1248,6 @@ static bool cu_shape(CuShape *out)
     *out = c;
     return c.cus > 0;
 }
-// Outputs a block of k periods keeps (fft_geometry's hop_out, arithmetic only); 0: no such block
-static int64_t fft_hop_out(const Plan &p, int k)
-{
-    const int64_t disc = ((int64_t)(p.T / 2 + 2) * p.L + p.M - 1) / p.M;
-    const int64_t hop_periods = ((int64_t)k * p.L - disc - (int64_t)fft_lead_periods(p) * p.L) / p.L;
-    return hop_periods < 1 || 2 * hop_periods * p.L < (int64_t)k * p.L ? 0 : hop_periods * p.L;
-}
 
 // Whole-signal float32 / float64 job (or an int16 / int32 one that names the engine)?  (zero-extended signal starting at absolute index 0, all outputs)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
@@ -1222,6 +1258,36 @@ bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
     const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32) : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64);
     return p.phases == 0 && p.att_db >= 120. && elem_ok && j.in_abs0 == 0 &&
            j.out_k0 == 0 && (uint64_t)j.out_frames <= plan_out_len(p, (uint64_t)j.in_frames);
+}
+
+// Rows of fft_pairs that serve a ratio (indices; -1: none); cand: every block size — what the one-round rule chooses among
+struct RatioRows { int big = -1, sml = -1, tiny = -1, cand[8], n_cand = 0; };
+static RatioRows fft_ratio_rows(const Plan &p)
+{
+    RatioRows r;
+    int n = 0;
+    const PairEntry *pairs = fft_pairs(&n);
+    for (int i = 0; i < n; ++i)
+        if (pairs[i].L == p.L && pairs[i].M == p.M) {
+            if (r.n_cand < 8) r.cand[r.n_cand++] = i;
+            if (pairs[i].small == 3) continue; // (one-round float32 jobs only: fft_one_round_pick)
+            if (pairs[i].small == 2) r.tiny = i;
+            else if (pairs[i].small) r.sml = i;
+            else r.big = i;
+        }
+    return r;
+}
+
+// byte offsets over `blocks` blocks at a frame stride fit the kernels' 32-bit operands
+static bool fft_offsets_fit(const FftGeom &g, int blocks, int64_t frame_stride, size_t esz)
+{
+    return blocks * (int64_t)std::max(g.N_in, g.N_out) * frame_stride * (int64_t)esz < (1LL << 30);
+}
+
+// block pairs (the paired kernels' work items) over `span` outputs, all columns
+static int64_t fft_pair_items(int64_t span, int64_t hop_out, uint64_t cols)
+{
+    return ((span + hop_out - 1) / hop_out + 1) / 2 * (int64_t)cols;
 }
 
 // Streams on this engine (HIPSOXR_STREAM_FFT): what it cannot serve is refused when the stream is created, by name.
@@ -1238,16 +1304,14 @@ const char *fft_stream_refusal(const Plan &p, int elem, uint32_t ch, int32_t *le
     if (elem == HIPSOXR_I16 && ch > 1 && ch % 2) return "STREAM_FFT stream: int16 streams are served with one channel or an even channel count (as HIPSOXR_KERNEL_FFT_PCM: interleaved channel pairs)";
     int n = 0;
     const PairEntry *pairs = fft_pairs(&n);
-    const PairEntry *big = nullptr;
-    for (int i = 0; i < n; ++i)
-        if (pairs[i].L == p.L && pairs[i].M == p.M && !pairs[i].small) big = &pairs[i];
+    const int big = fft_ratio_rows(p).big;
     FftGeom g;
-    if (!big || !fft_geometry(p, g, false, big->k))
+    if (big < 0 || !fft_geometry(p, g, false, pairs[big].k))
         return "STREAM_FFT stream: the ratio is outside the paired-kernel schedule table of the frequency-domain engine (fft.hip)";
-    // the kernels' 32-bit byte offsets over a pair of blocks at the frame stride (launch_fft: cp2 / st2ok)
-    if (2 * (int64_t)std::max(g.N_in, g.N_out) * (int64_t)ch * (int64_t)elem_size(elem) >= (1LL << 30))
+    // the kernels' 32-bit byte offsets over a pair of blocks at the frame stride (fft_layout: cp2 / st2ok)
+    if (!fft_offsets_fit(g, 2, (int64_t)ch, elem_size(elem)))
         return "STREAM_FFT stream: too many channels for the frequency-domain engine's interleaved kernels";
-    *lead_periods = g.lead_periods; // (fft_lead_periods: the same for every block size of the ratio)
+    *lead_periods = g.lead_periods; // (fft_kept_run: the same for every block size of the ratio)
     return nullptr;
 }
 
@@ -1266,6 +1330,7 @@ static void fft_launch_log(const char *form, int64_t L, int64_t M, int k, int sm
     fclose(f);
 }
 
+// ---- the job as the launch code sees it -------------------------------------------------------------------
 // (job.in_abs0 != 0 — in[0] is sample in_abs0 of a column that is zero outside [in_abs0, in_abs0 + in_frames) — is served
 // for the two-stage form's inner calls; the public paths come here through fft_job_eligible, which wants 0.)
 // window (launch_fft_window, stream chunks): the job is outputs [out_k0, out_k0 + out_frames) of the column.  The paired
@@ -1273,313 +1338,358 @@ static void fft_launch_log(const char *form, int64_t L, int64_t M, int k, int sm
 // frames, so block 0 starts lead_periods before P0 and the block arithmetic is the whole-signal job's; the one thing the
 // kernels do for it is drop the outputs below out_lo = out_k0 - P0 L (< L <= hop_out: inside the first block's run) and
 // key the dither by P0 L + local index.  Served by k_fft_pair2 / k_fft_strided2 only: *handled stays false otherwise.
-static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0, bool window)
+struct FftJobView {
+    bool window;
+    int64_t P0, out_lo, span; // span: outputs from the origin to the end of the job — what blocks are counted over
+    uint64_t cols;
+    // f64: the ARITHMETIC is float64 (block size, LDS bytes per point, table set) — float64 jobs, float32 jobs that ask
+    // for libsoxr's own VHQ width with HIPSOXR_KERNEL_FFT_F64 (wide32), and int32 samples.  pcm: integer samples
+    // (HIPSOXR_KERNEL_FFT_PCM), int16 on float32 and int32 on float64 arithmetic — every size rule is the float job's of
+    // that arithmetic width.  kind: the launch log's name of the instance.
+    bool io64, wide32, pcm, pcm32, f64;
+    const char *kind;
+    size_t esz;
+};
+static FftJobView fft_job_view(const Plan &p, const hipsoxr_job_t &j, bool window)
 {
-    *handled = false;
-    const int64_t P0 = window ? j.out_k0 / p->L : 0, out_lo = window ? j.out_k0 - P0 * p->L : 0;
-    const int64_t span = out_lo + j.out_frames; // outputs from the origin to the end of the job: what blocks are counted over
-    // geometry cache key: (plan, variant) with variant 0 = default search, 1 = small-block search,
-    // 2 + i = forced k of paired-kernel entry i
-    auto get = [&](int variant, int force_k, FftGeom *g) -> const char * {
-        std::lock_guard<std::mutex> lk(g_fft_mu);
-        for (auto &e : g_fft)
-            if (e.first.first == p && e.first.second == variant) { *g = e.second; return nullptr; }
-        if (const char *err = fft_build(*p, g, variant == 1, force_k)) return err;
-        g_fft.push_back({{p, variant}, *g});
-        return nullptr;
-    };
-    // ---- paired-block kernels: compile-time schedules for the common ratios (fft_pairs) -------------------
+    FftJobView v;
+    v.window = window;
+    v.P0 = window ? j.out_k0 / p.L : 0; v.out_lo = window ? j.out_k0 - v.P0 * p.L : 0;
+    v.span = v.out_lo + j.out_frames;
+    v.cols = (uint64_t)j.n_clips * j.n_channels;
+    v.io64 = j.elem == HIPSOXR_F64; v.wide32 = !v.io64 && j.kernel == HIPSOXR_KERNEL_FFT_F64;
+    v.pcm = j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32; v.pcm32 = j.elem == HIPSOXR_I32;
+    v.f64 = v.io64 || v.wide32 || v.pcm32;
+    v.kind = v.pcm ? (v.pcm32 ? "i32" : "i16") : v.io64 ? "f64" : v.wide32 ? "f32on64" : "f32";
+    v.esz = elem_size(j.elem);
+    return v;
+}
+
+// ---- row choice --------------------------------------------------------------------------------------------
+struct FftRow { const PairEntry *use = nullptr; FftGeom g; }; // use == nullptr: no row of the table serves the job
+
+// One-round jobs (see kOneRoundCost): float32 unit-stride columns — exactly the jobs that run `kern2` (v2ok, not f64,
+// not pcm) — as whole signals, where the throughput rule left the large blocks.  Every other element type, layout and the
+// stream path keep the size rules' choice `use`; so does this one under HIPSOXR_FFT_LARGE_ONLY / _SMALL_ONLY (they name a
+// block size), and HIPSOXR_FFT_NO_TINY takes k = 8 away.  Ties go to `use`.  HIPSOXR_DEBUG_FFT_K (debug builds): k > 0
+// forces that block size for every such job, whatever its size; k < 0 turns the rule off.
+// -> the index of the row to take instead of `use`, or -1: the size rules' choice stands.
+static int fft_one_round_pick(const Plan *p, const hipsoxr_job_t &j, const FftJobView &v, const RatioRows &rows, const PairEntry *use, bool use_is_big)
+{
     int n_pairs = 0;
     const PairEntry *pairs = fft_pairs(&n_pairs);
-    const bool no_pair = switches().fft_no_pair;
-    const uint64_t cols_p = (uint64_t)j.n_clips * j.n_channels;
-    // f64: the ARITHMETIC is float64 (block size, LDS bytes per point, table set) — float64 jobs, and float32 jobs that
-    // ask for libsoxr's own VHQ width with HIPSOXR_KERNEL_FFT_F64 (io64 = the signal's elements are 8 bytes)
-    const bool io64 = j.elem == HIPSOXR_F64, wide32 = !io64 && j.kernel == HIPSOXR_KERNEL_FFT_F64;
-    // pcm: integer samples (HIPSOXR_KERNEL_FFT_PCM), int16 on float32 and int32 on float64 arithmetic — every size rule
-    // below is the float job's of that arithmetic width
-    const bool pcm = j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32, pcm32 = j.elem == HIPSOXR_I32;
-    const bool f64 = io64 || wide32 || pcm32;
-    // float64, integer samples: the paired kernels only (unit-stride columns; channel pairs; strided columns) — else the
-    // exact engine (integer samples: the caller's error)
-    const char *kind = pcm ? (pcm32 ? "i32" : "i16") : io64 ? "f64" : wide32 ? "f32on64" : "f32"; // (the launch log's name of the instance)
-    const PairEntry *log_row = nullptr;
-    struct LogNone { // leaving without a launch: the log says so
-        const bool *handled; const Plan *p; const PairEntry *const *row; const char *kind; bool window;
-        ~LogNone()
-        {
-            if (switches().dbg_launch_log && !*handled)
-                fft_launch_log("none", p->L, p->M, *row ? (*row)->k : 0, *row ? (*row)->small : -1, kind, 0, 0, dim3(0, 0, 0), 0, 0, window);
-        }
-    } log_none = {handled, p, &log_row, kind, window};
-    if ((f64 || pcm) && (no_pair || cols_p > 65535)) return nullptr;
-    if (!no_pair && cols_p <= 65535) {
-        const PairEntry *big = nullptr, *sml = nullptr, *tiny = nullptr;
-        int big_i = 0, sml_i = 0, tiny_i = 0;
-        int cand_i[8], n_cand = 0; // every block size of the ratio: what the one-round rule chooses among
-        for (int i = 0; i < n_pairs; ++i)
-            if (pairs[i].L == p->L && pairs[i].M == p->M) {
-                if (n_cand < 8) cand_i[n_cand++] = i;
-                if (pairs[i].small == 3) continue; // (one-round float32 jobs only: below)
-                if (pairs[i].small == 2) { tiny = &pairs[i]; tiny_i = i; }
-                else if (pairs[i].small) { sml = &pairs[i]; sml_i = i; }
-                else { big = &pairs[i]; big_i = i; }
-            }
-        if (big) {
-            FftGeom g;
-            if (const char *err = get(2 + big_i, big->k, &g)) return err;
-            const PairEntry *use = g.ok ? big : nullptr;
-            if (g.ok && sml) {
-                // few work items (one 60 s clip = 300 pairs): half-size blocks give twice as many,
-                // shorter workgroups, at the price of more overlap
-                const int64_t wgs = ((span + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
-                // (float64: LDS is 16 bytes per point — the half-size blocks keep four workgroups per CU)
-                // (7056-point blocks: 56 KB of LDS, two workgroups per CU — the 35 KB blocks of the k = 10 geometry keep
-                //  four and win at every size: 44.1k -> 16k VHQ, 8 x 60 s planar 41 vs 68 us, 80 x 60 s 427 vs 638 us)
-                const bool big_lds = big->nt > 384;
-                if (((wgs < 480 || big_lds) && !switches().fft_large_only) || switches().fft_small_only || f64) { // measured crossover: ~470 pairs of large blocks
-                    FftGeom gs;
-                    if (const char *err = get(2 + sml_i, sml->k, &gs)) return err;
-                    if (gs.ok) { g = gs; use = sml; }
-                }
-            }
-            // Fewer still (a 60 s clip is 612 pairs of half-size blocks on 2048 workgroup slots): the launch is the
-            // latency of one workgroup plus what queues behind it; quarter-size blocks (10 KB of LDS, 32 % overlap)
-            // shorten both: 2 s clip 7.4 -> 6.5 us, 10 s HQ 7.6 -> 6.2 us, 30 s 9.0 -> 7.7 us (60 s: 10.85 vs 10.73 us).
-            if (use == sml && tiny && !switches().fft_large_only && !switches().fft_no_tiny) {
-                const int64_t wgs = ((span + g.hop_out - 1) / g.hop_out + 1) / 2 * (int64_t)cols_p;
-                // (float32: at 612 pairs — the 60 s clip — the two sizes are within 1 %.  float64: 16 bytes per point, and
-                //  the 20 KB blocks win at every size — 60 s mono 27.1 -> 21.6 us, 64 x 10 s 236 -> 202 us, stereo 60 s 47 -> 37 us)
-                if (f64 || wgs <= 500) {
-                    FftGeom gt;
-                    if (const char *err = get(2 + tiny_i, tiny->k, &gt)) return err;
-                    if (gt.ok) { g = gt; use = tiny; }
-                }
-            }
-            // One-round jobs (see kOneRoundCost): float32 unit-stride columns — exactly the jobs that run `kern2` below
-            // (v2ok, not f64, not pcm) — as whole signals, where the throughput rule above left the large blocks.  Every
-            // other element type, layout and the stream path keep the choice made above; so does this one under
-            // HIPSOXR_FFT_LARGE_ONLY / _SMALL_ONLY (they name a block size), and HIPSOXR_FFT_NO_TINY takes k = 8 away.
-            // Ties go to the choice made above.  HIPSOXR_DEBUG_FFT_K (debug builds): k > 0 forces that block size for
-            // every such job, whatever its size; k < 0 turns the rule off.
-            const bool plain_cols = j.in_frame_stride == 1 && j.out_frame_stride == 1 &&
-                                    (j.n_channels == 1 || j.in_chan_stride != 1 || j.out_chan_stride != 1); // (=> no XCD map, no channel pairs)
-            const int force_k1 = switches().dbg_fft_k;
-            if (use && (use != big || force_k1 > 0) && plain_cols && j.elem == HIPSOXR_F32 && !wide32 && !window && force_k1 >= 0 &&
-                ((!switches().fft_large_only && !switches().fft_small_only) || force_k1 > 0)) {
-                CuShape cu;
-                auto wgs_of = [&](int64_t hop) { return ((span + hop - 1) / hop + 1) / 2 * (int64_t)cols_p; };
-                // a candidate's cost; < 0: not a candidate (no figures, no such block, or not co-resident on this device)
-                auto cost_of = [&](const PairEntry &e, const CuShape &cu) -> double {
-                    const OneRoundCost *c = one_round_cost(e);
-                    const int64_t hop = fft_hop_out(*p, e.k);
-                    if (!c || !hop || !e.kern2) return -1.;
-                    const int64_t lds = std::max(e.k * p->L, e.k * p->M) * (int64_t)sizeof(float2);
-                    if (2 * hop * (int64_t)sizeof(float) + 16 > lds) return -1.; // (the staged run must fit the transform buffer: v2ok)
-                    const int64_t slots = std::min(cu.lds / lds, cu.threads / (int64_t)e.nt);
-                    const int64_t per_cu = (wgs_of(hop) + cu.cus - 1) / cu.cus;
-                    if (per_cu > slots) return -1.;
-                    return (double)c->chain_us + (double)c->queue_us * (double)(per_cu - 1);
-                };
-                // (the answer depends on the plan, the job's size and the choice made above alone: the last one is kept per
-                //  thread, so that a loop over one job — 10 us a launch, as long as the kernel runs — pays for the rule once)
-                struct Memo { const Plan *p; int64_t L, M, span; int32_t T; uint64_t cols; const PairEntry *from; bool no_tiny; int dev, pick; };
-                static thread_local Memo memo = {nullptr, 0, 0, 0, 0, 0, nullptr, false, -1, -1};
-                int dev_now = -1;
-                (void)hipGetDevice(&dev_now);
-                const bool memo_hit = force_k1 == 0 && memo.p == p && memo.L == p->L && memo.M == p->M && memo.T == p->T && memo.span == span &&
-                                      memo.cols == cols_p && memo.from == use && memo.dev == dev_now && memo.no_tiny == switches().fft_no_tiny;
-                int pick = memo_hit ? memo.pick : -1;
-                if (memo_hit) {
-                } else if (force_k1 > 0) {
-                    for (int c = 0; c < n_cand; ++c)
-                        if (pairs[cand_i[c]].k == force_k1 && pairs[cand_i[c]].kern2) pick = cand_i[c];
-                } else if (cu_shape(&cu)) {
-                    double best = cost_of(*use, cu);
-                    for (int c = 0; c < n_cand && best >= 0.; ++c) { // (the thresholds' choice outside the model: it stands)
-                        const PairEntry &e = pairs[cand_i[c]];
-                        if (&e == use || (e.small == 2 && switches().fft_no_tiny)) continue;
-                        const double v = cost_of(e, cu);
-                        if (v >= 0. && v < best - (pick < 0 ? kOneRoundTieUs : 0.)) { best = v; pick = cand_i[c]; }
-                    }
-                }
-                if (!memo_hit && force_k1 == 0) memo = {p, p->L, p->M, span, p->T, cols_p, use, switches().fft_no_tiny, dev_now, pick};
-                if (pick >= 0 && &pairs[pick] != use) {
-                    FftGeom gc;
-                    if (const char *err = get(2 + pick, pairs[pick].k, &gc)) return err;
-                    if (gc.ok && gc.hop_out == fft_hop_out(*p, pairs[pick].k)) { g = gc; use = &pairs[pick]; }
-                }
-            }
-            if (use) {
-                log_row = use;
-                FftArgs a;
-                // (sample 0 of the columns; window: frame P0 M / P0 L of them.  int16 channel pairs: the shift is a whole
-                //  number of frames, so with the even frame strides cp_pcm_ok asks for, the 4-byte alignment it checks on
-                //  j.in / j.out holds for the shifted pointers too)
-                a.in = (const char *)j.in - (j.in_abs0 - P0 * p->M) * j.in_frame_stride * (int64_t)elem_size(j.elem);
-                a.out = (char *)j.out - out_lo * j.out_frame_stride * (int64_t)elem_size(j.elem);
-                auto set_geom = [](FftArgs &a, const FftGeom &g) {
-                    a.WA = g.dev; a.WB = a.WA + g.A; a.P = a.WB + g.B; a.Q = a.P + (g.A + 1); a.Hs = a.Q + g.B;
-                    a.WA2 = a.Hs + (g.B + 1); a.WB2 = a.WA2 + g.N_in;
-                    a.Hr = reinterpret_cast<const float *>(a.WB2 + g.N_out); a.trace = nullptr;
-                    a.WA2d = g.devd; a.WB2d = g.devd + g.N_in; a.Hrd = reinterpret_cast<const double *>(g.devd + g.N_in + g.N_out);
-                    a.TWA = g.twa ? g.dev + g.twa : nullptr; a.TWB = g.twb ? g.dev + g.twb : nullptr;
-                    a.A = g.A; a.B = g.B; a.nA = a.nB = 0;
-                    for (int i = 0; i < 8; ++i) a.radA[i] = a.radB[i] = 1;
-                    a.lead_periods = g.lead_periods; a.hop_periods = g.hop_periods; a.v0 = g.v0; a.hop_out = g.hop_out;
-                };
-                set_geom(a, g);
-                a.L = p->L; a.M = p->M;
-                a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-                a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
-                a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-                a.in_lo = j.in_abs0 - P0 * p->M; a.in_frames = a.in_lo + j.in_frames; a.out_frames = span;
-                a.out_lo = out_lo; a.out_abs0 = P0 * p->L;
-                if (out_lo >= g.hop_out) return "internal: the job window starts beyond the first block"; // (cannot happen: out_lo < L <= hop_out)
-                a.clip_tab = j.clip_table_dev;
-                a.clip_counter = pcm ? j.clip_counter : nullptr; a.dither = j.dither; a.seed = j.dither_seed; a.ch0 = ch0;
-                const int64_t n_blocks = (span + g.hop_out - 1) / g.hop_out;
-                if (n_blocks > 2147483647LL) return "job too long for one launch";
-                // interleaved data with an even channel count: pair channels (one (Real, Real) word per frame)
-                const size_t esz = elem_size(j.elem);
-                const bool cp_layout = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && !switches().fft_no_chpair;
-                // ... when a block's byte offsets fit the kernel's 32-bit operands (buffer loads: element alignment is enough)
-                // (int16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
-                const bool cp_pcm_ok = !pcm || (!pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
-                                                ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0);
-                const bool cp2 = !wide32 && cp_pcm_ok && (int64_t)std::max(g.N_in, g.N_out) * std::max(j.in_frame_stride, j.out_frame_stride) * (int64_t)esz < (1LL << 30);
-                // (channel pairing rides on the XCD-aware work-item map: decided together, so that a job without the
-                //  map — HIPSOXR_FFT_NO_XCD_MAP, or too many work items — runs unpaired on the strided kernel instead of failing)
-                const int64_t cp_items8 = (n_blocks + 7) / 8 * 8;
-                const bool cp_map_ok = j.n_channels > 1 && j.n_clips <= 65535 && cp_items8 * (int64_t)(j.n_channels / 2) <= 2147483647LL &&
-                                       !switches().fft_no_xcd_map;
-                a.chpair = (cp_layout && cp_map_ok && cp2) ? 1 : 0;
-                const size_t lds1 = std::max((size_t)std::max(g.N_in, g.N_out) * (f64 ? sizeof(double2) : sizeof(float2)), switches().dbg_fft_lds);
-                if (f64 && lds1 > 160 * 1024) return nullptr;
-                // work items per channel unit: blocks (channel pairs) or pairs of blocks (single channels)
-                const int64_t items = a.chpair ? n_blocks : (n_blocks + 1) / 2, items8 = (items + 7) / 8 * 8;
-                const int64_t units = a.chpair ? j.n_channels / 2 : j.n_channels;
-                a.xcd_map = (j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && j.n_clips <= 65535 &&
-                             items8 * units <= 2147483647LL && !switches().fft_no_xcd_map) ? 1 : 0;
-                if (a.chpair && !a.xcd_map) return "internal: channel pairing needs the XCD map"; // (cannot happen: cp_map_ok above)
-                a.pairs_per_col = items;
-                dim3 grid = a.xcd_map ? dim3((unsigned)(items8 * units), j.n_clips, 1)
-                                      : dim3((unsigned)((n_blocks + 1) / 2), (unsigned)cols_p, 1);
-                // unit-stride columns (mono / planar): buffer loads, staged aligned stores
-                // (integer samples are staged as the arithmetic's values, up to 7 elements into the run's first granule)
-                const size_t stage_bytes = pcm ? 2 * (size_t)g.hop_out * (f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * esz + 16;
-                const bool v2ok = !a.xcd_map && !a.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 && stage_bytes <= lds1;
-                const bool cp2ok = a.chpair && a.xcd_map && cp2;
-                // strided columns that are not channel pairs (odd channel counts, channel slices): two blocks of one column
-                // per transform when the byte offsets of a pair of blocks fit the 32-bit operands
-                const bool st2ok = !wide32 && !pcm && !a.chpair && !v2ok &&
-                                   2 * (int64_t)std::max(g.N_in, g.N_out) * std::max(j.in_frame_stride, j.out_frame_stride) * (int64_t)esz < (1LL << 30);
-                // Throughput form (fftwave.hip): one wave per pair of 24-period blocks, two register passes per transform —
-                // float32 unit-stride columns with enough pairs to fill the chip's 2048 wave slots four times over (below
-                // that the last, partly filled round costs more than the form gains; and a single pair's latency is
-                // longer than on the 6-wave workgroups of k_fft_pair2).
-                FftWaveKernel wk;
-                // (never a window, and never a column with frames missing in FRONT — a.in_lo > 0, data-dependent front
-                //  extension: k_fft_wave's front guard covers the lead-in of block 0 only)
-                if (v2ok && !f64 && !pcm && !window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk)) {
-                    // (the job size first, from the kernel's own constants: its geometry — a host DFT of the filter and two
-                    //  device allocations — is built only for a job that can take it; 48k -> 44.1k never does)
-                    const int64_t pairs_w = ((j.out_frames + wk.hop - 1) / wk.hop + 1) / 2;
-                    const int64_t wave_min = switches().dbg_wave_min ? switches().dbg_wave_min : wk.min_pairs;
-                    FftGeom gw;
-                    if (pairs_w * (int64_t)cols_p >= wave_min && pairs_w * (int64_t)cols_p <= 2147483000LL) // (item numbers are 32-bit; a larger job stays on k_fft_pair2)
-                        if (const char *err = get(1000 + wk.k, wk.k, &gw)) return err;
-                    if (gw.ok && gw.v0 == wk.v0 && gw.hop_out == wk.hop && gw.hop_periods == wk.hop_periods) {
-                        set_geom(a, gw);
-                        if (const char *e = fft_wave_launch(wk, a, (unsigned)pairs_w, (unsigned)cols_p, stream)) return e;
-                        if (switches().dbg_launch_log)
-                            fft_launch_log("wave", p->L, p->M, wk.k, -1, kind, 64, 0, dim3((unsigned)pairs_w, (unsigned)cols_p, 1), gw.hop_out, 2 * pairs_w, window);
-                        *handled = true;
-                        return nullptr;
-                    }
-                }
-                if (!v2ok && !cp2ok && !st2ok) return nullptr; // the general path (float32) or the exact engine
-                // ragged batches: the unit-stride kernel reads its clip's row; nothing else does
-                if (j.clip_table && !v2ok) return nullptr;
-                void (*kern)(FftArgs) = nullptr;
-                unsigned nt = use->nt;
-                size_t lds = lds1;
-                if (v2ok) {
-                    kern = pcm ? (pcm32 ? use->kern2i32 : use->kern2i16) : io64 ? use->kern2d : wide32 ? use->kern2fd : use->kern2;
-                } else {
-                    kern = pcm ? use->kcpi16 : cp2ok ? (f64 ? use->kcpd : use->kcp) : (f64 ? use->kstd : use->kst); // (pcm: cp2ok — st2ok wants floats)
-                }
-                if (!kern) return "internal: a float32-only block size was chosen for another kind of job"; // (cannot happen: plain_cols above)
-                if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
-#ifdef FFT2_TRACE
-                size_t trace_n = 0;
-                if (switches().dbg_trace) {
-                    trace_n = (size_t)grid.x * grid.y * (nt / 64) * 16;
-                    HIP_TRY(hipMalloc((void **)&a.trace, trace_n * 8));
-                    HIP_TRY(hipMemset(a.trace, 0, trace_n * 8));
-                }
-#endif
-                hipLaunchKernelGGL(kern, grid, dim3(nt), lds, (hipStream_t)stream, a);
-                HIP_TRY(hipGetLastError());
-                if (switches().dbg_launch_log)
-                    fft_launch_log(v2ok ? "pair2" : cp2ok ? "strided2_cp" : "strided2_st", use->L, use->M, use->k, use->small, kind, nt, lds, grid, g.hop_out, n_blocks, window);
-#ifdef FFT2_TRACE
-                if (a.trace) { // debugging aid only: synchronous dump of the per-wave time stamps
-                    std::vector<unsigned long long> h(trace_n);
-                    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-                    HIP_TRY(hipMemcpy(h.data(), a.trace, trace_n * 8, hipMemcpyDeviceToHost));
-                    if (FILE *f = fopen(switches().dbg_trace, "wb")) { fwrite(h.data(), 8, trace_n, f); fclose(f); }
-                    (void)hipFree(a.trace);
-                }
-#endif
-                *handled = true;
-                return nullptr;
-            }
+    const bool plain_cols = j.in_frame_stride == 1 && j.out_frame_stride == 1 &&
+                            (j.n_channels == 1 || j.in_chan_stride != 1 || j.out_chan_stride != 1); // (=> no XCD map, no channel pairs)
+    const int force_k1 = switches().dbg_fft_k;
+    if (!((!use_is_big || force_k1 > 0) && plain_cols && j.elem == HIPSOXR_F32 && !v.wide32 && !v.window && force_k1 >= 0 &&
+          ((!switches().fft_large_only && !switches().fft_small_only) || force_k1 > 0)))
+        return -1;
+    // a candidate's cost; < 0: not a candidate (no figures, no such block, or not co-resident on this device)
+    auto cost_of = [&](const PairEntry &e, const CuShape &cu) -> double {
+        const OneRoundCost *c = one_round_cost(e);
+        const int64_t hop = fft_hop_out(*p, e.k);
+        if (!c || !hop || !e.kern2) return -1.;
+        const int64_t lds = std::max(e.k * p->L, e.k * p->M) * (int64_t)sizeof(float2);
+        if (2 * hop * (int64_t)sizeof(float) + 16 > lds) return -1.; // (the staged run must fit the transform buffer: v2ok)
+        const int64_t slots = std::min(cu.lds / lds, cu.threads / (int64_t)e.nt);
+        const int64_t per_cu = (fft_pair_items(v.span, hop, v.cols) + cu.cus - 1) / cu.cus;
+        if (per_cu > slots) return -1.;
+        return (double)c->chain_us + (double)c->queue_us * (double)(per_cu - 1);
+    };
+    // (the answer depends on the plan, the job's size and the size rules' choice alone: the last one is kept per thread,
+    //  so that a loop over one job — 10 us a launch, as long as the kernel runs — pays for the rule once)
+    struct Memo { const Plan *p; int64_t L, M, span; int32_t T; uint64_t cols; const PairEntry *from; bool no_tiny; int dev, pick; };
+    static thread_local Memo memo = {nullptr, 0, 0, 0, 0, 0, nullptr, false, -1, -1};
+    int dev_now = -1;
+    (void)hipGetDevice(&dev_now);
+    const bool memo_hit = force_k1 == 0 && memo.p == p && memo.L == p->L && memo.M == p->M && memo.T == p->T && memo.span == v.span &&
+                          memo.cols == v.cols && memo.from == use && memo.dev == dev_now && memo.no_tiny == switches().fft_no_tiny;
+    if (memo_hit) return memo.pick;
+    int pick = -1;
+    CuShape cu;
+    if (force_k1 > 0) {
+        for (int c = 0; c < rows.n_cand; ++c)
+            if (pairs[rows.cand[c]].k == force_k1 && pairs[rows.cand[c]].kern2) pick = rows.cand[c];
+    } else if (cu_shape(&cu)) {
+        double best = cost_of(*use, cu);
+        for (int c = 0; c < rows.n_cand && best >= 0.; ++c) { // (the size rules' choice outside the model: it stands)
+            const PairEntry &e = pairs[rows.cand[c]];
+            if (&e == use || (e.small == 2 && switches().fft_no_tiny)) continue;
+            const double cst = cost_of(e, cu);
+            if (cst >= 0. && cst < best - (pick < 0 ? kOneRoundTieUs : 0.)) { best = cst; pick = rows.cand[c]; }
         }
     }
-    // ---- general path: one block per workgroup ---------------------------------------------------
-    if (f64 || pcm || j.clip_table || window) return nullptr; // float32 only, no ragged batches, whole signals
+    if (force_k1 == 0) memo = {p, p->L, p->M, v.span, p->T, v.cols, use, switches().fft_no_tiny, dev_now, pick};
+    return pick;
+}
+
+// The row a job runs on, with its geometry: full-size, half-size for few work items, quarter-size for fewer still, then
+// the one-round rule — the geometry cache is asked in that order, and only for the rows the rules reach.
+static const char *fft_choose_row(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, FftRow *row)
+{
+    int n_pairs = 0;
+    const PairEntry *pairs = fft_pairs(&n_pairs);
+    const RatioRows rows = fft_ratio_rows(*p);
+    if (rows.big < 0) return nullptr;
+    const PairEntry *big = &pairs[rows.big], *sml = rows.sml < 0 ? nullptr : &pairs[rows.sml], *tiny = rows.tiny < 0 ? nullptr : &pairs[rows.tiny];
     FftGeom g;
-    if (const char *err = get(0, 0, &g)) return err;
+    if (const char *err = fft_geom_cached(p, 2 + rows.big, big->k, &g)) return err;
+    const PairEntry *use = g.ok ? big : nullptr;
+    if (g.ok && sml) {
+        // few work items (one 60 s clip = 300 pairs): half-size blocks give twice as many,
+        // shorter workgroups, at the price of more overlap
+        const int64_t wgs = fft_pair_items(v.span, g.hop_out, v.cols);
+        // (float64: LDS is 16 bytes per point — the half-size blocks keep four workgroups per CU)
+        // (7056-point blocks: 56 KB of LDS, two workgroups per CU — the 35 KB blocks of the k = 10 geometry keep
+        //  four and win at every size: 44.1k -> 16k VHQ, 8 x 60 s planar 41 vs 68 us, 80 x 60 s 427 vs 638 us)
+        const bool big_lds = big->nt > 384;
+        if (((wgs < 480 || big_lds) && !switches().fft_large_only) || switches().fft_small_only || v.f64) { // measured crossover: ~470 pairs of large blocks
+            FftGeom gs;
+            if (const char *err = fft_geom_cached(p, 2 + rows.sml, sml->k, &gs)) return err;
+            if (gs.ok) { g = gs; use = sml; }
+        }
+    }
+    // Fewer still (a 60 s clip is 612 pairs of half-size blocks on 2048 workgroup slots): the launch is the
+    // latency of one workgroup plus what queues behind it; quarter-size blocks (10 KB of LDS, 32 % overlap)
+    // shorten both: 2 s clip 7.4 -> 6.5 us, 10 s HQ 7.6 -> 6.2 us, 30 s 9.0 -> 7.7 us (60 s: 10.85 vs 10.73 us).
+    if (use == sml && tiny && !switches().fft_large_only && !switches().fft_no_tiny) {
+        // (float32: at 612 pairs — the 60 s clip — the two sizes are within 1 %.  float64: 16 bytes per point, and
+        //  the 20 KB blocks win at every size — 60 s mono 27.1 -> 21.6 us, 64 x 10 s 236 -> 202 us, stereo 60 s 47 -> 37 us)
+        if (v.f64 || fft_pair_items(v.span, g.hop_out, v.cols) <= 500) {
+            FftGeom gt;
+            if (const char *err = fft_geom_cached(p, 2 + rows.tiny, tiny->k, &gt)) return err;
+            if (gt.ok) { g = gt; use = tiny; }
+        }
+    }
+    if (use) {
+        const int pick = fft_one_round_pick(p, j, v, rows, use, use == big);
+        if (pick >= 0 && &pairs[pick] != use) {
+            FftGeom gc;
+            if (const char *err = fft_geom_cached(p, 2 + pick, pairs[pick].k, &gc)) return err;
+            if (gc.ok) { g = gc; use = &pairs[pick]; }
+        }
+    }
+    row->use = use; row->g = g;
+    return nullptr;
+}
+
+// ---- layout decision ----------------------------------------------------------------------------------------
+// Which kernel form a job takes on a geometry, and its launch shape — arithmetic alone (cf. kernels.hip interp_tile_form).
+//   v2ok   unit-stride columns (mono / planar): k_fft_pair2 — buffer loads, staged aligned stores
+//   cp2ok  interleaved data with an even channel count: k_fft_strided2<CP = true>, one (Real, Real) word per frame
+//   st2ok  other strided columns (odd channel counts, channel slices): k_fft_strided2<CP = false>, two blocks per transform
+// None of the three: not the paired kernels' job (the caller's error, or the exact engine).
+struct FftLayout {
+    int32_t chpair = 0, xcd_map = 0;
+    int64_t n_blocks = 0, items = 0, units = 0; // items: work items per channel unit — blocks (channel pairs) or pairs of blocks (single channels)
+    dim3 grid;
+    bool v2ok = false, cp2ok = false, st2ok = false;
+    size_t lds = 0;
+};
+static const char *fft_layout(const hipsoxr_job_t &j, const FftJobView &v, const FftGeom &g, const Switches &sw, FftLayout *out)
+{
+    FftLayout y;
+    y.n_blocks = (v.span + g.hop_out - 1) / g.hop_out;
+    if (y.n_blocks > 2147483647LL) return "job too long for one launch";
+    // interleaved data with an even channel count: pair channels (one (Real, Real) word per frame)
+    const bool cp_layout = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && !sw.fft_no_chpair;
+    // ... when a block's byte offsets fit the kernel's 32-bit operands (buffer loads: element alignment is enough)
+    // (int16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
+    const bool cp_pcm_ok = !v.pcm || (!v.pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
+                                      ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0);
+    const int64_t fstride = std::max(j.in_frame_stride, j.out_frame_stride);
+    const bool cp2 = !v.wide32 && cp_pcm_ok && fft_offsets_fit(g, 1, fstride, v.esz);
+    // (channel pairing rides on the XCD-aware work-item map: decided together, so that a job without the
+    //  map — HIPSOXR_FFT_NO_XCD_MAP, or too many work items — runs unpaired on the strided kernel instead of failing)
+    const int64_t cp_items8 = (y.n_blocks + 7) / 8 * 8;
+    const bool cp_map_ok = j.n_channels > 1 && j.n_clips <= 65535 && cp_items8 * (int64_t)(j.n_channels / 2) <= 2147483647LL && !sw.fft_no_xcd_map;
+    y.chpair = (cp_layout && cp_map_ok && cp2) ? 1 : 0;
+    y.lds = std::max((size_t)std::max(g.N_in, g.N_out) * (v.f64 ? sizeof(double2) : sizeof(float2)), sw.dbg_fft_lds);
+    *out = y;
+    if (v.f64 && y.lds > 160 * 1024) return nullptr; // (no form: the block does not fit LDS in float64)
+    y.items = y.chpair ? y.n_blocks : (y.n_blocks + 1) / 2;
+    const int64_t items8 = (y.items + 7) / 8 * 8;
+    y.units = y.chpair ? j.n_channels / 2 : j.n_channels;
+    y.xcd_map = (j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && j.n_clips <= 65535 &&
+                 items8 * y.units <= 2147483647LL && !sw.fft_no_xcd_map) ? 1 : 0;
+    if (y.chpair && !y.xcd_map) return "internal: channel pairing needs the XCD map"; // (cannot happen: cp_map_ok above)
+    y.grid = y.xcd_map ? dim3((unsigned)(items8 * y.units), j.n_clips, 1) : dim3((unsigned)((y.n_blocks + 1) / 2), (unsigned)v.cols, 1);
+    // (integer samples are staged as the arithmetic's values, up to 7 elements into the run's first granule)
+    const size_t stage_bytes = v.pcm ? 2 * (size_t)g.hop_out * (v.f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * v.esz + 16;
+    y.v2ok = !y.xcd_map && !y.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 && stage_bytes <= y.lds;
+    y.cp2ok = y.chpair && y.xcd_map && cp2;
+    // ... when the byte offsets of a PAIR of blocks fit the 32-bit operands
+    y.st2ok = !v.wide32 && !v.pcm && !y.chpair && !y.v2ok && fft_offsets_fit(g, 2, fstride, v.esz);
+    *out = y;
+    return nullptr;
+}
+
+// ---- kernel arguments ---------------------------------------------------------------------------------------
+// table pointers and geometry members of a launch on `g` (nA / nB / radA / radB: empty — fft_launch_block fills them)
+static void fft_args_geom(FftArgs &a, const FftGeom &g)
+{
+    const FftTabs t = fft_tabs(g);
+    a.WA = g.dev + t.WA; a.WB = g.dev + t.WB; a.P = g.dev + t.P; a.Q = g.dev + t.Q; a.Hs = g.dev + t.Hs;
+    a.WA2 = g.dev + t.WA2; a.WB2 = g.dev + t.WB2; a.Hr = reinterpret_cast<const float *>(g.dev + t.Hr);
+    a.WA2d = g.devd + t.WA2d; a.WB2d = g.devd + t.WB2d; a.Hrd = reinterpret_cast<const double *>(g.devd + t.Hrd);
+    a.TWA = g.twa ? g.dev + g.twa : nullptr; a.TWB = g.twb ? g.dev + g.twb : nullptr;
+    a.A = g.A; a.B = g.B; a.nA = a.nB = 0;
+    for (int i = 0; i < 8; ++i) a.radA[i] = a.radB[i] = 1;
+    a.lead_periods = g.lead_periods; a.hop_periods = g.hop_periods; a.v0 = g.v0; a.hop_out = g.hop_out;
+}
+// ... and the job's part, the same for every form: sample 0 of the columns (window: frame P0 M / P0 L of them.  int16
+// channel pairs: the shift is a whole number of frames, so with the even frame strides cp_pcm_ok asks for, the 4-byte
+// alignment it checks on j.in / j.out holds for the shifted pointers too)
+static FftArgs fft_args(const Plan &p, const hipsoxr_job_t &j, const FftJobView &v, const FftGeom &g, uint32_t ch0)
+{
+    FftArgs a;
+    fft_args_geom(a, g);
+    a.in_lo = j.in_abs0 - v.P0 * p.M; a.in_frames = a.in_lo + j.in_frames; a.out_frames = v.span;
+    a.in = (const char *)j.in - a.in_lo * j.in_frame_stride * (int64_t)v.esz;
+    a.out = (char *)j.out - v.out_lo * j.out_frame_stride * (int64_t)v.esz;
+    a.out_lo = v.out_lo; a.out_abs0 = v.P0 * p.L;
+    a.L = p.L; a.M = p.M;
+    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
+    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
+    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.clip_tab = j.clip_table_dev;
+    a.clip_counter = v.pcm ? j.clip_counter : nullptr; a.dither = j.dither; a.seed = j.dither_seed; a.ch0 = ch0;
+    a.chpair = 0; a.xcd_map = 0; a.pairs_per_col = 0; a.trace = nullptr;
+    return a;
+}
+
+// ---- one launcher per form ------------------------------------------------------------------------------------
+// (-DFFT2_TRACE: per-wave time stamps of the paired kernels, dumped synchronously behind the launch)
+#ifdef FFT2_TRACE
+static const char *fft_trace_begin(FftArgs &a, dim3 grid, unsigned nt, size_t *n)
+{
+    *n = 0;
+    if (!switches().dbg_trace) return nullptr;
+    *n = (size_t)grid.x * grid.y * (nt / 64) * 16;
+    HIP_TRY(hipMalloc((void **)&a.trace, *n * 8));
+    HIP_TRY(hipMemset(a.trace, 0, *n * 8));
+    return nullptr;
+}
+static const char *fft_trace_dump(const FftArgs &a, size_t n, void *stream)
+{
+    if (!a.trace) return nullptr;
+    std::vector<unsigned long long> h(n);
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    HIP_TRY(hipMemcpy(h.data(), a.trace, n * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(switches().dbg_trace, "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+    (void)hipFree(a.trace);
+    return nullptr;
+}
+#else
+static const char *fft_trace_begin(FftArgs &, dim3, unsigned, size_t *) { return nullptr; }
+static const char *fft_trace_dump(const FftArgs &, size_t, void *) { return nullptr; }
+#endif
+
+// Throughput form (fftwave.hip): one wave per pair of 24-period blocks, two register passes per transform — float32
+// unit-stride columns with enough pairs to fill the chip's 2048 wave slots four times over (below that the last, partly
+// filled round costs more than the form gains; and a single pair's latency is longer than on the 6-wave workgroups of
+// k_fft_pair2).  Never a window, and never a column with frames missing in FRONT — a.in_lo > 0, data-dependent front
+// extension: k_fft_wave's front guard covers the lead-in of block 0 only.  *handled stays false: not this form's job.
+static const char *fft_try_wave(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, const FftLayout &lay, FftArgs a, void *stream, bool *handled)
+{
+    FftWaveKernel wk;
+    if (!(lay.v2ok && !v.f64 && !v.pcm && !v.window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk))) return nullptr;
+    // (the job size first, from the kernel's own constants: its geometry — a host DFT of the filter and two
+    //  device allocations — is built only for a job that can take it; 48k -> 44.1k never does)
+    const int64_t pairs_w = ((j.out_frames + wk.hop - 1) / wk.hop + 1) / 2;
+    const int64_t wave_min = switches().dbg_wave_min ? switches().dbg_wave_min : wk.min_pairs;
+    FftGeom gw;
+    if (pairs_w * (int64_t)v.cols >= wave_min && pairs_w * (int64_t)v.cols <= 2147483000LL) // (item numbers are 32-bit; a larger job stays on k_fft_pair2)
+        if (const char *err = fft_geom_cached(p, 1000 + wk.k, wk.k, &gw)) return err;
+    if (!(gw.ok && gw.v0 == wk.v0 && gw.hop_out == wk.hop && gw.hop_periods == wk.hop_periods)) return nullptr;
+    fft_args_geom(a, gw);
+    if (const char *e = fft_wave_launch(wk, a, (unsigned)pairs_w, (unsigned)v.cols, stream)) return e;
+    if (switches().dbg_launch_log)
+        fft_launch_log("wave", p->L, p->M, wk.k, -1, v.kind, 64, 0, dim3((unsigned)pairs_w, (unsigned)v.cols, 1), gw.hop_out, 2 * pairs_w, v.window);
+    *handled = true;
+    return nullptr;
+}
+
+static const char *fft_launch_paired(const PairEntry &e, const FftGeom &g, const FftJobView &v, const FftLayout &lay, FftArgs a, void *stream, bool *handled)
+{
+    void (*kern)(FftArgs) = nullptr;
+    if (lay.v2ok) kern = v.pcm ? (v.pcm32 ? e.kern2i32 : e.kern2i16) : v.io64 ? e.kern2d : v.wide32 ? e.kern2fd : e.kern2;
+    else kern = v.pcm ? e.kcpi16 : lay.cp2ok ? (v.f64 ? e.kcpd : e.kcp) : (v.f64 ? e.kstd : e.kst); // (pcm: cp2ok — st2ok wants floats)
+    if (!kern) return "internal: a float32-only block size was chosen for another kind of job"; // (cannot happen: plain_cols of fft_one_round_pick)
+    if (const char *err = ensure_dyn_lds((const void *)kern, lay.lds)) return err;
+    size_t trace_n = 0;
+    if (const char *err = fft_trace_begin(a, lay.grid, e.nt, &trace_n)) return err;
+    hipLaunchKernelGGL(kern, lay.grid, dim3(e.nt), lay.lds, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log)
+        fft_launch_log(lay.v2ok ? "pair2" : lay.cp2ok ? "strided2_cp" : "strided2_st", e.L, e.M, e.k, e.small, v.kind, e.nt, lay.lds, lay.grid, g.hop_out, lay.n_blocks, v.window);
+    if (const char *err = fft_trace_dump(a, trace_n, stream)) return err;
+    *handled = true;
+    return nullptr;
+}
+
+// A job on a row of the table: the wave form where it wins, else the row's paired kernel (*handled stays false: no form)
+static const char *fft_launch_row(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, const FftRow &row, void *stream, uint32_t ch0, bool *handled)
+{
+    if (v.out_lo >= row.g.hop_out) return "internal: the job window starts beyond the first block"; // (cannot happen: out_lo < L <= hop_out)
+    FftLayout lay;
+    if (const char *err = fft_layout(j, v, row.g, switches(), &lay)) return err;
+    FftArgs a = fft_args(*p, j, v, row.g, ch0);
+    a.chpair = lay.chpair; a.xcd_map = lay.xcd_map; a.pairs_per_col = lay.items;
+    if (const char *err = fft_try_wave(p, j, v, lay, a, stream, handled)) return err;
+    if (*handled) return nullptr;
+    if (!lay.v2ok && !lay.cp2ok && !lay.st2ok) return nullptr;
+    if (j.clip_table && !lay.v2ok) return nullptr; // ragged batches: the unit-stride kernel reads its clip's row; nothing else does
+    return fft_launch_paired(*row.use, row.g, v, lay, a, stream, handled);
+}
+
+// General path: one block per workgroup — float32 whole signals of any 7-smooth plan, no ragged batches
+static const char *fft_launch_block(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, void *stream, bool *handled)
+{
+    if (v.f64 || v.pcm || j.clip_table || v.window) return nullptr;
+    FftGeom g;
+    if (const char *err = fft_geom_cached(p, 0, 0, &g)) return err;
     if (g.ok) {
         const int64_t wgs = ((j.out_frames + g.hop_out - 1) / g.hop_out) * (int64_t)j.n_clips * j.n_channels;
         if ((wgs < 8 * 256 && !switches().fft_large_only) || switches().fft_small_only) {
             FftGeom gs;
-            if (const char *err = get(1, 0, &gs)) return err;
+            if (const char *err = fft_geom_cached(p, 1, 0, &gs)) return err;
             if (gs.ok && gs.k < g.k) g = gs;
         }
     }
     if (!g.ok) return nullptr;
-    FftArgs a;
-    a.in = (const char *)j.in - j.in_abs0 * j.in_frame_stride * 4; a.out = j.out;
-    a.WA = g.dev; a.WB = a.WA + g.A; a.P = a.WB + g.B; a.Q = a.P + (g.A + 1); a.Hs = a.Q + g.B;
-    a.WA2 = a.Hs + (g.B + 1); a.WB2 = a.WA2 + g.N_in;
-    a.Hr = reinterpret_cast<const float *>(a.WB2 + g.N_out); a.trace = nullptr;
-    a.WA2d = a.WB2d = nullptr; a.Hrd = nullptr; a.clip_tab = nullptr;
-    a.chpair = 0; a.pairs_per_col = 0; a.xcd_map = 0;
-    a.clip_counter = nullptr; a.dither = a.seed = a.ch0 = 0;
-    a.out_lo = a.out_abs0 = 0; a.TWA = a.TWB = nullptr;
-    a.A = g.A; a.B = g.B; a.nA = g.nA; a.nB = g.nB;
+    FftArgs a = fft_args(*p, j, v, g, 0);
+    a.nA = g.nA; a.nB = g.nB;
     for (int i = 0; i < 8; ++i) { a.radA[i] = g.radA[i]; a.radB[i] = g.radB[i]; }
-    a.L = p->L; a.M = p->M;
-    a.lead_periods = g.lead_periods; a.hop_periods = g.hop_periods; a.v0 = g.v0; a.hop_out = g.hop_out;
-    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
-    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-    a.in_lo = j.in_abs0; a.in_frames = j.in_abs0 + j.in_frames; a.out_frames = j.out_frames;
     const int64_t n_blocks = (j.out_frames + g.hop_out - 1) / g.hop_out;
-    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-    if (cols > 65535) return "too many (clip, channel) columns for one launch (max 65535)";
+    if (v.cols > 65535) return "too many (clip, channel) columns for one launch (max 65535)";
     if (n_blocks > 2147483647LL) return "job too long for one launch";
-    if (const char *e = ensure_dyn_lds((const void *)k_fft_block, std::max(g.lds_bytes, switches().dbg_fft_lds))) return e;
-    const size_t dbg_lds = switches().dbg_fft_lds;
-    hipLaunchKernelGGL(k_fft_block, dim3((unsigned)n_blocks, (unsigned)cols, 1), dim3(256), std::max(g.lds_bytes, dbg_lds),
-                       (hipStream_t)stream, a);
+    const size_t lds = std::max(g.lds_bytes, switches().dbg_fft_lds);
+    const dim3 grid((unsigned)n_blocks, (unsigned)v.cols, 1);
+    if (const char *e = ensure_dyn_lds((const void *)k_fft_block, lds)) return e;
+    hipLaunchKernelGGL(k_fft_block, grid, dim3(256), lds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
-    if (switches().dbg_launch_log)
-        fft_launch_log("block", p->L, p->M, g.k, -1, kind, 256, std::max(g.lds_bytes, dbg_lds), dim3((unsigned)n_blocks, (unsigned)cols, 1), g.hop_out, n_blocks, window);
+    if (switches().dbg_launch_log) fft_launch_log("block", p->L, p->M, g.k, -1, v.kind, 256, lds, grid, g.hop_out, n_blocks, v.window);
     *handled = true;
     return nullptr;
+}
+
+// ---- dispatcher ---------------------------------------------------------------------------------------------
+// The forms in order: the wave form and the paired kernels on a row of the table, else k_fft_block.  float64 arithmetic
+// and integer samples: the paired kernels only — else the exact engine (integer samples: the caller's error).
+static const char *launch_fft_impl(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0, bool window)
+{
+    *handled = false;
+    const FftJobView v = fft_job_view(*p, j, window);
+    const bool paired = !switches().fft_no_pair && v.cols <= 65535;
+    FftRow row;
+    const char *err = nullptr;
+    if (paired) err = fft_choose_row(p, j, v, &row);
+    if (row.use) err = fft_launch_row(p, j, v, row, stream, ch0, handled);
+    else if (!err && (paired || (!v.f64 && !v.pcm))) err = fft_launch_block(p, j, v, stream, handled);
+    if (!*handled && switches().dbg_launch_log) // leaving without a launch: the log says so, with the row chosen so far
+        fft_launch_log("none", p->L, p->M, row.use ? row.use->k : 0, row.use ? row.use->small : -1, v.kind, 0, 0, dim3(0, 0, 0), 0, 0, window);
+    return err;
 }
 
 const char *launch_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled, uint32_t ch0)

@@ -23,10 +23,10 @@ ROOT = os.path.dirname(HERE)
 FFT_SRC = os.path.join(ROOT, "python-soxr_amd", "csrc", "fft.hip")
 FLOOR_JSON = os.path.join(HERE, "golden", "fft_table_floor.json")
 
-# PairEntry's kernel pointers, in the struct's order (launch_fft_impl picks a field by layout, element type and selector)
+# PairEntry's kernel pointers, in the struct's order (fft_launch_paired picks a field by layout, element type and selector)
 INSTANCES = (("pair2", "f32"), ("pair2", "f64"), ("pair2", "f32on64"), ("strided2_cp", "f32"), ("strided2_cp", "f64"),
              ("strided2_st", "f32"), ("strided2_st", "f64"), ("pair2", "i16"), ("pair2", "i32"), ("strided2_cp", "i16"))
-WIDE_KINDS = ("f64", "f32on64", "i32")          # float64 arithmetic (`f64` in launch_fft_impl)
+WIDE_KINDS = ("f64", "f32on64", "i32")          # float64 arithmetic (`f64` of FftJobView)
 QUALITIES = ("VHQ", "HQ")
 FFT, FFT_F64, FFT_PCM = 5, 8, 9                 # hipsoxr_kernel_t
 
@@ -125,14 +125,14 @@ def rates_of(L, M):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# launch_fft_impl's arithmetic, restated
+# the arithmetic of fft_kept_run (csrc/fft.hip), restated
 def lead_periods(L, M, T):
     disc = ((T // 2 + 2) * L + M - 1) // M
     return (disc + L - 1) // L
 
 
 def hop_out(L, M, T, k):
-    """fft_geometry(force_k = k) / fft_hop_out: outputs a block of k periods keeps; 0: the row is not admissible for T taps."""
+    """fft_geometry(force_k = k) / fft_hop_out (both through fft_kept_run): outputs a block of k periods keeps; 0: the row is not admissible for T taps."""
     if M * k // 2 > 4096 or L * k // 2 > 4096:
         return 0
     disc = ((T // 2 + 2) * L + M - 1) // M
@@ -158,7 +158,7 @@ def children(rows):
 
 
 def pick_row(ratio_rows, T, env, wide, f32_unit, macros):
-    """The row launch_fft_impl chooses for a job of a few work items (far below every size threshold) of this ratio, under
+    """The row fft_choose_row chooses for a job of a few work items (far below every size threshold) of this ratio, under
     the switches of `env`; None: no paired kernel.  wide: float64 arithmetic.  f32_unit: float32 unit-stride columns."""
     large, small_only, no_tiny = ("HIPSOXR_FFT_LARGE_ONLY" in env), ("HIPSOXR_FFT_SMALL_ONLY" in env), ("HIPSOXR_FFT_NO_TINY" in env)
     force_k = int(env.get("HIPSOXR_DEBUG_FFT_K", 0))
@@ -199,7 +199,7 @@ _FULL_SIZE_ROWS_OF_RATIOS_WITH_A_HALF_SIZE_ROW = ((147, 160, 32, 0), (160, 147, 
                                                   (1, 2, 2048, 0), (2, 1, 2048, 0), (1, 3, 1792, 0), (3, 1, 1792, 0),
                                                   (2, 3, 1792, 0), (3, 2, 1792, 0))
 UNREACHABLE = {(row, inst): "float64 arithmetic never stays on the full-size row of a ratio that has a half-size one: "
-                            "`(...) || switches().fft_small_only || f64` in launch_fft_impl takes `sml` whenever its geometry "
+                            "`(...) || switches().fft_small_only || v.f64` in fft_choose_row takes `sml` whenever its geometry "
                             "is admissible (gs.ok), HIPSOXR_FFT_LARGE_ONLY set or not"
                for row in _FULL_SIZE_ROWS_OF_RATIOS_WITH_A_HALF_SIZE_ROW for inst in INSTANCES if inst[1] in WIDE_KINDS}
 

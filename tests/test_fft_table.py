@@ -58,7 +58,7 @@ def test_every_instance_has_a_case_or_a_reason(table, plan):
     assert len(tp.children(rows)) <= 6
     keys = {tp.row_key(r) for r in rows}
     for (row, inst), why in tp.UNREACHABLE.items():
-        assert row in keys and "launch_fft_impl" in why, (row, inst)
+        assert row in keys and "fft_choose_row" in why, (row, inst)
     census = {}
     for r in rows:
         for inst in tp.instances_of(r, macros):
