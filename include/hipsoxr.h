@@ -133,12 +133,12 @@ typedef enum {
 /* Selector of hipsoxr_run_device_adjoint alone (job.kernel there; the forward entries refuse it by name), numbered on from
  * hipsoxr_kernel_t. */
 typedef enum {
-    HIPSOXR_KERNEL_ADJOINT = 10 /* hipsoxr_run_device_adjoint only: the exact engine's transposed operator for EVERY
+    HIPSOXR_KERNEL_ADJOINT = 10 /* hipsoxr_run_device_adjoint (and its _ragged form) only: the exact engine's transposed operator for EVERY
                                   constant-rate plan.  On an exact-bank plan it runs what AUTO runs there, bit for bit; on an
                                   interpolated-phase plan (hipsoxr_plan_info_t::interpolated != 0, which AUTO and EXACT
                                   refuse) the gather-form adjoint on the plan's own interpolation table — the coefficients
                                   the forward's HIPSOXR_KERNEL_EXACT multiplies by, to the bit.  float32 / float64, whole
-                                  signals, no clip_table, constant-rate plans (not hipsoxr_plan_create_vr's); refused by
+                                  signals, a clip_table on the _ragged entry alone, constant-rate plans (not hipsoxr_plan_create_vr's); refused by
                                   name otherwise, and on hipsoxr_run_device. */
 } hipsoxr_adjoint_kernel_t;
 
@@ -225,7 +225,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
@@ -241,6 +241,20 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *, const hipsoxr_j
  * another path.  kernel = HIPSOXR_KERNEL_ADJOINT: the same on every constant-rate plan, interpolated-phase plans included
  * (A is then the forward HIPSOXR_KERNEL_EXACT computes from the plan's interpolation table).  Zero frames, clips or channels: success, nothing launched.  Asynchronous on `hip_stream`. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
+/* The same operator over a RAGGED batch — clips of unequal length, ONE launch: the gradient of a hipsoxr_run_device job that
+ * has a clip_table.  The job is read in the adjoint's direction as above, and clip_table is REQUIRED: n_clips host rows
+ * { gy offset, n_y, gx offset, n_x }, offsets in elements from `in` / `out` (the clip strides are ignored), n_y[c] <=
+ * hipsoxr_plan_out_len(plan, n_x[c]); in_frames / out_frames of the job are the LARGEST per-clip n_y / n_x.  clip_table_dev
+ * follows the forward's rule: NULL = the host table is uploaded in stream order on every call, a caller's device copy is
+ * used as it is and must equal the host table.  Every element of every clip's gx[0, n_x[c]) is written (zeros where
+ * n_y[c] == 0), nothing outside it — not the elements between packed clips either.  Each clip has, bit for bit, the result
+ * of the same clip run alone through hipsoxr_run_device_adjoint (finite cotangents; a non-finite gy[k] reaches, inside its
+ * own clip only, what it reaches in the kernel form the ragged launch took).  Selectors: HIPSOXR_KERNEL_AUTO, _EXACT (exact-bank
+ * plans) and HIPSOXR_KERNEL_ADJOINT (every constant-rate plan).  Refused by name, before anything is launched: a NULL
+ * clip_table, a negative offset or count, a row above the job's in_frames / out_frames, n_y[c] above the plan's output length
+ * for n_x[c], integer element types, in_abs0 / out_k0 != 0, variable-rate plans, any other selector.  No clips, no channels
+ * or out_frames == 0: success, nothing launched.  Asynchronous on `hip_stream`. */
+HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
 
 /* ---- stream: the soxr_t counterpart (host pointers, state carried across calls) ----------- */
 HIPSOXR_API hipsoxr_error_t hipsoxr_stream_create(double in_rate, double out_rate,

@@ -61,6 +61,19 @@
 //                 REACH: 0 <= j < T is exactly a - T/2 <= q_k <= a + T/2 - 1, the true support of gy[k]: a lane never
 //                 multiplies outside its own [k_lo, k_hi], there is no padding and no 0 * inf.  A non-finite gy[k] reaches
 //                 the gx[a] of its true support and nothing else — tighter than the two exact-bank kernels above.
+//
+// RAGGED batches (hipsoxr_run_device_adjoint_ragged): every kernel has a second instantiation, `bool RAGGED`, that serves
+// clips of unequal length in ONE launch.  A column's clip reads its row { gy offset, n_y, gx offset, n_x } from a device copy
+// of the job's clip table; the row stands where the equal-length form has clip * ics, a.n_y, clip * ocs and a.n_x.  The
+// grid's frame axis is sized by the LONGEST clip, and a workgroup (k_adj_gather: a lane) whose tile, periods or frame start
+// at or behind its clip's n_x does nothing for that column — a decision that is uniform over the workgroup, so no barrier is
+// ever met by part of one.  Every element of every clip's gx[0, n_x[c]) is written (zeros where n_y[c] == 0) and nothing
+// else: not the elements between packed clips.  All offsets are 64-bit.  The equal-length instantiations are the code they
+// were.  FORM: the tiled kernel when the plan has tile tables and the LONGEST clip has at least kAdjMinPeriods * Mc frames —
+// the short clips of such a launch run on it too, it is correct at any length — else the lane-per-element kernel.  By
+// ARITHMETIC above each clip has, for finite cotangents, the bits of the same clip run alone, whichever form either took.
+// REACH of a non-finite gy[k] of clip c: inside clip c only, the interval above of the form THE RAGGED LAUNCH took (a short
+// clip in a tiled launch has k_adj_tile's reach, although alone it would run k_adj_gather); k_adj_interp: the true support.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -100,8 +113,15 @@ struct AdjArgs {
     int32_t inter;        // k_adj_gather: channel index fastest (interleaved frames)
     uint32_t n_clips, n_channels, n_groups;
     int64_t ics, ifs, ichs, ocs, ofs, ochs;
-    int64_t n_y, n_x;
+    int64_t n_y, n_x;     // RAGGED: the largest per-clip values (n_x sizes the grid's frame axis)
 };
+// The RAGGED instantiations take the table behind the same arguments (the equal-length kernels keep their argument block).
+struct AdjRaggedArgs : AdjArgs {
+    const int64_t *rows;  // [n_clips][4] = gy offset, n_y, gx offset, n_x (device copy of hipsoxr_job_t::clip_table):
+                          // a row replaces clip * ics, a.n_y, clip * ocs, a.n_x
+};
+template <bool RAGGED> struct AdjArgsOf { typedef AdjArgs type; };
+template <> struct AdjArgsOf<true> { typedef AdjRaggedArgs type; };
 
 __host__ __device__ static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; } // b > 0
 __host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
@@ -112,8 +132,10 @@ __device__ __forceinline__ double fma_r(double a, double b, double c) { return _
 // ---------------------------------------------------------------------------------------------
 // k_adj_gather
 // ---------------------------------------------------------------------------------------------
-template <typename Real>
-__global__ void __launch_bounds__(256) k_adj_gather(AdjArgs a)
+// RAGGED: the (frame, channel) of a lane is decomposed with the LONGEST clip's n_x (a.n_x); the clip loop strides gridDim.y,
+// so one lane meets clips of different lengths and asks `fr < n_x[clip]` for each.
+template <typename Real, bool RAGGED>
+__global__ void __launch_bounds__(256) k_adj_gather(typename AdjArgsOf<RAGGED>::type a)
 {
     const int64_t per_clip = a.n_x * (int64_t)a.n_channels;
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -126,14 +148,18 @@ __global__ void __launch_bounds__(256) k_adj_gather(AdjArgs a)
     const int64_t k0 = q * a.L + a.d_lo[s];
     const Real *c = (const Real *)a.ct + s;
     for (uint32_t clip = blockIdx.y; clip < a.n_clips; clip += gridDim.y) {
-        const Real *g = (const Real *)a.gy + (int64_t)clip * a.ics + ch * a.ichs;
+        const int64_t *row = nullptr; // the clip's row; the equal-length form has none
+        if constexpr (RAGGED) row = a.rows + 4 * (int64_t)clip;
+        if (RAGGED && fr >= row[3]) continue;
+        const int64_t n_y = RAGGED ? row[1] : a.n_y;
+        const Real *g = (const Real *)a.gy + (RAGGED ? row[0] : (int64_t)clip * a.ics) + ch * a.ichs;
         Real acc = 0;
         for (int32_t i = 0; i < a.Tt; ++i) {
             const int64_t k = k0 + i;
-            const Real v = (k >= 0 && k < a.n_y) ? g[k * a.ifs] : (Real)0;
+            const Real v = (k >= 0 && k < n_y) ? g[k * a.ifs] : (Real)0;
             acc = fma_r(c[(int64_t)i * a.M], v, acc);
         }
-        ((Real *)a.gx)[(int64_t)clip * a.ocs + fr * a.ofs + ch * a.ochs] = acc;
+        ((Real *)a.gx)[(RAGGED ? row[2] : (int64_t)clip * a.ocs) + fr * a.ofs + ch * a.ochs] = acc;
     }
 }
 
@@ -145,8 +171,11 @@ __global__ void __launch_bounds__(256) k_adj_gather(AdjArgs a)
 // [x pb Lc + dmin, + x_count) of cg channels, frame n of it at LDS element (n + pad (n / Lc)) cg + channel: rows of
 // Lc + pad frames — an odd count, so that the lanes of a wave (stride one row) fall on different banks.  Phase tile st
 // (phases s = 16 st .. 16 st + 15) reads slab frames e0[st] + ii (ii < I) of its lane's period, coefficient tab[st][ii][s].
-template <typename Real>
-__global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
+// RAGGED: a workgroup whose periods start at or behind its clip's n_x skips the column — a workgroup-uniform decision
+// (blockIdx.x and the clip's row) — so the barrier in front of staging fires only once an earlier column of this workgroup
+// has staged a slab.  A clip shorter than 4 Mc frames is served like any other: the kernel is correct at any length.
+template <typename Real, bool RAGGED>
+__global__ void __launch_bounds__(1024) k_adj_tile(typename AdjArgsOf<RAGGED>::type a)
 {
     constexpr int RS = kAdjRS;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -163,14 +192,22 @@ __global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
     const bool live = per < pb;
     const int32_t rows = (a.x_count + Lc - 1) / Lc;
     const int32_t row_elems = Lc * cg;
+    [[maybe_unused]] bool staged = false; // RAGGED: an earlier column of this workgroup staged a slab (uniform)
 
     for (uint32_t y = blockIdx.y; y < a.n_clips * a.n_groups; y += gridDim.y) {
         // (run-time division goes through the vector ALU; readfirstlane keeps the results on the scalar side)
         const uint32_t clip = __builtin_amdgcn_readfirstlane(y / a.n_groups);
         const uint32_t ch0 = __builtin_amdgcn_readfirstlane((y - clip * a.n_groups) * (uint32_t)cg);
         const int32_t ncg = (int32_t)min((uint32_t)cg, a.n_channels - ch0); // channels of this group that exist
-        const Real *g = (const Real *)a.gy + (int64_t)clip * a.ics + (int64_t)ch0 * a.ichs;
-        if (y != blockIdx.y) __syncthreads(); // the slab of the column before is still being read
+        const int64_t *row = nullptr; // the clip's row (clip is wave-uniform: scalar loads); the equal-length form has none
+        if constexpr (RAGGED) row = a.rows + 4 * (int64_t)clip;
+        if constexpr (RAGGED)
+            if (q0 * a.Mc >= row[3]) continue; // nothing of this clip in this workgroup's periods
+        const Real *g = (const Real *)a.gy + (RAGGED ? row[0] : (int64_t)clip * a.ics) + (int64_t)ch0 * a.ichs;
+        if constexpr (RAGGED) {
+            if (staged) __syncthreads(); // the slab of the column before — the last one not skipped — is still being read
+            staged = true;
+        } else if (y != blockIdx.y) __syncthreads(); // the slab of the column before is still being read
 
         // stage: a wave per slab row, lanes along the row's (frame, channel) elements — whole frames of an interleaved
         // tensor are read as they lie in memory
@@ -181,14 +218,14 @@ __global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
                 const int32_t n = r * Lc + j;
                 if (n < a.x_count) {
                     const int64_t f = g0 + n;
-                    dst[e] = (cc < ncg && f >= 0 && f < a.n_y) ? g[f * a.ifs + (int64_t)cc * a.ichs] : (Real)0;
+                    dst[e] = (cc < ncg && f >= 0 && f < (RAGGED ? row[1] : a.n_y)) ? g[f * a.ifs + (int64_t)cc * a.ichs] : (Real)0;
                 }
             }
         }
         __syncthreads();
 
         const Real *xl = xs + (size_t)((live ? per : 0) * (Lc + pad) * cg + c); // this lane's (period, channel)
-        Real *const go = (Real *)a.gx + (int64_t)clip * a.ocs + (int64_t)(ch0 + c) * a.ochs;
+        Real *const go = (Real *)a.gx + (RAGGED ? row[2] : (int64_t)clip * a.ocs) + (int64_t)(ch0 + c) * a.ochs;
         const int64_t a0 = (q0 + per) * a.Mc; // first input frame of this lane's period
         const bool store = live && c < ncg;
 
@@ -224,7 +261,7 @@ __global__ void __launch_bounds__(1024) k_adj_tile(AdjArgs a)
 #pragma unroll
             for (int rr = 0; rr < RS; ++rr) {
                 const int64_t fr = a0 + s0 + rr;
-                if (store && s0 + rr < Mc && fr < a.n_x) go[fr * a.ofs] = acc[rr];
+                if (store && s0 + rr < Mc && fr < (RAGGED ? row[3] : a.n_x)) go[fr * a.ofs] = acc[rr];
             }
         }
     }
@@ -245,8 +282,11 @@ struct AdjInterpArgs {
     uint64_t n_cols; // clips x channels
     uint32_t n_channels;
     int64_t ics, ifs, ichs, ocs, ofs, ochs;
-    int64_t n_y, n_x;
+    int64_t n_y, n_x;    // RAGGED: the largest per-clip values
 };
+struct AdjInterpRaggedArgs : AdjInterpArgs { const int64_t *rows; }; // as AdjRaggedArgs::rows
+template <bool RAGGED> struct AdjInterpArgsOf { typedef AdjInterpArgs type; };
+template <> struct AdjInterpArgsOf<true> { typedef AdjInterpRaggedArgs type; };
 
 template <typename Real> struct AdjVec4;
 template <> struct AdjVec4<float> { typedef float4 type; };
@@ -256,8 +296,11 @@ template <typename Real> struct AdjRec { int32_t dq, row; Real xx, g; };
 
 // UNION: a wave walks the union of its lanes' k ranges (wave-uniform k: one table row per step, neighbouring records);
 // else every lane walks its own [k_lo, k_hi] (no idle steps, 64 rows per step).  Same terms in the same order either way.
-template <typename Real, bool UNION>
-__global__ void __launch_bounds__(kAdjIW) k_adj_interp(AdjInterpArgs a)
+// RAGGED: the tile's frame and k ranges and the walks depend on the clip's n_x and n_y, so they are found per column; a
+// tile at or behind its clip's n_x skips the column (workgroup-uniform: no barrier is met by some threads only), and a clip
+// with n_y == 0 has an empty k range — no chunk, zeros written to all its frames.
+template <typename Real, bool UNION, bool RAGGED>
+__global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<RAGGED>::type a)
 {
     typedef typename AdjVec4<Real>::type V4;
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
@@ -265,21 +308,35 @@ __global__ void __launch_bounds__(kAdjIW) k_adj_interp(AdjInterpArgs a)
     const int32_t T = a.T, H = T / 2;
     const int tid = (int)threadIdx.x;
     const int64_t a0 = (int64_t)blockIdx.x * kAdjIW, fr = a0 + tid;
-    const int64_t a_end = a0 + kAdjIW < a.n_x ? a0 + kAdjIW : a.n_x; // the tile's frames: [a0, a_end), never empty
     auto k_lo = [&](int64_t f) { const int64_t k = ceil_div((f - H) * a.L, a.M); return k > 0 ? k : (int64_t)0; };
-    auto k_hi = [&](int64_t f) { const int64_t k = ceil_div((f + H) * a.L, a.M); return (k < a.n_y ? k : a.n_y) - 1; };
-    const int64_t k_first = k_lo(a0), k_end = k_hi(a_end - 1) + 1; // the tile reads gy[k_first, k_end)
-    // this wave's (UNION) or this lane's walk, relative to k_first: [wl, wh], empty behind the signal's end
-    const int64_t f0 = UNION ? a0 + (tid & ~63) : fr, f1 = UNION ? (f0 + 63 < a_end ? f0 + 63 : a_end - 1) : fr;
+    auto k_hi = [&](int64_t f, int64_t n_y) { const int64_t k = ceil_div((f + H) * a.L, a.M); return (k < n_y ? k : n_y) - 1; };
+    // the tile's share of a clip of n_x frames and n_y cotangent samples (equal lengths: found once, here; RAGGED: per column)
+    int64_t k_first = 0, k_end = 0;
     int32_t wl = 0, wh = -1;
-    if (f0 < a_end) { wl = (int32_t)(k_lo(f0) - k_first); wh = (int32_t)(k_hi(f1) - k_first); }
-    if (UNION) { wl = __builtin_amdgcn_readfirstlane(wl); wh = __builtin_amdgcn_readfirstlane(wh); }
+    auto geo = [&](int64_t n_y, int64_t n_x) {
+        const int64_t a_end = a0 + kAdjIW < n_x ? a0 + kAdjIW : n_x; // the tile's frames: [a0, a_end), never empty
+        k_first = k_lo(a0); k_end = k_hi(a_end - 1, n_y) + 1;        // the tile reads gy[k_first, k_end)
+        // this wave's (UNION) or this lane's walk, relative to k_first: [wl, wh], empty behind the signal's end
+        const int64_t f0 = UNION ? a0 + (tid & ~63) : fr, f1 = UNION ? (f0 + 63 < a_end ? f0 + 63 : a_end - 1) : fr;
+        int32_t l = 0, h = -1;
+        if (f0 < a_end) { l = (int32_t)(k_lo(f0) - k_first); h = (int32_t)(k_hi(f1, n_y) - k_first); }
+        if (UNION) { l = __builtin_amdgcn_readfirstlane(l); h = __builtin_amdgcn_readfirstlane(h); }
+        wl = l; wh = h;
+    };
+    if (!RAGGED) geo(a.n_y, a.n_x);
     const int32_t jb = tid + H - 1; // tap of gy[k] in this lane's frame: fr - q_k + H - 1 = jb - (q_k - a0)
     const V4 *tab = (const V4 *)a.tab;
 
     for (uint64_t col = blockIdx.y; col < a.n_cols; col += gridDim.y) {
         const int64_t clip = (int64_t)(col / a.n_channels), ch = (int64_t)(col - (uint64_t)clip * a.n_channels);
-        const Real *g = (const Real *)a.gy + clip * a.ics + ch * a.ichs;
+        const int64_t *row = nullptr; // the clip's row; the equal-length form has none
+        if constexpr (RAGGED) row = a.rows + 4 * clip;
+        const int64_t n_x = RAGGED ? row[3] : a.n_x;
+        if (RAGGED) {
+            if (a0 >= n_x) continue; // nothing of this clip in this tile
+            geo(row[1], n_x);
+        }
+        const Real *g = (const Real *)a.gy + (RAGGED ? row[0] : clip * a.ics) + ch * a.ichs;
         Real acc = 0;
         for (int64_t kc = k_first; kc < k_end; kc += kAdjIC) {
             __syncthreads(); // the chunk before is still being read
@@ -310,7 +367,7 @@ __global__ void __launch_bounds__(kAdjIW) k_adj_interp(AdjInterpArgs a)
                 acc = mine ? fma_r(c, rc.g, acc) : acc;
             }
         }
-        if (fr < a.n_x) ((Real *)a.gx)[clip * a.ocs + fr * a.ofs + ch * a.ochs] = acc;
+        if (fr < n_x) ((Real *)a.gx)[(RAGGED ? row[2] : clip * a.ocs) + fr * a.ofs + ch * a.ochs] = acc;
     }
 }
 
@@ -449,20 +506,25 @@ static const char *adj_ensure(Plan *p, AdjBank **out)
 
 // HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per launch, in the style of fft.hip's fft_launch_log — what
 // tests/test_gpu_adjoint_forms.py reads the launch form from.
-static void adj_launch_log(const char *kernel, size_t width, const AdjBank &b, int lanes, size_t lds, const AdjArgs &a, dim3 grid, unsigned nt)
+// A ragged launch (a.rows) appends " ragged=<n_clips>"; an equal-length launch writes its line as it always did.
+static void adj_launch_log(const char *kernel, size_t width, const AdjBank &b, int lanes, size_t lds, const AdjRaggedArgs &a, dim3 grid, unsigned nt)
 {
     FILE *f = fopen(switches().dbg_launch_log, "a");
     if (!f) return;
-    fprintf(f, "kernel=%s width=%zu L=%lld M=%lld lanes=%d lds=%zu cg=%d pb=%d grid=%ux%ux%u block=%u n_st=%d\n", kernel, width,
+    fprintf(f, "kernel=%s width=%zu L=%lld M=%lld lanes=%d lds=%zu cg=%d pb=%d grid=%ux%ux%u block=%u n_st=%d", kernel, width,
             (long long)b.L, (long long)b.M, lanes, lds, a.cg, a.pb, grid.x, grid.y, grid.z, nt, b.n_st);
+    if (a.rows) fprintf(f, " ragged=%u", a.n_clips);
+    fputc('\n', f);
     fclose(f);
 }
 
+// rows: the device copy of a ragged job's clip table, or NULL (equal-length clips).  A ragged job's in_frames / out_frames
+// are its largest clip's: the form is chosen by, and the grid's frame axis sized by, the LONGEST clip.
 template <typename Real>
-static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st)
+static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows = nullptr)
 {
     const int prec = sizeof(Real) == 4 ? 0 : 1;
-    AdjArgs a{};
+    AdjRaggedArgs a{}; // (the equal-length kernels take its AdjArgs part)
     a.gy = j.in; a.gx = j.out;
     a.ct = b.ct[prec]; a.d_lo = b.d_lo; a.tab = b.tab[prec]; a.e0 = b.e0;
     a.L = b.L; a.M = b.M; a.Lc = b.Lc; a.Mc = b.Mc;
@@ -471,6 +533,7 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
     a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
     a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
     a.n_y = j.in_frames; a.n_x = j.out_frames;
+    a.rows = rows;
     const bool inter = j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1; // frames of interleaved channels
     a.inter = inter ? 1 : 0;
 
@@ -502,8 +565,9 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
             int nw = std::min(16, (b.n_st + z - 1) / z);
             z = std::min(z, (b.n_st + nw - 1) / nw);
             a.n_waves = nw;
-            if (const char *e = ensure_dyn_lds((const void *)k_adj_tile<Real>, lds)) return e;
-            hipLaunchKernelGGL(k_adj_tile<Real>, dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, a);
+            if (const char *e = ensure_dyn_lds(rows ? (const void *)k_adj_tile<Real, true> : (const void *)k_adj_tile<Real, false>, lds)) return e;
+            if (rows) hipLaunchKernelGGL((k_adj_tile<Real, true>), dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, a);
+            else hipLaunchKernelGGL((k_adj_tile<Real, false>), dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, (AdjArgs)a);
             HIP_TRY(hipGetLastError());
             if (switches().dbg_launch_log) adj_launch_log("adj_tile", sizeof(Real), b, lanes, lds, a, dim3((uint32_t)gx, gy, (uint32_t)z), (unsigned)nw * 64);
             return nullptr;
@@ -512,7 +576,8 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
     const int64_t per_clip = j.out_frames * (int64_t)j.n_channels;
     const int64_t gx = (per_clip + 255) / 256;
     if (gx > 2147483647LL) return "adjoint job: too long for one launch";
-    hipLaunchKernelGGL(k_adj_gather<Real>, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, a);
+    if (rows) hipLaunchKernelGGL((k_adj_gather<Real, true>), dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_adj_gather<Real, false>), dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, (AdjArgs)a);
     HIP_TRY(hipGetLastError());
     if (switches().dbg_launch_log) adj_launch_log("adj_gather", sizeof(Real), b, 0, 0, a, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535), 1), 256);
     return nullptr;
@@ -520,16 +585,17 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
 
 // k_adj_interp on the plan's own interpolation table (uploaded by device_bank_ensure, as for the forward).
 template <typename Real>
-static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st)
+static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows = nullptr)
 {
     const int prec = sizeof(Real) == 4 ? 0 : 1;
-    AdjInterpArgs a{};
+    AdjInterpRaggedArgs a{};
     a.gy = j.in; a.gx = j.out; a.tab = p.dev[prec].interp_tab;
     a.L = p.L; a.M = p.M; a.T = p.T; a.P = p.phases;
     a.n_cols = (uint64_t)j.n_clips * j.n_channels; a.n_channels = j.n_channels;
     a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
     a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
     a.n_y = j.in_frames; a.n_x = j.out_frames;
+    a.rows = rows;
     // positions are 64-bit products, as in the forward: (frame + T/2) L and k M
     const __int128 lim = (__int128)1 << 62;
     if ((__int128)(j.out_frames + p.T) * p.L >= lim || (__int128)j.in_frames * p.M >= lim) return "adjoint job: too long for one launch";
@@ -537,14 +603,19 @@ static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipS
     if (gx > 2147483647LL) return "adjoint job: too long for one launch";
     const dim3 grid((uint32_t)gx, (uint32_t)std::min<uint64_t>(a.n_cols, 65535));
     const bool per_lane = switches().adj_interp_per_lane;
-    if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false>), grid, dim3(kAdjIW), 0, st, a);
-    else hipLaunchKernelGGL((k_adj_interp<Real, true>), grid, dim3(kAdjIW), 0, st, a);
+    if (rows) {
+        if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false, true>), grid, dim3(kAdjIW), 0, st, a);
+        else hipLaunchKernelGGL((k_adj_interp<Real, true, true>), grid, dim3(kAdjIW), 0, st, a);
+    } else if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false, false>), grid, dim3(kAdjIW), 0, st, (AdjInterpArgs)a);
+    else hipLaunchKernelGGL((k_adj_interp<Real, true, false>), grid, dim3(kAdjIW), 0, st, (AdjInterpArgs)a);
     HIP_TRY(hipGetLastError());
     if (switches().dbg_launch_log)
         if (FILE *f = fopen(switches().dbg_launch_log, "a")) {
-            fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u\n", sizeof(Real),
+            fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u", sizeof(Real),
                     (long long)p.L, (long long)p.M, p.T, p.phases, kAdjIW, kAdjIC, sizeof(AdjRec<Real>) * kAdjIC, per_lane ? "lane" : "union",
                     grid.x, grid.y, grid.z, (unsigned)kAdjIW);
+            if (rows) fprintf(f, " ragged=%u", j.n_clips);
+            fputc('\n', f);
             fclose(f);
         }
     return nullptr;
@@ -558,7 +629,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
     if (by_name && p->vr) return "adjoint job: variable-rate plans are not served (HIPSOXR_KERNEL_ADJOINT takes constant-rate plans)";
     if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
     if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
-    if (j.clip_table) return "adjoint job: ragged batches (clip_table) are not served";
+    if (j.clip_table) return "adjoint job: ragged batches (clip_table) are served by hipsoxr_run_device_adjoint_ragged, not by this entry";
     if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && !by_name)
         return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
     if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
@@ -574,6 +645,55 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
     AdjBank *b = nullptr;
     if (const char *e = adj_ensure(p, &b)) return e;
     return j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, (hipStream_t)stream) : adj_launch<double>(*b, j, (hipStream_t)stream);
+}
+
+// hipsoxr_run_device_adjoint_ragged: all clips of a clip table in ONE launch of the kernel's RAGGED form.  The refusals are
+// made by name before the device is asked for, as in launch_adjoint.  More than 65535 columns: the kernels' gridDim.y
+// loops wrap.
+const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT;
+    if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
+    if (p->vr) return "adjoint job: variable-rate plans are not served (ragged batches take constant-rate plans)";
+    if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans are served by name, HIPSOXR_KERNEL_ADJOINT)";
+    if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
+    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && !by_name)
+        return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
+    if (!j.clip_table) return "adjoint job: the ragged entry needs a clip_table (equal-length clips: hipsoxr_run_device_adjoint)";
+    for (uint32_t c = 0; c < j.n_clips; ++c) {
+        const int64_t *r = j.clip_table + 4 * (size_t)c;
+        if (r[0] < 0 || r[1] < 0 || r[2] < 0 || r[3] < 0) return "adjoint job: ragged: a clip's offset or frame count is negative";
+        if (r[1] > j.in_frames || r[3] > j.out_frames) return "adjoint job: ragged: a clip's frame count is above the job's in_frames / out_frames (the largest per-clip values)";
+        if ((uint64_t)r[1] > plan_out_len(*p, (uint64_t)r[3]))
+            return "adjoint job: ragged: a clip's n_y (cotangent frames) exceeds the plan's output length for its n_x";
+    }
+    if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
+    if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+    if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    AdjBank *b = nullptr;
+    if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
+        if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    } else if (const char *e = adj_ensure(p, &b)) return e;
+    // The kernels read the DEVICE copy of the table; without one the host table, validated above, is uploaded in stream
+    // order (launch_job's rule: the buffer lives until the launch behind it has run).  A caller's copy is trusted.
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t *rows = j.clip_table_dev;
+    void *tmp = nullptr;
+    if (!rows) {
+        const size_t bytes = (size_t)j.n_clips * 4 * sizeof(int64_t);
+        if (hipMallocAsync(&tmp, bytes, st) != hipSuccess) return "adjoint job: ragged: no device memory for the clip table";
+        if (hipMemcpyAsync(tmp, j.clip_table, bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+            (void)hipFreeAsync(tmp, st);
+            return "adjoint job: ragged: clip table upload failed";
+        }
+        rows = (const int64_t *)tmp;
+    }
+    const char *e;
+    if (p->phases) e = j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, st, rows) : adj_interp_launch<double>(*p, j, st, rows);
+    else e = j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, st, rows) : adj_launch<double>(*b, j, st, rows);
+    if (tmp) (void)hipFreeAsync(tmp, st);
+    return e;
 }
 
 } // namespace hipsoxr

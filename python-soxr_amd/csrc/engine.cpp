@@ -497,6 +497,12 @@ hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *h, const hipsoxr_job_
     return launch_adjoint(&h->p, *job, hip_stream); // (refusals, by name, and the empty job: there)
 }
 
+hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *h, const hipsoxr_job_t *job, void *hip_stream)
+{
+    if (!h || !job) return "null argument";
+    return launch_adjoint_ragged(&h->p, *job, hip_stream);
+}
+
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------

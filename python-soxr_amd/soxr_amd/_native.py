@@ -60,7 +60,7 @@ RESIDENT = 128
 AUTO_RESIDENT = 256
 STREAM_FFT = 512  # device-chunk streams on the frequency-domain engine (TensorStream(engine="fft"))
 KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA, KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM = range(10)
-KERNEL_ADJOINT = 10  # hipsoxr_run_device_adjoint only: the transposed operator on every constant-rate plan (interpolated-phase plans too)
+KERNEL_ADJOINT = 10  # hipsoxr_run_device_adjoint / _adjoint_ragged only: the transposed operator on every constant-rate plan (interpolated-phase plans too)
 ADJOINT_INTERP_TILE = 256  # frames per workgroup of k_adj_interp (csrc/adjoint.hip kAdjIW): where its tile edges fall
 
 
@@ -100,6 +100,7 @@ SIGNATURES = {
     "hipsoxr_plan_out_len": (C.c_uint64, [C.c_void_p, C.c_uint64]),
     "hipsoxr_run_device": (_err, [C.c_void_p, _P(Job), C.c_void_p]),
     "hipsoxr_run_device_adjoint": (_err, [C.c_void_p, _P(Job), C.c_void_p]),
+    "hipsoxr_run_device_adjoint_ragged": (_err, [C.c_void_p, _P(Job), C.c_void_p]),
     "hipsoxr_stream_create": (_err, [C.c_double, C.c_double, C.c_uint, C.c_int, C.c_ulong, C.c_ulong,
                                      _P(C.c_void_p)]),
     "hipsoxr_stream_create_with_plan": (_err, [C.c_void_p, C.c_uint, C.c_int, C.c_ulong, _P(C.c_void_p)]),

@@ -88,6 +88,26 @@ class Plan:
         j.clip_table = clip_table
         _n.check(_n.lib.hipsoxr_run_device_adjoint(self._h, _C.byref(j), stream))
 
+    def run_adjoint_ragged(self, gy_ptr, gx_ptr, elem, n_channels, table, gy_strides, gx_strides, stream=None,
+                           kernel=_n.KERNEL_AUTO, table_dev=None):
+        """Raw launch of the transposed operator over a ragged batch (hipsoxr_run_device_adjoint_ragged): ONE launch for
+        all clips.  table: int64 host array [n_clips, 4] of rows (gy offset, n_y, gx offset, n_x), offsets in elements
+        from gy_ptr / gx_ptr, n_y <= out_len(n_x) per clip; table_dev: a device copy of it (pointer), or None = uploaded
+        in stream order.  strides = (frame, channel) in elements.  Selectors as for `run_adjoint`."""
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+        n = t.shape[0]
+        if n == 0:  # (an empty array has no address worth passing: the entry refuses a NULL table)
+            t = np.zeros((1, 4), np.int64)
+        j = _n.Job()
+        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
+        j.n_clips, j.n_channels = n, n_channels
+        j.in_frame_stride, j.in_chan_stride = gy_strides
+        j.out_frame_stride, j.out_chan_stride = gx_strides
+        j.in_abs0, j.out_k0 = 0, 0
+        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
+        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
+        _n.check(_n.lib.hipsoxr_run_device_adjoint_ragged(self._h, _C.byref(j), stream))
+
 
 class PreparedJob:
     """A device job whose descriptor is built once: `launch()` is a single C call
@@ -174,7 +194,8 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO
     the same launch and the same bits, on an interpolated-phase plan (`plan.phases != 0`: 48000 -> 44101, non-integral
     rates) the gather-form adjoint on the plan's interpolation table, whose coefficients are the very bits the forward
     with kernel=KERNEL_EXACT multiplies by.  There a non-finite gy[k] reaches exactly the frames of its true support.
-    The two-stage form's adjoint, variable rate, streams, ragged batches, dist.py and integer types are not served."""
+    Ragged batches: `dist.resample_ragged_adjoint` / `dist.resample_ragged`.  The two-stage form's adjoint, variable
+    rate, streams and integer types are not served."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch

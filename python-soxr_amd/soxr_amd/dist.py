@@ -14,6 +14,10 @@ the GIL released (src/soxr_ext.cpp:222,297; tests/gil_bench.py:22-56).  The MI35
   at plan time, through torch's communicator or, with no torch in the path, through `hipsoxr_plan_broadcast`
   (C ABI, raw `ncclComm_t`).
 
+* gradients of a ragged batch: `resample_ragged(plan, clips)` is the differentiable form of `RaggedJob`, and
+  `resample_ragged_adjoint(plan, gys, in_frames)` the transposed operator over all clips in ONE launch
+  (`hipsoxr_run_device_adjoint_ragged`) — what its backward runs.
+
 bench.py and the multi-process tests import these from here; nothing below touches `oracle/`.
 """
 import ctypes as _C
@@ -178,6 +182,147 @@ class RaggedJob:
             outs.append(v[:, 0] if mono else v)
             pos += n
         return outs
+
+
+def _split(packed, lengths, monos):
+    """per-clip views of a packed [sum(lengths), channels] tensor ([frames] for a clip that came in as [frames])"""
+    outs, pos = [], 0
+    for n, mono in zip(lengths, monos):
+        v = packed[pos:pos + n]
+        outs.append(v[:, 0] if mono else v)
+        pos += n
+    return outs
+
+
+def _ragged_adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
+    """The ragged C entry's own refusal of (plan, element type, selector), or None: asked with an empty job, as
+    `device._adjoint_refusal` asks the equal-length entry."""
+    try:
+        plan.run_adjoint_ragged(None, None, elem, 0, np.zeros((0, 4), np.int64), (0, 0), (0, 0), kernel=kernel)
+    except RuntimeError as e:
+        return str(e)
+    return None
+
+
+def _ragged_adjoint_plain(plan, gys, in_frames, kernel):
+    """`resample_ragged_adjoint` proper: the one C call, without autograd.  -> packed gx [sum(in_frames), channels]"""
+    import torch
+    if not gys:
+        raise ValueError("no clips")
+    if len(gys) != len(in_frames):
+        raise ValueError("one in_frames entry per cotangent clip")
+    device, dtype = gys[0].device, gys[0].dtype
+    ch = 1 if gys[0].ndim == 1 else gys[0].shape[1]
+    for g in gys:
+        if g.device != device or g.dtype != dtype or g.ndim not in (1, 2) or (1 if g.ndim == 1 else g.shape[1]) != ch:
+            raise ValueError("clips of one job share device, dtype and channel count; each is [frames] or [frames, channels]")
+    if not gys[0].is_cuda:
+        raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
+    elem, es = _dev._torch_elem(dtype), gys[0].element_size()
+    keep = [g if g.is_contiguous() else g.contiguous() for g in gys]  # (a strided clip is the one case that is copied)
+    n_y, n_x = [int(g.shape[0]) for g in keep], [int(n) for n in in_frames]
+    gx = torch.empty((sum(n_x), ch), dtype=dtype, device=device)
+    ptrs = [g.data_ptr() for g in keep if g.shape[0] > 0]   # (an empty tensor has no storage address)
+    base = min(ptrs) if ptrs else gx.data_ptr()
+    gy_off = np.array([(g.data_ptr() - base) // es if g.shape[0] > 0 else 0 for g in keep], dtype=np.int64)
+    gx_off = np.concatenate([[0], np.cumsum(n_x)[:-1]]).astype(np.int64) * ch
+    table = np.ascontiguousarray(np.stack([gy_off, n_y, gx_off, n_x], axis=1), dtype=np.int64)
+    plan.run_adjoint_ragged(base, gx.data_ptr(), elem, ch, table, (ch, 1), (ch, 1),
+                            stream=torch.cuda.current_stream(device).cuda_stream, kernel=kernel)
+    return gx
+
+
+_RAGGED_AUTOGRAD = None
+
+
+def _ragged_autograd_fns():
+    """The torch.autograd.Function pair over a ragged batch (built on first use, as `device._autograd_fns`).  Each takes
+    the clips as separate inputs and returns ONE packed tensor, so autograd hands back one packed cotangent and a backward
+    is one ragged launch: the forward's backward is the ragged adjoint, the adjoint's backward the ragged forward on the
+    exact engine — differentiable to any order."""
+    global _RAGGED_AUTOGRAD
+    if _RAGGED_AUTOGRAD is not None:
+        return _RAGGED_AUTOGRAD
+    import torch
+
+    class RaggedFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, kernel, grad_kernel, *clips):
+            job = RaggedJob(plan, [c.detach() for c in clips], kernel=kernel)
+            job.launch()
+            ctx.plan, ctx.grad_kernel, ctx.n_in, ctx.n_out = plan, grad_kernel, job.n_in, job.n_out
+            ctx.monos = [c.ndim == 1 for c in clips]
+            return job.y
+
+        @staticmethod
+        def backward(ctx, gy):
+            gys = _split(gy.contiguous(), ctx.n_out, [False] * len(ctx.n_out))
+            gxs = resample_ragged_adjoint(ctx.plan, gys, ctx.n_in, kernel=ctx.grad_kernel)
+            need = ctx.needs_input_grad[3:]
+            return (None, None, None) + tuple((g[:, 0] if mono else g) if nd else None
+                                              for g, mono, nd in zip(gxs, ctx.monos, need))
+
+    class RaggedAdjointFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, in_frames, kernel, *gys):
+            ctx.plan, ctx.kernel, ctx.n_x = plan, kernel, [int(n) for n in in_frames]
+            ctx.n_y, ctx.monos = [int(g.shape[0]) for g in gys], [g.ndim == 1 for g in gys]
+            return _ragged_adjoint_plain(plan, [g.detach() for g in gys], in_frames, kernel)
+
+        @staticmethod
+        def backward(ctx, ggx):  # (the ragged forward on the exact engine; its own gradient is this adjoint again, same selector)
+            xs = _split(ggx.contiguous(), ctx.n_x, [False] * len(ctx.n_x))
+            ys = resample_ragged(ctx.plan, xs, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
+            need = ctx.needs_input_grad[3:]
+            return (None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
+                                              for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
+
+    _RAGGED_AUTOGRAD = (RaggedFn, RaggedAdjointFn)
+    return _RAGGED_AUTOGRAD
+
+
+def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
+    """The transposed operator over a ragged batch, ONE launch for all clips: gx[c] = A_c^T gys[c], A_c the resample of
+    in_frames[c] input frames that the exact engine computes on `plan` (what the backward of `resample_ragged` runs).
+
+    gys : list of [frames] / [frames, channels] float32 / float64 device tensors of one device, dtype and channel count,
+          clip c with at most plan.out_len(in_frames[c]) frames (a truncated cotangent).  They are read where they lie,
+          as `RaggedJob` reads its clips (a non-contiguous one is copied).
+    Returns per-clip views ([in_frames[c]] or [in_frames[c], channels], as gys[c]) of one packed
+    [sum(in_frames), channels] buffer; every element is written.  Each clip has the bits of
+    `device.resample_tensor_adjoint` on that clip alone (finite cotangents).  On the current torch stream,
+    asynchronously.  Selectors as there: KERNEL_AUTO / KERNEL_EXACT on exact-bank plans, KERNEL_ADJOINT on every
+    constant-rate plan.  Differentiable: its backward is the ragged forward on the exact engine."""
+    import torch
+    monos = [g.ndim == 1 for g in gys]
+    if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
+        gx = _ragged_autograd_fns()[1].apply(plan, [int(n) for n in in_frames], kernel, *gys)
+    else:
+        gx = _ragged_adjoint_plain(plan, list(gys), in_frames, kernel)
+    return _split(gx, [int(n) for n in in_frames], monos)
+
+
+def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AUTO):
+    """Resample a batch of clips of unequal length on one device as one job; returns the list of per-clip outputs (views
+    of one packed buffer).  Without `requires_grad` on any clip, or under `no_grad`, this is exactly
+    `RaggedJob(plan, clips, kernel).launch()` and its `outputs()`.
+
+    Differentiable otherwise: the result carries a grad_fn whose backward is ONE ragged launch of the transposed operator
+    (`resample_ragged_adjoint` with `grad_kernel`), whatever the number of clips; gradients of gradients flow too.  A clip
+    that does not require grad gets none.  As for `device.resample_tensor`, the gradient is the EXACT engine's adjoint
+    (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
+    interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called."""
+    import torch
+    if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
+        why = _ragged_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
+        if why:
+            raise RuntimeError(why)
+        y = _ragged_autograd_fns()[0].apply(plan, kernel, grad_kernel, *clips)
+        n_out = [plan.out_len(int(c.shape[0])) for c in clips]
+        return _split(y, n_out, [c.ndim == 1 for c in clips])
+    job = RaggedJob(plan, clips, kernel=kernel)
+    job.launch()
+    return job.outputs()
 
 
 # Plans per (device, conversion), least recently used first: device tables live where they were built, and a long-lived
