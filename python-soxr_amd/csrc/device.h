@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/hipsoxr.h"
 #include "plan.h"
+#include "stream_rules.h" // VrPos
 
 namespace hipsoxr {
 
@@ -15,12 +16,6 @@ inline size_t elem_size(int elem)
 {
     return elem == HIPSOXR_F32 ? 4 : elem == HIPSOXR_F64 ? 8 : elem == HIPSOXR_I32 ? 4 : 2;
 }
-
-// Variable-rate launches: input position of local output i is the Q64.64 fixed-point quadratic
-//   t(i) = T0 + i*S0 + D*i(i-1)/2     (128-bit two's-complement words, hi:lo)
-struct VrPos {
-    uint64_t t_hi, t_lo, s_hi, s_lo, d_hi, d_lo;
-};
 
 // Enqueue one job (validated by the caller) on `stream`.  vr != nullptr: positions come from *vr
 // instead of the plan's rational ratio (interpolated-phase plans only).

@@ -39,35 +39,6 @@ namespace hipsoxr {
 Plan::~Plan() { twostage_release(this); device_bank_release(this); fft_release(this); adjoint_release(this); }
 } // namespace hipsoxr
 
-// Variable-rate state (SOXR_VR streams; reference: src/soxr_ext.cpp:74, :200-204).  Time is kept in
-// Q64.64 fixed point.  The current segment starts at output k_s with input position t_s and step
-// s0; during the first n_slew outputs the step grows by `delta` per output, afterwards it is s1:
-//     t(k_s + n) = t_s + n*s0 + delta*n(n-1)/2                      n <= n_slew
-//                = t(k_s + n_slew) + (n - n_slew)*s1                n >  n_slew
-// All integer arithmetic: positions are exact, monotonic, and independent of how calls are cut.
-typedef unsigned __int128 u128;
-typedef __int128 i128;
-struct VrState {
-    bool on = false;
-    double max_io = 0.;  // in_rate/out_rate at creation: the largest io ratio the filter allows
-    uint64_t k_s = 0, n_slew = 0;
-    i128 t_s = 0, s0 = 0, delta = 0, s1 = 0;
-
-    i128 pos(uint64_t k) const
-    {
-        const u128 n = k - k_s;
-        if (n <= n_slew) return t_s + (i128)n * s0 + delta * (i128)(n * (n - 1) / 2);
-        const u128 N = n_slew;
-        return t_s + (i128)N * s0 + delta * (i128)(N * (N - 1) / 2) + (i128)(n - N) * s1;
-    }
-    i128 step(uint64_t k) const
-    {
-        const u128 n = k - k_s;
-        return n < n_slew ? s0 + (i128)n * delta : s1;
-    }
-};
-static inline i128 q64(double x) { return (i128)(u128)std::ldexp(x, 64); } // truncating, exact scaling
-
 struct hipsoxr_stream {
     VrState vr;
     hipsoxr_plan *plan = nullptr;
@@ -510,17 +481,6 @@ hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *h, const hipso
 // ------------------------------------------------------------------------------------------------
 static inline size_t esz(const hipsoxr_stream *s) { return elem_size(s->elem); }
 
-// Number of outputs computable from the first N input frames without zero-extension:
-// output k needs inputs up to floor(k*M/L) + T/2.
-static uint64_t k_avail(const Plan &p, uint64_t N)
-{
-    const int64_t H = p.T / 2;
-    if ((int64_t)N - 1 - H < 0) return 0;
-    unsigned __int128 Q = (unsigned __int128)(N - 1 - (uint64_t)H);
-    unsigned __int128 v = ((Q + 1) * (unsigned __int128)p.L - 1) / (unsigned __int128)p.M;
-    return (uint64_t)v + 1;
-}
-
 // Absolute index of the first input sample the next output (k_done) needs.
 static int64_t first_needed(const hipsoxr_stream *s)
 {
@@ -545,31 +505,38 @@ static int64_t first_needed(const hipsoxr_stream *s)
     return n0;
 }
 
-// Variable rate: number of outputs [0, K) computable from N input frames without zero-extension
-// (output k reads up to floor(t(k)) + T/2), or — at end of input — the total K with
-// t(k) + step(k)/2 <= N (the constant-rate rule floor(N*L/M + 1/2), restated for a moving step).
-static uint64_t vr_k_limit(const hipsoxr_stream *s, bool ended)
+// What of the ring the outputs still to come need (stream_rules.h: the retire rule, for every site that drops or moves frames)
+static inline RingKeep stream_keep(const hipsoxr_stream *s) { return ring_keep(first_needed(s), s->in_base, s->in_fill); }
+
+static inline bool stream_dither(const hipsoxr_stream *s) { return s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER); }
+
+// The clock of the launch (or resident message) that starts at k_done, in *vp; nullptr on constant-rate streams
+static inline const VrPos *stream_clock(const hipsoxr_stream *s, VrPos *vp)
 {
-    const VrState &v = s->vr;
-    const int64_t H = s->plan->p.T / 2;
-    const i128 N = (i128)s->n_in_total << 64;
-    auto ok = [&](uint64_t k) -> bool {
-        if (ended) return v.pos(k) + v.step(k) / 2 <= N;
-        return (int64_t)(v.pos(k) >> 64) + H <= (int64_t)s->n_in_total - 1;
-    };
-    uint64_t lo = s->k_done; // invariant: every k < lo is ok (already emitted, or checked)
-    if (!ok(lo)) return lo;
-    uint64_t span = 1;
-    while (ok(lo + span)) { lo += span; span <<= 1; } // t is strictly increasing: exponential + binary search
-    uint64_t hi = lo + span;                           // ok(lo), !ok(hi)
-    while (hi - lo > 1) {
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (ok(mid)) lo = mid; else hi = mid;
-    }
-    return hi;
+    if (!s->vr.on) return nullptr;
+    *vp = vr_pos_at(s->vr, s->k_done);
+    return vp;
 }
 
-// Move the still-needed tail of the staged input to the front of the alternate buffer.
+// The job of an emission: outputs [k_done, k_done + n) from the ring, to `out` in the stream's layout (out_chan_stride:
+// frames between the planes of a split layout).  Callers set what is theirs: `in` of an empty ring, another engine.
+static inline hipsoxr_job_t stream_job(const hipsoxr_stream *s, void *out, size_t n, int64_t out_chan_stride)
+{
+    hipsoxr_job_t j;
+    std::memset(&j, 0, sizeof j);
+    j.in = s->d_in; j.out = out; j.elem = s->elem;
+    j.kernel = HIPSOXR_KERNEL_EXACT; // bit-exact chunk invariance
+    j.n_clips = 1; j.n_channels = s->ch;
+    j.in_frame_stride = j.out_frame_stride = s->split ? 1 : (int64_t)s->ch;
+    j.in_chan_stride = s->split ? (int64_t)s->in_cap : 1; j.out_chan_stride = s->split ? out_chan_stride : 1;
+    j.in_abs0 = s->in_base; j.in_frames = (int64_t)s->in_fill;
+    j.out_k0 = (int64_t)s->k_done; j.out_frames = (int64_t)n;
+    j.clip_counter = s->d_clips;
+    j.dither = stream_dither(s) ? 1u : 0u;
+    j.dither_seed = s->dither_seed;
+    return j;
+}
+
 static void ring_free(hipsoxr_stream *s, void *p)
 {
     if (!p) return;
@@ -583,23 +550,21 @@ static const char *host_ring_reserve(hipsoxr_stream *s, size_t ilen)
     const size_t frame = (size_t)s->ch * esz(s);
     if (s->d_in && s->in_fill + ilen <= s->in_cap) return nullptr;
     if (!s->res.running) HIP_TRY(stream_wait(s)); // (a resident kernel is idle between calls: it has answered the last one)
-    const int64_t n0 = first_needed(s);
-    const int64_t keep_from = std::min<int64_t>(std::max<int64_t>(n0, s->in_base), s->in_base + (int64_t)s->in_fill);
-    const size_t drop = (size_t)(keep_from - s->in_base), keep = s->in_fill - drop;
-    size_t cap = std::max<size_t>(s->in_cap, 1024);
-    while (cap < keep + 8 * ilen) cap <<= 1; // compaction every eighth call
+    const RingKeep k = stream_keep(s);
+    const size_t room = 8 * ilen; // compaction every eighth call
+    const size_t cap = ring_grow(s->in_cap, k.keep, room);
     if (cap != s->in_cap || !s->d_in) {
         resident_stop(s); // the ring moves: the next call launches another instance on the new one
         void *nb = nullptr;
         if (hipHostMalloc(&nb, cap * frame, hipHostMallocDefault) != hipSuccess) return "hipHostMalloc failed";
-        if (keep) std::memcpy(nb, (char *)s->d_in + drop * frame, keep * frame);
+        if (k.keep) std::memcpy(nb, (char *)s->d_in + k.drop * frame, k.keep * frame);
         if (s->d_in) (void)hipHostFree(s->d_in);
         s->d_in = nb; s->in_cap = cap;
-    } else if (keep && drop) {
-        std::memmove(s->d_in, (char *)s->d_in + drop * frame, keep * frame);
+    } else if (k.keep && k.drop) {
+        std::memmove(s->d_in, (char *)s->d_in + k.drop * frame, k.keep * frame);
     }
-    s->in_base = keep_from;
-    s->in_fill = keep;
+    s->in_base = k.keep_from;
+    s->in_fill = k.keep;
     return nullptr;
 }
 
@@ -621,38 +586,50 @@ static const char *host_ring_to_device(hipsoxr_stream *s)
     return nullptr;
 }
 
+// Move the still-needed tail of the staged input to the front of the alternate buffer.
 static const char *stream_compact(hipsoxr_stream *s, size_t want_cap)
 {
-    const int64_t n0 = first_needed(s);
-    int64_t keep_from = std::max<int64_t>(n0, s->in_base);
-    keep_from = std::min<int64_t>(keep_from, s->in_base + (int64_t)s->in_fill);
-    const size_t drop = (size_t)(keep_from - s->in_base), keep = s->in_fill - drop;
+    const RingKeep k = stream_keep(s);
     const size_t cap = std::max(want_cap, s->in_cap);
-    if (drop == 0 && cap == s->in_cap) return nullptr;
+    if (k.drop == 0 && cap == s->in_cap) return nullptr;
     if (s->alt_cap < cap || !s->d_in_alt) {
         if (s->d_in_alt) HIP_TRY(hipFree(s->d_in_alt));
         s->d_in_alt = nullptr;
         HIP_TRY(hipMalloc(&s->d_in_alt, cap * s->ch * esz(s)));
         s->alt_cap = cap;
     }
-    if (keep) {
+    if (k.keep) {
         if (!s->split) {
-            HIP_TRY(hipMemcpyAsync(s->d_in_alt, (char *)s->d_in + drop * s->ch * esz(s),
-                                   keep * s->ch * esz(s), hipMemcpyDeviceToDevice, s->st));
+            HIP_TRY(hipMemcpyAsync(s->d_in_alt, (char *)s->d_in + k.drop * s->ch * esz(s),
+                                   k.keep * s->ch * esz(s), hipMemcpyDeviceToDevice, s->st));
         } else {
-            HIP_TRY(hipMemcpy2DAsync(s->d_in_alt, s->alt_cap * esz(s), (char *)s->d_in + drop * esz(s),
-                                     s->in_cap * esz(s), keep * esz(s), s->ch,
+            HIP_TRY(hipMemcpy2DAsync(s->d_in_alt, s->alt_cap * esz(s), (char *)s->d_in + k.drop * esz(s),
+                                     s->in_cap * esz(s), k.keep * esz(s), s->ch,
                                      hipMemcpyDeviceToDevice, s->st));
         }
     }
     std::swap(s->d_in, s->d_in_alt);
     std::swap(s->in_cap, s->alt_cap);
-    s->in_base = keep_from;
-    s->in_fill = keep;
+    s->in_base = k.keep_from;
+    s->in_fill = k.keep;
     return nullptr;
 }
 
-static const char *stream_append(hipsoxr_stream *s, const void *in, size_t ilen)
+// Room in the device ring for `ilen` more frames: retire consumed input first; grow (power of two) only if that is not
+// enough.  Enqueues on s->st.
+static const char *device_ring_reserve(hipsoxr_stream *s, size_t ilen)
+{
+    if (s->in_fill + ilen <= s->in_cap) return nullptr;
+    // room for the history plus four chunks of this size: compaction (a device-to-device copy)
+    // then runs every fourth call instead of every call
+    const size_t room = 4 * ilen;
+    const RingKeep k = stream_keep(s);
+    return stream_compact(s, ring_grow_bounded(s->in_cap, k.keep, room, ilen));
+}
+
+// Append a host chunk to the ring.  h_buf / h_bytes: the pinned bounce buffer a device ring's copy goes through (grown here
+// when the chunk needs it: the stream's own, or the one of the deferred path's two whose turn it is).
+static const char *stream_append(hipsoxr_stream *s, const void *in, size_t ilen, void **h_buf, size_t *h_bytes)
 {
     const size_t bytes_in = ilen * s->ch * esz(s);
     if (!s->split && !s->ring_on_host && s->n_in_total == 0 && bytes_in <= kHostRingChunk && !switches().no_host_ring) {
@@ -675,32 +652,19 @@ static const char *stream_append(hipsoxr_stream *s, const void *in, size_t ilen)
             return nullptr;
         }
     }
-    if (s->in_fill + ilen > s->in_cap) {
-        // retire consumed input first; grow (power of two) only if that is not enough
-        const int64_t n0 = first_needed(s);
-        int64_t keep_from = std::min<int64_t>(std::max<int64_t>(n0, s->in_base),
-                                              s->in_base + (int64_t)s->in_fill);
-        size_t keep = s->in_fill - (size_t)(keep_from - s->in_base);
-        // room for the history plus four chunks of this size: compaction (a device-to-device copy)
-        // then runs every fourth call instead of every call
-        size_t need = keep + 4 * ilen, cap = std::max<size_t>(s->in_cap, 1024);
-        if (need > ((size_t)1 << 24)) need = keep + ilen;
-        while (cap < need) cap <<= 1;
-        if (const char *e = stream_compact(s, cap)) return e;
-    }
-    const size_t chunk_bytes = ilen * s->ch * esz(s);
-    const bool bounce = chunk_bytes <= kPinnedMax && !pinned_ensure(&s->h_in, &s->h_in_bytes, chunk_bytes);
+    if (const char *e = device_ring_reserve(s, ilen)) return e;
+    const bool bounce = bytes_in <= kPinnedMax && !pinned_ensure(h_buf, h_bytes, bytes_in);
     if (!s->split) {
         const void *src = in;
-        if (bounce) { std::memcpy(s->h_in, in, chunk_bytes); src = s->h_in; }
-        HIP_TRY(hipMemcpyAsync((char *)s->d_in + s->in_fill * s->ch * esz(s), src, chunk_bytes,
+        if (bounce) { std::memcpy(*h_buf, in, bytes_in); src = *h_buf; }
+        HIP_TRY(hipMemcpyAsync((char *)s->d_in + s->in_fill * s->ch * esz(s), src, bytes_in,
                                hipMemcpyHostToDevice, s->st));
     } else {
         const void *const *chans = (const void *const *)in;
         for (unsigned c = 0; c < s->ch; ++c) {
             const void *src = chans[c];
             if (bounce) {
-                src = (char *)s->h_in + (size_t)c * ilen * esz(s);
+                src = (char *)*h_buf + (size_t)c * ilen * esz(s);
                 std::memcpy((void *)src, chans[c], ilen * esz(s));
             }
             HIP_TRY(hipMemcpyAsync((char *)s->d_in + ((size_t)c * s->in_cap + s->in_fill) * esz(s), src,
@@ -712,33 +676,38 @@ static const char *stream_append(hipsoxr_stream *s, const void *in, size_t ilen)
     return nullptr;
 }
 
-// Emit up to olen frames (host destination).  `out_off` = frame offset into the caller's buffers.
-static const char *stream_emit_once(hipsoxr_stream *s, void *out, size_t olen, size_t *odone);
-
 // Variable-rate streams evaluate one position law per launch, so a call that crosses the end of a
-// slew is served by two launches; everything else is a single one.
-static const char *stream_emit(hipsoxr_stream *s, void *out, size_t olen, size_t *odone)
+// slew is served by two launches; everything else is a single one.  `once` emits up to olen frames to `out` (the
+// stream's layout: split planes or an interleaved pointer, advanced here) and says how many; at most max_passes of them.
+// (`once` is a template argument: a direct call, nothing per emission that the two loops did not have.)
+typedef const char *(*emit_once_fn)(hipsoxr_stream *s, void *out, size_t olen, size_t *odone);
+template <emit_once_fn once>
+static inline const char *emit_passes(hipsoxr_stream *s, unsigned max_passes, void *out, size_t olen, size_t *odone)
 {
-    if (!s->vr.on) return stream_emit_once(s, out, olen, odone);
     size_t total = 0;
-    std::vector<void *> chans(s->split ? s->ch : 0);
-    for (int pass = 0; pass < 4 && total < olen; ++pass) {
-        void *o = out;
-        if (s->split) {
-            for (unsigned c = 0; c < s->ch; ++c) chans[c] = (char *)((void *const *)out)[c] + total * esz(s);
-            o = chans.data();
-        } else {
-            o = (char *)out + total * s->ch * esz(s);
-        }
+    std::vector<void *> chans; // (split layouts only: the planes' pointers, advanced)
+    if (s->split) chans.resize(s->ch);
+    for (unsigned pass = 0; out && pass < max_passes && total < olen; ++pass) {
+        for (size_t c = 0; c < chans.size(); ++c) chans[c] = (char *)((void *const *)out)[c] + total * esz(s);
+        void *o = s->split ? (void *)chans.data() : (char *)out + total * s->ch * esz(s);
         size_t got = 0;
-        if (const char *e = stream_emit_once(s, o, olen - total, &got)) return e;
+        if (const char *e = once(s, o, olen - total, &got)) return e;
         total += got;
-        if (!got) break;
         // another pass only if this one stopped at the end of a slew (an empty pass costs a wait on the stream)
-        if (!(s->vr.n_slew && s->k_done == s->vr.k_s + s->vr.n_slew)) break;
+        if (!got || !slew_just_ended(s->vr, s->k_done)) break;
     }
     *odone = total;
     return nullptr;
+}
+
+// How long an idle resident kernel stays, in microseconds (half of it: the gap that breaks a run of small calls)
+static inline int resident_gap_us() { return std::min(kResidentWatchdogUs, std::max(50, switches().resident_idle_us)); }
+
+// Completion words of a launch (ChainDone, ResidentBox::done): workgroups [0, *next) have answered `seq`; true when all have
+static inline bool done_words_seen(const volatile uint32_t *words, unsigned n_wgs, uint32_t seq, unsigned *next)
+{
+    while (*next < n_wgs && words[*next] == seq) ++*next;
+    return *next == n_wgs;
 }
 
 // Synchronous small chunk through the resident kernel: post the call's numbers, spin on the answer.
@@ -790,7 +759,7 @@ static const char *resident_emit(hipsoxr_stream *s, const hipsoxr_job_t &j, bool
         ResidentLaunch rl;
         rl.box = r.box; rl.words = (const uint64_t *)r.words; rl.ctl = r.ctl + r.ctl_next++; rl.base_seq = base_seq;
         if (++r.epoch == 0) ++r.epoch;
-        rl.epoch = r.epoch; rl.idle_us = std::min(kResidentWatchdogUs, std::max(50, switches().resident_idle_us));
+        rl.epoch = r.epoch; rl.idle_us = resident_gap_us();
         hipsoxr_job_t cap = jr; // room for chunks a quarter longer than this one
         cap.out_frames = std::max<int64_t>(64, j.out_frames + j.out_frames / 4 + 2);
         std::lock_guard<std::mutex> reserve(g_resident_mu);
@@ -815,18 +784,16 @@ static const char *resident_emit(hipsoxr_stream *s, const hipsoxr_job_t &j, bool
     r.seq = seq;
     volatile uint32_t *done = r.box->done, *exited = &r.box->exited;
     const auto t0 = std::chrono::steady_clock::now();
-    unsigned next = 0; // workgroups [0, next) have answered
+    unsigned next = 0;
     for (uint64_t spin = 0;; ++spin) {
-        while (next < r.n_wgs && done[next] == seq) ++next;
-        if (next == r.n_wgs) break;
+        if (done_words_seen(done, r.n_wgs, seq, &next)) break;
         if (*exited == r.epoch) {
             // the instance left (idle for too long) before it saw the message, which is still in the box: the next
             // instance takes it.  (An instance answers a message completely or not at all: k_chain_resident.)
             (void)hipStreamSynchronize(s->st);
             r.running = false;
             g_resident_mcu -= (int64_t)r.cost_mcu;
-            while (next < r.n_wgs && done[next] == seq) ++next;
-            if (next == r.n_wgs) break;
+            if (done_words_seen(done, r.n_wgs, seq, &next)) break;
             // (refused — over the budget, say: nobody has touched the message, the ordinary path serves this call;
             //  a later instance starts behind it, at r.seq, and ignores the stale words)
             if (const char *e = launch(seq - 1)) return *e ? e : nullptr;
@@ -855,26 +822,9 @@ static const char *resident_emit(hipsoxr_stream *s, const hipsoxr_job_t &j, bool
     return nullptr;
 }
 
-static const char *stream_emit_once(hipsoxr_stream *s, void *out, size_t olen, size_t *odone)
+// Where an emission of n frames goes: the stream's device buffer (grown here), or — *direct — pinned host memory.
+static const char *emit_target(hipsoxr_stream *s, size_t n, bool *direct)
 {
-    const Plan &p = s->plan->p;
-    VrState &v = s->vr;
-    if (v.on && v.n_slew && s->k_done >= v.k_s + v.n_slew) { // slew finished: renormalise to a constant segment
-        const uint64_t k1 = v.k_s + v.n_slew;
-        v.t_s = v.pos(k1); v.k_s = k1; v.s0 = v.s1; v.delta = 0; v.n_slew = 0;
-    }
-    const uint64_t k_end = v.on ? vr_k_limit(s, s->ended)
-                                : s->ended ? plan_out_len(p, s->n_in_total) : k_avail(p, s->n_in_total);
-    size_t n = 0;
-    if (k_end > s->k_done) n = (size_t)std::min<uint64_t>(k_end - s->k_done, olen);
-    // one launch evaluates one quadratic: stop at the end of a slew (stream_emit comes back for the rest)
-    if (v.on && v.n_slew && s->k_done + n > v.k_s + v.n_slew) n = (size_t)(v.k_s + v.n_slew - s->k_done);
-    *odone = n;
-    if (n == 0) {
-        // the caller's input buffer is borrowed only for the call; a host ring took its copy with memcpy, nothing is queued
-        if (!s->res.running && !s->ring_on_host) HIP_TRY(stream_wait(s));
-        return nullptr;
-    }
     if (n > s->out_cap) {
         size_t cap = 1024;
         while (cap < n) cap <<= 1;
@@ -894,105 +844,107 @@ static const char *stream_emit_once(hipsoxr_stream *s, void *out, size_t olen, s
     // copy path costs ~17 us more where the direct writes did merge (48k -> 44.1k stereo, 20 000 frames: 52 -> 70 us).
     const size_t direct_max = switches().direct_max > 0 ? (size_t)switches().direct_max
                               : (s->ch == 1 || s->split) ? kPinnedMax : kHostRingChunk;
-    const bool direct = out_bytes <= direct_max && !pinned_ensure(&s->h_out, &s->h_out_bytes, out_bytes);
-    hipsoxr_job_t j;
-    std::memset(&j, 0, sizeof j);
-    j.in = s->d_in; j.out = direct ? s->h_out : s->d_out; j.elem = s->elem;
-    j.kernel = HIPSOXR_KERNEL_EXACT; // bit-exact chunk invariance
-    j.n_clips = 1; j.n_channels = s->ch;
-    if (!s->split) {
-        j.in_frame_stride = s->ch; j.in_chan_stride = 1;
-        j.out_frame_stride = s->ch; j.out_chan_stride = 1;
-    } else {
-        j.in_frame_stride = 1; j.in_chan_stride = (int64_t)s->in_cap;
-        j.out_frame_stride = 1; j.out_chan_stride = direct ? (int64_t)n : (int64_t)s->out_cap;
-    }
-    j.in_abs0 = s->in_base; j.in_frames = (int64_t)s->in_fill;
-    j.out_k0 = (int64_t)s->k_done; j.out_frames = (int64_t)n;
-    j.clip_counter = s->d_clips;
-    j.dither = (s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER)) ? 1u : 0u;
-    j.dither_seed = s->dither_seed;
-    if (s->in_fill == 0) { // nothing staged yet (e.g. flush of an empty stream): any valid pointer
-        j.in = s->d_out;
-    }
-    ChainDone cd;
-    cd.words = nullptr; cd.cap = 0; cd.seq = 0;
-    bool served = false;
-    const bool small_call = s->ring_on_host && direct && !s->split && s->in_fill > 0 && n <= 2048;
-    VrPos vp = {0, 0, 0, 0, 0, 0};
-    if (v.on) { // this launch's (or message's) clock: position and step at the first output, step increment while a slew lasts
-        const i128 T0 = v.pos(s->k_done), S0 = v.step(s->k_done), D = s->k_done < v.k_s + v.n_slew ? v.delta : 0;
-        vp = VrPos{(uint64_t)((u128)T0 >> 64), (uint64_t)(u128)T0, (uint64_t)((u128)S0 >> 64), (uint64_t)(u128)S0,
-                   (uint64_t)((u128)D >> 64), (uint64_t)(u128)D};
-    }
-    if (!s->resident && s->resident_auto_ok) {
-        const auto now = std::chrono::steady_clock::now();
-        const auto gap = std::chrono::microseconds(std::min(kResidentWatchdogUs, std::max(50, switches().resident_idle_us)) / 2);
+    *direct = out_bytes <= direct_max && !pinned_ensure(&s->h_out, &s->h_out_bytes, out_bytes);
+    return nullptr;
+}
+
+// Auto-resident streams (resident_auto_ok): count the run of small back-to-back calls that turns the resident path on,
+// and turn it off again where the run breaks.
+static void auto_resident_step(hipsoxr_stream *s, bool small_call)
+{
+    const bool counting = !s->resident && s->resident_auto_ok;
+    if (!counting && !s->resident_by_auto) return;
+    const auto now = std::chrono::steady_clock::now();
+    const auto gap = std::chrono::microseconds(resident_gap_us() / 2);
+    if (counting) {
         s->small_run = (small_call && (s->small_run == 0 || now - s->last_small < gap)) ? s->small_run + 1 : 0;
-        s->last_small = now;
         if (s->small_run >= kAutoResidentRun) s->resident = s->resident_by_auto = true;
-    } else if (s->resident_by_auto) {
+    } else if (!small_call || now - s->last_small >= gap || (s->res.running && s->res.box->exited == s->res.epoch)) {
         // a stream that turned resident by itself drops back the moment the run breaks: a call that is not small, one
         // that comes after a gap (its instance has idled out or is about to), or an instance that left on its own
-        const auto now = std::chrono::steady_clock::now();
-        const auto gap = std::chrono::microseconds(std::min(kResidentWatchdogUs, std::max(50, switches().resident_idle_us)) / 2);
-        if (!small_call || now - s->last_small >= gap || (s->res.running && s->res.box->exited == s->res.epoch)) {
-            resident_stop(s);
-            s->resident = s->resident_by_auto = false;
-            s->small_run = small_call ? 1 : 0;
-        }
-        s->last_small = now;
+        resident_stop(s);
+        s->resident = s->resident_by_auto = false;
+        s->small_run = small_call ? 1 : 0;
     }
-    if (s->resident && small_call) {
-        if (const char *e = resident_emit(s, j, &served, v.on ? &vp : nullptr)) return e;
-    }
-    if (served) {
-        std::memcpy(out, s->h_out, out_bytes);
-        s->k_done += n;
-        return nullptr;
-    }
+    s->last_small = now;
+}
+
+// The ordinary path of an emission: launch the job and — direct results — wait until they are in s->h_out.
+static const char *emit_launch(hipsoxr_stream *s, const hipsoxr_job_t &j, const VrPos *vp, bool direct)
+{
     resident_stop(s);
     if (direct && !s->h_done && !switches().no_done_words &&
         hipHostMalloc((void **)&s->h_done, kDoneWords * sizeof(uint32_t), hipHostMallocDefault) == hipSuccess)
         std::memset(s->h_done, 0, kDoneWords * sizeof(uint32_t));
+    ChainDone cd;
     cd.words = s->h_done; cd.cap = s->h_done && direct ? kDoneWords : 0; cd.seq = ++s->done_seq;
-    if (v.on) {
-        if (const char *e = launch_job(&s->plan->p, j, s->st, &vp, nullptr, cd.cap ? &cd : nullptr)) return e;
-    } else {
-        if (const char *e = launch_job(&s->plan->p, j, s->st, nullptr, nullptr, cd.cap ? &cd : nullptr)) return e;
+    if (const char *e = launch_job(&s->plan->p, j, s->st, vp, nullptr, cd.cap ? &cd : nullptr)) return e;
+    if (!direct) return nullptr; // (the copy out of device memory queues behind the launch, and the wait covers both)
+    bool seen = false;
+    if (cd.n_wgs) { // the kernel reports by itself (ChainDone): no event
+        unsigned next = 0;
+        for (uint64_t spin = 0; !seen && spin < (1ULL << 22); ++spin) { // (~10 ms: then the ordinary wait, which also reports errors)
+            seen = done_words_seen(cd.words, cd.n_wgs, cd.seq, &next);
+            if (!seen) __builtin_ia32_pause();
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
     }
+    if (!seen) HIP_TRY(stream_wait(s));
+    return nullptr;
+}
+
+// n frames to the caller: out of s->h_out (direct: they are there), or out of device memory with a copy and the wait
+static const char *emit_copy_out(hipsoxr_stream *s, void *out, size_t n, bool direct)
+{
+    void *const *chans = (void *const *)out; // (split layouts)
     if (direct) {
-        bool seen = false;
-        if (cd.n_wgs) { // the kernel reports by itself (ChainDone): no event
-            volatile uint32_t *w = cd.words;
-            unsigned next = 0;
-            for (uint64_t spin = 0; spin < (1ULL << 22); ++spin) { // (~10 ms: then the ordinary wait, which also reports errors)
-                while (next < cd.n_wgs && w[next] == cd.seq) ++next;
-                if (next == cd.n_wgs) { seen = true; break; }
-                __builtin_ia32_pause();
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        }
-        if (!seen) HIP_TRY(stream_wait(s));
-        if (!s->split) {
-            std::memcpy(out, s->h_out, out_bytes);
-        } else {
-            void *const *chans = (void *const *)out;
-            for (unsigned c = 0; c < s->ch; ++c)
-                std::memcpy(chans[c], (char *)s->h_out + (size_t)c * n * esz(s), n * esz(s));
-        }
-    } else if (!s->split) {
-        HIP_TRY(hipMemcpyAsync(out, s->d_out, out_bytes, hipMemcpyDeviceToHost, s->st));
-        HIP_TRY(stream_wait(s));
+        if (!s->split) std::memcpy(out, s->h_out, n * s->ch * esz(s));
+        else for (unsigned c = 0; c < s->ch; ++c) std::memcpy(chans[c], (char *)s->h_out + (size_t)c * n * esz(s), n * esz(s));
+        return nullptr;
+    }
+    if (!s->split) {
+        HIP_TRY(hipMemcpyAsync(out, s->d_out, n * s->ch * esz(s), hipMemcpyDeviceToHost, s->st));
     } else {
-        void *const *chans = (void *const *)out;
         for (unsigned c = 0; c < s->ch; ++c)
             HIP_TRY(hipMemcpyAsync(chans[c], (char *)s->d_out + (size_t)c * s->out_cap * esz(s), n * esz(s),
                                    hipMemcpyDeviceToHost, s->st));
-        HIP_TRY(stream_wait(s));
     }
+    HIP_TRY(stream_wait(s));
+    return nullptr;
+}
+
+// Emit up to olen frames (host destination), one launch or one message to the resident kernel.
+static const char *stream_emit_once(hipsoxr_stream *s, void *out, size_t olen, size_t *odone)
+{
+    const size_t n = emit_count(s->plan->p, s->vr, s->n_in_total, s->k_done, s->ended, olen);
+    *odone = n;
+    if (n == 0) {
+        // the caller's input buffer is borrowed only for the call; a host ring took its copy with memcpy, nothing is queued
+        if (!s->res.running && !s->ring_on_host) HIP_TRY(stream_wait(s));
+        return nullptr;
+    }
+    bool direct = false;
+    if (const char *e = emit_target(s, n, &direct)) return e;
+    hipsoxr_job_t j = stream_job(s, direct ? s->h_out : s->d_out, n, direct ? (int64_t)n : (int64_t)s->out_cap);
+    if (s->in_fill == 0) j.in = s->d_out; // nothing staged yet (e.g. flush of an empty stream): any valid pointer
+    const bool small_call = s->ring_on_host && direct && !s->split && s->in_fill > 0 && n <= 2048;
+    VrPos clock;
+    const VrPos *vp = stream_clock(s, &clock);
+    auto_resident_step(s, small_call);
+    bool served = false;
+    if (s->resident && small_call)
+        if (const char *e = resident_emit(s, j, &served, vp)) return e;
+    if (!served)
+        if (const char *e = emit_launch(s, j, vp, direct)) return e;
+    if (const char *e = emit_copy_out(s, out, n, direct)) return e;
     s->k_done += n;
     return nullptr;
+}
+
+static const char *stream_emit(hipsoxr_stream *s, void *out, size_t olen, size_t *odone)
+{
+    if (!s->vr.on) return stream_emit_once(s, out, olen, odone); // (one pass, and no table of plane pointers to make)
+    return emit_passes<stream_emit_once>(s, 4, out, olen, odone);
 }
 
 // Deferred output.  The reference's contract lets a call return any number of frames, including none
@@ -1035,27 +987,15 @@ static const char *stream_process_deferred(hipsoxr_stream *s, const void *in, si
         const int b = (int)(s->calls & 1);
         const size_t bytes = ilen * frame;
         if (s->ring_on_host || ((!s->split || !s->d_in) && s->n_in_total == 0 && bytes <= kHostRingChunk && !switches().no_host_ring)) {
-            if (const char *e = stream_append(s, in, ilen)) return e; // host ring: a memcpy, nothing in flight to protect
+            if (const char *e = stream_append(s, in, ilen, &s->h_in, &s->h_in_bytes)) return e; // host ring: a memcpy, nothing in flight to protect
         } else if (bytes <= kPinnedMax && (!s->ev_src[b] || hipEventSynchronize(s->ev_src[b]) == hipSuccess) &&
                    !pinned_ensure(&s->h_src[b], &s->h_src_bytes[b], bytes)) {
-            if (s->in_fill + ilen > s->in_cap) { // retire / grow the ring exactly as stream_append does
-                void *keep_h = s->h_in; size_t keep_b = s->h_in_bytes;
-                s->h_in = s->h_src[b]; s->h_in_bytes = s->h_src_bytes[b];
-                const char *e = stream_append(s, in, ilen);
-                s->h_src[b] = s->h_in; s->h_src_bytes[b] = s->h_in_bytes;
-                s->h_in = keep_h; s->h_in_bytes = keep_b;
-                if (e) return e;
-            } else {
-                std::memcpy(s->h_src[b], in, bytes);
-                HIP_TRY(hipMemcpyAsync((char *)s->d_in + s->in_fill * frame, s->h_src[b], bytes, hipMemcpyHostToDevice, s->st));
-                s->in_fill += ilen;
-                s->n_in_total += ilen;
-            }
+            if (const char *e = stream_append(s, in, ilen, &s->h_src[b], &s->h_src_bytes[b])) return e;
             if (!s->ev_src[b] && hipEventCreateWithFlags(&s->ev_src[b], hipEventDisableTiming) != hipSuccess) s->ev_src[b] = nullptr;
             if (s->ev_src[b]) HIP_TRY(hipEventRecord(s->ev_src[b], s->st));
             else HIP_TRY(hipStreamSynchronize(s->st));
         } else {
-            if (const char *e = stream_append(s, in, ilen)) return e;
+            if (const char *e = stream_append(s, in, ilen, &s->h_in, &s->h_in_bytes)) return e;
             HIP_TRY(stream_wait(s)); // large chunk straight from the caller's (borrowed) buffer
         }
         ++s->calls;
@@ -1063,8 +1003,7 @@ static const char *stream_process_deferred(hipsoxr_stream *s, const void *in, si
     // 3. launch for what is computable now, once the previous result is fully handed out
     if (s->pend_off == s->pend_n) {
         s->pend_n = s->pend_off = 0;
-        const uint64_t k_end = k_avail(p, s->n_in_total);
-        size_t n = k_end > s->k_done ? (size_t)(k_end - s->k_done) : 0;
+        const size_t n = emit_count(p, s->n_in_total, s->k_done, false, SIZE_MAX); // everything due: the result buffer is sized to it
         if (n * frame > kPinnedMax) {
             // More than one pinned result buffer holds (chunks whose output exceeds 1 MiB, or a backlog left by a
             // caller who drained slowly): one capped launch per call would fall behind by the excess on every call
@@ -1080,18 +1019,7 @@ static const char *stream_process_deferred(hipsoxr_stream *s, const void *in, si
         if (n && !pinned_ensure(&s->h_res[slot], &s->h_res_bytes[slot], n * frame)) {
             if (!s->ev_res[slot] && hipEventCreateWithFlags(&s->ev_res[slot], hipEventDisableTiming) != hipSuccess)
                 s->ev_res[slot] = nullptr;
-            hipsoxr_job_t j;
-            std::memset(&j, 0, sizeof j);
-            j.in = s->d_in; j.out = s->h_res[slot]; j.elem = s->elem;
-            j.kernel = HIPSOXR_KERNEL_EXACT;
-            j.n_clips = 1; j.n_channels = s->ch;
-            j.in_frame_stride = s->ch; j.in_chan_stride = 1;
-            j.out_frame_stride = s->ch; j.out_chan_stride = 1;
-            j.in_abs0 = s->in_base; j.in_frames = (int64_t)s->in_fill;
-            j.out_k0 = (int64_t)s->k_done; j.out_frames = (int64_t)n;
-            j.clip_counter = s->d_clips;
-            j.dither = (s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER)) ? 1u : 0u;
-            j.dither_seed = s->dither_seed;
+            const hipsoxr_job_t j = stream_job(s, s->h_res[slot], n, 1);
             if (const char *e = launch_job(&s->plan->p, j, s->st)) return e;
             if (s->ev_res[slot]) HIP_TRY(hipEventRecord(s->ev_res[slot], s->st));
             s->k_done += n;
@@ -1100,6 +1028,19 @@ static const char *stream_process_deferred(hipsoxr_stream *s, const void *in, si
     }
     *odone = got;
     return nullptr;
+}
+
+// The split adapter's boundary: n frames of ch planes woven into one interleaved signal, and back.  E = bytes per sample, a
+// constant: the memcpy is then a plain move.
+template <size_t E> static void weave(char *dst, const void *const *planes, size_t ch, size_t n)
+{
+    for (size_t c = 0; c < ch; ++c)
+        for (size_t f = 0; f < n; ++f) std::memcpy(dst + (f * ch + c) * E, (const char *)planes[c] + f * E, E);
+}
+template <size_t E> static void unweave(void *const *planes, const char *src, size_t ch, size_t n)
+{
+    for (size_t c = 0; c < ch; ++c)
+        for (size_t f = 0; f < n; ++f) std::memcpy((char *)planes[c] + f * E, src + (f * ch + c) * E, E);
 }
 
 static const char *stream_new(hipsoxr_plan *plan, bool own, unsigned ch, hipsoxr_datatype_t io,
@@ -1269,31 +1210,11 @@ static const char *stream_process_inner(hipsoxr_stream *s, const void *in, size_
 // the call it stands in for the stream's own).  Nothing waits.
 static const char *device_emit_once(hipsoxr_stream *s, void *d_out, size_t olen, size_t *odone)
 {
-    const Plan &p = s->plan->p;
-    VrState &v = s->vr;
-    if (v.on && v.n_slew && s->k_done >= v.k_s + v.n_slew) { // slew finished: renormalise to a constant segment
-        const uint64_t k1 = v.k_s + v.n_slew;
-        v.t_s = v.pos(k1); v.k_s = k1; v.s0 = v.s1; v.delta = 0; v.n_slew = 0;
-    }
-    const uint64_t k_end = v.on ? vr_k_limit(s, s->ended)
-                                : s->ended ? plan_out_len(p, s->n_in_total) : k_avail(p, s->n_in_total);
-    size_t n = 0;
-    if (k_end > s->k_done) n = (size_t)std::min<uint64_t>(k_end - s->k_done, olen);
-    if (v.on && v.n_slew && s->k_done + n > v.k_s + v.n_slew) n = (size_t)(v.k_s + v.n_slew - s->k_done); // one quadratic per launch
+    const size_t n = emit_count(s->plan->p, s->vr, s->n_in_total, s->k_done, s->ended, olen);
     *odone = n;
     if (n == 0) return nullptr;
-    hipsoxr_job_t j;
-    std::memset(&j, 0, sizeof j);
-    j.in = s->in_fill ? s->d_in : d_out; j.out = d_out; j.elem = s->elem;
-    j.kernel = HIPSOXR_KERNEL_EXACT;
-    j.n_clips = 1; j.n_channels = s->ch;
-    j.in_frame_stride = s->ch; j.in_chan_stride = 1;
-    j.out_frame_stride = s->ch; j.out_chan_stride = 1;
-    j.in_abs0 = s->in_base; j.in_frames = (int64_t)s->in_fill;
-    j.out_k0 = (int64_t)s->k_done; j.out_frames = (int64_t)n;
-    j.clip_counter = s->d_clips;
-    j.dither = (s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER)) ? 1u : 0u;
-    j.dither_seed = s->dither_seed;
+    hipsoxr_job_t j = stream_job(s, d_out, n, 1);
+    if (!s->in_fill) j.in = d_out; // (an empty ring: any valid pointer)
     if (s->fft) {
         // the chunk's outputs as a job window on the frequency-domain engine — every emission, whatever its size (a
         // 10-frame call is legal and merely wasteful); not served = an error, never the exact engine
@@ -1301,32 +1222,11 @@ static const char *device_emit_once(hipsoxr_stream *s, void *d_out, size_t olen,
         j.kernel = (s->elem == HIPSOXR_I16 || s->elem == HIPSOXR_I32) ? HIPSOXR_KERNEL_FFT_PCM : HIPSOXR_KERNEL_FFT;
         if (const char *e = launch_fft_window(&s->plan->p, j, s->st, &handled)) return e;
         if (!handled) return "STREAM_FFT stream: the frequency-domain engine cannot serve this call (plan or layout outside its paired kernels)";
-    } else if (v.on) {
-        const i128 T0 = v.pos(s->k_done), S0 = v.step(s->k_done), D = s->k_done < v.k_s + v.n_slew ? v.delta : 0;
-        const VrPos vp = {(uint64_t)((u128)T0 >> 64), (uint64_t)(u128)T0, (uint64_t)((u128)S0 >> 64), (uint64_t)(u128)S0,
-                          (uint64_t)((u128)D >> 64), (uint64_t)(u128)D};
-        if (const char *e = launch_job(&s->plan->p, j, s->st, &vp, nullptr, nullptr)) return e;
     } else {
-        if (const char *e = launch_job(&s->plan->p, j, s->st, nullptr, nullptr, nullptr)) return e;
+        VrPos clock;
+        if (const char *e = launch_job(&s->plan->p, j, s->st, stream_clock(s, &clock), nullptr, nullptr)) return e;
     }
     s->k_done += n;
-    return nullptr;
-}
-
-// Room in the device ring for `ilen` more frames (retire consumed input first; grow — power of two, room for four chunks,
-// so that compaction runs every fourth call — only if that is not enough).  Enqueues on s->st.
-static const char *device_ring_reserve(hipsoxr_stream *s, size_t ilen)
-{
-    if (s->ring_on_host) { if (const char *e = host_ring_to_device(s)) return e; } // (a ring inherited from a small-chunk stream)
-    if (s->in_fill + ilen > s->in_cap) {
-        const int64_t n0 = first_needed(s);
-        const int64_t keep_from = std::min<int64_t>(std::max<int64_t>(n0, s->in_base), s->in_base + (int64_t)s->in_fill);
-        const size_t keep = s->in_fill - (size_t)(keep_from - s->in_base);
-        size_t need = keep + 4 * ilen, cap = std::max<size_t>(s->in_cap, 1024);
-        if (need > ((size_t)1 << 24)) need = keep + ilen;
-        while (cap < need) cap <<= 1;
-        if (const char *e = stream_compact(s, cap)) return e;
-    }
     return nullptr;
 }
 
@@ -1343,20 +1243,15 @@ static bool stream_item_prepare(hipsoxr_stream *s, const void *d_in, size_t ilen
     const Plan &p = s->plan->p;
     *err = nullptr;
     if (s->vr.on || s->ended || !d_in || !ilen || !d_out || s->ring_on_host || s->split || s->fft) return false; // (fft: the small-launch kernel is the exact engine)
-    const uint64_t n_total = s->n_in_total + ilen;
-    const uint64_t k_end = k_avail(p, n_total);
-    const size_t n = k_end > s->k_done ? (size_t)std::min<uint64_t>(k_end - s->k_done, olen) : 0;
+    const size_t n = emit_count(p, s->n_in_total + ilen, s->k_done, false, olen); // (counted with this call's chunk in)
     if (n >= 4096) return false;
     it->ring = s->d_in; it->ring_dst = s->d_in; it->keep_from = 0;
     if (s->in_fill + ilen > s->in_cap || !s->d_in) { // the ring moves: keep [first frame the next output needs, end), into the other buffer
-        const int64_t n0 = first_needed(s);
-        const int64_t keep_from = std::min<int64_t>(std::max<int64_t>(n0, s->in_base), s->in_base + (int64_t)s->in_fill);
-        const size_t keep = s->in_fill - (size_t)(keep_from - s->in_base);
+        const RingKeep k = stream_keep(s);
         // room for sixteen SMALL chunks (the move then runs every ~16th call), for four of the larger ones (advisor, round 5: both
         // buffers of a stream end up at this capacity — with thousands of grouped streams the factor is memory)
-        size_t need = keep + std::min<size_t>(16 * ilen, std::max<size_t>(4 * ilen, 65536)), cap = std::max<size_t>(s->in_cap, 1024);
-        if (need > ((size_t)1 << 24)) need = keep + ilen;
-        while (cap < need) cap <<= 1;
+        const size_t room = std::min<size_t>(16 * ilen, std::max<size_t>(4 * ilen, 65536));
+        const size_t cap = ring_grow_bounded(s->in_cap, k.keep, room, ilen);
         if (s->alt_cap < cap || !s->d_in_alt) {
             if (s->d_in_alt && hipFree(s->d_in_alt) != hipSuccess) { *err = "hipFree failed"; return false; }
             s->d_in_alt = nullptr; s->alt_cap = 0;
@@ -1364,7 +1259,7 @@ static bool stream_item_prepare(hipsoxr_stream *s, const void *d_in, size_t ilen
             s->alt_cap = cap;
         }
         it->ring_dst = s->d_in_alt;
-        it->keep_from = keep_from - s->in_base;
+        it->keep_from = (int64_t)k.drop;
         if (!s->d_in) it->ring = s->d_in_alt; // (first call: nothing to keep, and the launch reads only the chunk)
     }
     it->chunk = d_in; it->out = d_out; it->clip_counter = s->d_clips;
@@ -1396,15 +1291,13 @@ static const char *device_process(hipsoxr_stream *s, const void *d_in, size_t il
         s->ended = true;
     } else if (ilen > 0) {
         if (s->ended) return "Input after last input";
-        if (s->ring_on_host) { if (const char *e = host_ring_to_device(s)) return e; } // (a ring inherited from a small-chunk stream)
         {   // one dispatch: the small-launch kernel appends the chunk (and moves a full ring) itself
             ChainItem it;
             size_t n = 0;
             const char *perr = nullptr;
             if (stream_item_prepare(s, d_in, ilen, d_out, olen, &it, &n, &perr)) {
                 bool handled = false;
-                const bool dither = s->elem == HIPSOXR_I16 && !(s->flags & HIPSOXR_NO_DITHER);
-                if (const char *e = launch_chain_items(&s->plan->p, s->elem, s->ch, dither, &it, nullptr, 1, s->st, &handled)) return e;
+                if (const char *e = launch_chain_items(&s->plan->p, s->elem, s->ch, stream_dither(s), &it, nullptr, 1, s->st, &handled)) return e;
                 if (handled) {
                     stream_item_commit(s, it, ilen, n);
                     *odone = n;
@@ -1418,16 +1311,31 @@ static const char *device_process(hipsoxr_stream *s, const void *d_in, size_t il
         s->in_fill += ilen;
         s->n_in_total += ilen;
     }
-    size_t total = 0;
-    while (d_out && total < olen) {
-        size_t got = 0;
-        if (const char *e = device_emit_once(s, (char *)d_out + total * frame, olen - total, &got)) return e;
-        total += got;
-        if (!got) break;
-        if (!(s->vr.on && s->vr.n_slew && s->k_done == s->vr.k_s + s->vr.n_slew)) break; // another pass only at the end of a slew
+    return emit_passes<device_emit_once>(s, ~0u, d_out, olen, odone);
+}
+
+// Stream-order bookkeeping of a device call on the caller's HIP stream `user`.
+// Ordering against the stream's OWN HIP stream, where host-pointer calls and the pool put their work: what such calls
+// left there comes first (one event, only when there was such a call since the last device call); the other way
+// round — device calls still in flight when a host-pointer call, clear or delete arrives — `ext_sync` waits.
+// chunk: the call appends input — a ring in host memory (inherited from a small-chunk stream) moves to the device first,
+// with `user` standing in for the stream's own HIP stream.
+static inline const char *device_call_enter(hipsoxr_stream *s, hipStream_t user, bool chunk)
+{
+    resident_stop(s);
+    hipStream_t own = s->st;
+    if (user != own && s->own_used && s->ev) {
+        HIP_TRY(hipEventRecord(s->ev, own));
+        HIP_TRY(hipStreamWaitEvent(user, s->ev, 0));
     }
-    *odone = total;
-    return nullptr;
+    s->own_used = false;
+    if (s->ext_st && s->ext_st != user) HIP_TRY(hipStreamSynchronize(s->ext_st)); // (a different caller stream than last time)
+    s->ext_st = user; s->ext_pending = true;
+    if (!chunk || !s->ring_on_host) return nullptr;
+    s->st = user;
+    const char *e = host_ring_to_device(s);
+    s->st = own;
+    return e;
 }
 
 hipsoxr_error_t hipsoxr_stream_process_device(hipsoxr_stream_t *s, const void *in, size_t ilen, void *out, size_t olen,
@@ -1438,18 +1346,8 @@ hipsoxr_error_t hipsoxr_stream_process_device(hipsoxr_stream_t *s, const void *i
     if (s->split || s->split_io || s->defer || (s->flags & (HIPSOXR_RESIDENT | HIPSOXR_AUTO_RESIDENT)))
         return "device chunks: interleaved streams without the deferred / resident flags only";
     DeviceGuard guard(s->device);
-    resident_stop(s);
     hipStream_t own = s->st, user = (hipStream_t)hip_stream;
-    // Ordering against the stream's OWN HIP stream, where host-pointer calls and the pool put their work: what such calls
-    // left there comes first (one event, only when there was such a call since the last device call); the other way
-    // round — device calls still in flight when a host-pointer call, clear or delete arrives — `ext_sync` waits.
-    if (user != own && s->own_used && s->ev) {
-        HIP_TRY(hipEventRecord(s->ev, own));
-        HIP_TRY(hipStreamWaitEvent(user, s->ev, 0));
-    }
-    s->own_used = false;
-    if (s->ext_st && s->ext_st != user) HIP_TRY(hipStreamSynchronize(s->ext_st)); // (a different caller stream than last time)
-    s->ext_st = user; s->ext_pending = true;
+    if (const char *e = device_call_enter(s, user, in && ilen && !s->ended)) return e;
     s->st = user;
     const char *err = device_process(s, in, ilen, out, olen, odone);
     s->st = own;
@@ -1554,25 +1452,8 @@ hipsoxr_error_t hipsoxr_streams_process_device(hipsoxr_stream_t *const *handles,
     }
     DeviceGuard guard(s0->device);
     hipStream_t user = (hipStream_t)hip_stream;
-    // stream-order bookkeeping of every handle, as in hipsoxr_stream_process_device
-    for (size_t i = 0; i < n; ++i) {
-        hipsoxr_stream *s = handles[i];
-        resident_stop(s);
-        if (user != s->st && s->own_used && s->ev) {
-            HIP_TRY(hipEventRecord(s->ev, s->st));
-            HIP_TRY(hipStreamWaitEvent(user, s->ev, 0));
-        }
-        s->own_used = false;
-        if (s->ext_st && s->ext_st != user) HIP_TRY(hipStreamSynchronize(s->ext_st));
-        s->ext_st = user; s->ext_pending = true;
-        if (s->ring_on_host) {                          // (a ring inherited from a small-chunk stream)
-            hipStream_t own = s->st;
-            s->st = user;
-            const char *e = host_ring_to_device(s);
-            s->st = own;
-            if (e) return e;
-        }
-    }
+    for (size_t i = 0; i < n; ++i)
+        if (const char *e = device_call_enter(handles[i], user, true)) return e;
     ItemArena &ar = item_arena(s0->device);
     std::lock_guard<std::mutex> lk(ar.mu);
     ChainItem *host = nullptr, *dev = nullptr, *mirror = nullptr;
@@ -1584,9 +1465,8 @@ hipsoxr_error_t hipsoxr_streams_process_device(hipsoxr_stream_t *const *handles,
     if (perr) return perr;
     bool handled = false;
     if (all) {
-        const bool dither = s0->elem == HIPSOXR_I16 && !(s0->flags & HIPSOXR_NO_DITHER);
         if (const char *e = launch_copy(mirror, dev, n * sizeof(ChainItem), user)) return e;
-        if (const char *e = launch_chain_items(&s0->plan->p, s0->elem, s0->ch, dither, host, mirror, (uint32_t)n, user, &handled)) return e;
+        if (const char *e = launch_chain_items(&s0->plan->p, s0->elem, s0->ch, stream_dither(s0), host, mirror, (uint32_t)n, user, &handled)) return e;
     }
     if (!handled) { // (a stream with too many outputs due, or a plan the small-launch kernel does not take)
         for (size_t i = 0; i < n; ++i)
@@ -1632,12 +1512,10 @@ hipsoxr_error_t hipsoxr_stream_process(hipsoxr_stream_t *s, const void *in, size
     if (in) {
         s->ad_in.resize(std::max<size_t>(ilen * ch * e, 1));
         const void *const *planes = (const void *const *)in;
-        for (size_t c = 0; c < ch; ++c) {
-            const char *src = (const char *)planes[c];
-            char *dst = s->ad_in.data() + c * e;
-            if (e == 4) for (size_t f = 0; f < ilen; ++f) std::memcpy(dst + f * ch * 4, src + f * 4, 4);
-            else if (e == 2) for (size_t f = 0; f < ilen; ++f) std::memcpy(dst + f * ch * 2, src + f * 2, 2);
-            else for (size_t f = 0; f < ilen; ++f) std::memcpy(dst + f * ch * 8, src + f * 8, 8);
+        switch (e) {
+        case 2: weave<2>(s->ad_in.data(), planes, ch, ilen); break;
+        case 4: weave<4>(s->ad_in.data(), planes, ch, ilen); break;
+        default: weave<8>(s->ad_in.data(), planes, ch, ilen);
         }
         in_i = s->ad_in.data();
     }
@@ -1646,13 +1524,10 @@ hipsoxr_error_t hipsoxr_stream_process(hipsoxr_stream_t *s, const void *in, size
     if (const char *err = stream_process_inner(s, in_i, ilen, out_i, olen, odone)) return err;
     if (out_i && *odone) {
         void *const *planes = (void *const *)out;
-        const size_t n = *odone;
-        for (size_t c = 0; c < ch; ++c) {
-            char *dst = (char *)planes[c];
-            const char *src = s->ad_out.data() + c * e;
-            if (e == 4) for (size_t f = 0; f < n; ++f) std::memcpy(dst + f * 4, src + f * ch * 4, 4);
-            else if (e == 2) for (size_t f = 0; f < n; ++f) std::memcpy(dst + f * 2, src + f * ch * 2, 2);
-            else for (size_t f = 0; f < n; ++f) std::memcpy(dst + f * 8, src + f * ch * 8, 8);
+        switch (e) {
+        case 2: unweave<2>(planes, s->ad_out.data(), ch, *odone); break;
+        case 4: unweave<4>(planes, s->ad_out.data(), ch, *odone); break;
+        default: unweave<8>(planes, s->ad_out.data(), ch, *odone);
         }
     }
     return nullptr;
@@ -1679,7 +1554,7 @@ static const char *stream_process_inner(hipsoxr_stream *s, const void *in, size_
         s->ended = true; // end of input: flush
     } else if (ilen > 0) {
         if (s->ended) return "Input after last input";
-        if (const char *e = stream_append(s, in, ilen)) return e;
+        if (const char *e = stream_append(s, in, ilen, &s->h_in, &s->h_in_bytes)) return e;
     }
     if (olen == 0 || out == nullptr) {
         if (in && ilen && !s->res.running && !s->ring_on_host) HIP_TRY(stream_wait(s)); // host buffer is borrowed only for the call
@@ -1780,7 +1655,7 @@ hipsoxr_error_t hipsoxr_oneshot(double in_rate, double out_rate, unsigned num_ch
     if (const char *e = hipsoxr_stream_create(in_rate, out_rate, num_channels, io_type, recipe, flags, &s))
         return e;
     const char *err = nullptr;
-    if (ilen) err = stream_append(s, in, ilen);
+    if (ilen) err = stream_append(s, in, ilen, &s->h_in, &s->h_in_bytes);
     s->ended = true; // whole signal known: a single launch covers body and tail
     if (!err && olen && out) err = stream_emit(s, out, olen, odone);
     else if (!err) err = (hipStreamSynchronize(s->st) == hipSuccess) ? nullptr : "hip sync failed";

@@ -1,0 +1,233 @@
+// stream_rules_check.cpp — the stream layer's pure rules (python-soxr_amd/csrc/stream_rules.h) against slow, independent
+// statements of them.  No device: links plan.cpp alone.  Exit status 0 = every check held (tests/test_stream_rules.py).
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "plan.h"
+#include "stream_rules.h"
+
+using namespace hipsoxr;
+
+namespace hipsoxr {
+Plan::~Plan() {} // (the library's destructor releases device tables: there are none here)
+}
+
+static long g_checks = 0, g_failed = 0;
+#define CHECK(cond, ...)                                                                   \
+    do {                                                                                   \
+        ++g_checks;                                                                        \
+        if (!(cond)) {                                                                     \
+            if (++g_failed <= 20) { std::printf("FAILED %s:%d  %s  ", __FILE__, __LINE__, #cond); std::printf(__VA_ARGS__); std::printf("\n"); } \
+        }                                                                                  \
+    } while (0)
+
+static int64_t gcd(int64_t a, int64_t b) { return b ? gcd(b, a % b) : a; }
+
+// ---- k_avail: the count of k >= 0 with floor(k M / L) + T/2 <= N - 1 (the condition is monotonic in k) ----
+static uint64_t k_avail_slow(int64_t L, int64_t M, int32_t T, int64_t N)
+{
+    uint64_t k = 0;
+    while ((int64_t)k * M / L + T / 2 <= N - 1) ++k;
+    return k;
+}
+
+static void check_k_avail()
+{
+    Plan p;
+    const int32_t taps[3] = {2, 8, 30};
+    for (int64_t L = 1; L <= 12; ++L)
+        for (int64_t M = 1; M <= 12; ++M) {
+            if (gcd(L, M) != 1) continue;
+            for (int32_t T : taps)
+                for (int64_t N = 0; N <= 200; ++N) {
+                    p.L = L; p.M = M; p.T = T;
+                    const uint64_t got = k_avail(p, (uint64_t)N), want = k_avail_slow(L, M, T, N);
+                    CHECK(got == want, "k_avail L=%ld M=%ld T=%d N=%ld: %lu, brute force %lu", (long)L, (long)M, T, (long)N, (unsigned long)got, (unsigned long)want);
+                }
+        }
+    // the product's ratios at the tap counts their designs have
+    const double rates[4][2] = {{44100, 48000}, {48000, 44100}, {44100, 16000}, {16000, 48000}};
+    const int64_t lm[4][2] = {{160, 147}, {147, 160}, {160, 441}, {3, 1}};
+    for (int r = 0; r < 4; ++r) {
+        Plan q;
+        const char *e = plan_design(rates[r][0], rates[r][1], /*HQ*/ 4, &q);
+        CHECK(!e && q.L == lm[r][0] && q.M == lm[r][1] && q.phases == 0, "plan %g -> %g: %s L=%ld M=%ld", rates[r][0], rates[r][1], e ? e : "ok", (long)q.L, (long)q.M);
+        if (e) continue;
+        for (int64_t N = 0; N <= 3000; ++N) {
+            const uint64_t got = k_avail(q, (uint64_t)N), want = k_avail_slow(q.L, q.M, q.T, N);
+            CHECK(got == want, "k_avail %ld/%ld T=%d N=%ld: %lu, brute force %lu", (long)q.L, (long)q.M, q.T, (long)N, (unsigned long)got, (unsigned long)want);
+        }
+    }
+}
+
+// ---- ring_keep ----
+static void check_ring_keep()
+{
+    const int64_t bases[5] = {0, -37, 3, 1000, (int64_t)1 << 40}; // (the frequency-domain origin can be negative)
+    for (int64_t in_base : bases)
+        for (int64_t in_fill = 0; in_fill <= 20; ++in_fill)
+            for (int64_t fn = in_base - 5; fn <= in_base + in_fill + 5; ++fn) {
+                const RingKeep k = ring_keep(fn, in_base, (size_t)in_fill);
+                CHECK(in_base <= k.keep_from && k.keep_from <= in_base + in_fill, "keep_from %ld outside [%ld, %ld]", (long)k.keep_from, (long)in_base, (long)(in_base + in_fill));
+                if (fn >= in_base && fn <= in_base + in_fill) CHECK(k.keep_from == fn, "keep_from %ld, first needed %ld lies inside", (long)k.keep_from, (long)fn);
+                CHECK((int64_t)(k.drop + k.keep) == in_fill, "drop %zu + keep %zu != fill %ld", k.drop, k.keep, (long)in_fill);
+                CHECK((int64_t)k.drop == k.keep_from - in_base, "drop %zu, keep_from - base %ld", k.drop, (long)(k.keep_from - in_base));
+            }
+}
+
+// ---- ring_grow / ring_grow_bounded: start value times a power of two, the smallest that is enough ----
+static void check_grown(size_t cap, size_t in_cap, size_t need, const char *what)
+{
+    const size_t start = in_cap > 1024 ? in_cap : 1024;
+    CHECK(cap >= in_cap, "%s: cap %zu below in_cap %zu", what, cap, in_cap);
+    CHECK(cap % start == 0 && ((cap / start) & (cap / start - 1)) == 0, "%s: cap %zu is no power of two times %zu", what, cap, start);
+    CHECK(cap >= need, "%s: cap %zu < need %zu", what, cap, need);
+    CHECK(cap == start || cap / 2 < need, "%s: cap %zu is not the smallest (need %zu, start %zu)", what, cap, need, start);
+}
+
+static void check_ring_grow()
+{
+    const size_t caps[] = {0, 1, 1000, 1024, 1025, 3000, 4096, 100000, (size_t)1 << 24, ((size_t)1 << 24) + 7, (size_t)3 << 23};
+    const size_t keeps[] = {0, 1, 37, 1023, 1024, 5000, 1 << 20, ((size_t)1 << 24) - 1000, (size_t)1 << 24, ((size_t)1 << 24) + 5, (size_t)1 << 26};
+    const size_t ilens[] = {1, 7, 441, 4410, 20000, 1 << 20, 5 << 20};
+    const size_t factors[] = {1, 4, 8, 16};
+    for (size_t in_cap : caps)
+        for (size_t keep : keeps)
+            for (size_t ilen : ilens)
+                for (size_t f : factors) {
+                    const size_t room = f * ilen;
+                    check_grown(ring_grow(in_cap, keep, room), in_cap, keep + room, "ring_grow"); // (no fallback, however large)
+                    const size_t need = keep + room > ((size_t)1 << 24) ? keep + ilen : keep + room;
+                    check_grown(ring_grow_bounded(in_cap, keep, room, ilen), in_cap, need, "ring_grow_bounded");
+                }
+}
+
+// ---- emit_count, constant rate ----
+static void check_emit_count_constant()
+{
+    Plan p;
+    const int64_t lm[5][2] = {{160, 147}, {147, 160}, {2, 3}, {3, 1}, {1, 7}};
+    const size_t olens[] = {0, 1, 64, 100, 441, (size_t)-1};
+    for (auto &r : lm)
+        for (int32_t T : {2, 8, 30}) {
+            p.L = r[0]; p.M = r[1]; p.T = T;
+            for (uint64_t N = 0; N <= 600; N += (N < 40 ? 1 : 13)) {
+                const uint64_t avail = k_avail_slow(p.L, p.M, p.T, (int64_t)N), total = plan_out_len(p, N);
+                for (uint64_t k_done = 0; k_done <= avail + 2; k_done += (k_done < 5 ? 1 : 17))
+                    for (size_t olen : olens) {
+                        const uint64_t due = avail > k_done ? avail - k_done : 0, due_end = total > k_done ? total - k_done : 0;
+                        VrState off;
+                        CHECK(emit_count(p, N, k_done, false, olen) == (size_t)(due < olen ? due : olen), "emit_count N=%lu k_done=%lu olen=%zu", (unsigned long)N, (unsigned long)k_done, olen);
+                        CHECK(emit_count(p, N, k_done, true, olen) == (size_t)(due_end < olen ? due_end : olen), "emit_count (ended) N=%lu k_done=%lu olen=%zu", (unsigned long)N, (unsigned long)k_done, olen);
+                        CHECK(emit_count(p, off, N, k_done, false, olen) == emit_count(p, N, k_done, false, olen) && !off.on && off.n_slew == 0, "emit_count with a clock that is off");
+                    }
+            }
+        }
+}
+
+// ---- emit_count, variable rate: against a walk of the clock, one output at a time, in 128-bit integers ----
+struct Walk {          // the clock at output k (the next one to emit)
+    uint64_t k = 0;
+    i128 t = 0, step = 0, delta = 0, s1 = 0;
+    uint64_t n = 0, n_slew = 0; // outputs since the last change of ratio, of which the first n_slew slew
+
+    void advance() { t += step; ++n; step = n < n_slew ? step + delta : s1; ++k; }
+    void set_io_ratio(double ratio, uint64_t slew_len)
+    {
+        const i128 s_new = q64(ratio);
+        s1 = s_new; n = 0; n_slew = slew_len;
+        if (slew_len) delta = (s_new - step) / (i128)slew_len; else { step = s_new; delta = 0; }
+    }
+    bool ok(uint64_t n_in, int64_t H, bool ended) const
+    {
+        if (ended) return t + step / 2 <= ((i128)n_in << 64);
+        return (int64_t)(t >> 64) + H <= (int64_t)n_in - 1;
+    }
+};
+// what hipsoxr_stream_set_io_ratio does to the stream's VrState
+static void state_set_io_ratio(VrState &v, uint64_t k_done, double ratio, uint64_t slew_len)
+{
+    const i128 t_now = v.pos(k_done), s_now = v.step(k_done), s_new = q64(ratio);
+    v.k_s = k_done; v.t_s = t_now; v.s1 = s_new;
+    if (slew_len > 0) { v.s0 = s_now; v.n_slew = slew_len; v.delta = (s_new - s_now) / (i128)slew_len; }
+    else { v.s0 = s_new; v.n_slew = 0; v.delta = 0; }
+}
+
+struct VrEvent { int call; double ratio; uint64_t slew_len; }; // before call `call`: set_io_ratio
+// expect_crossed: a call stops at the end of a slew and makes another pass; expect_exact_end: a pass begins exactly there
+struct VrCase { const char *name; double io0; size_t ilen, olen; int calls; std::vector<VrEvent> events; bool expect_crossed, expect_exact_end; };
+
+static void run_vr_case(const VrCase &c)
+{
+    Plan p;
+    p.T = 16; p.phases = 64;
+    const int64_t H = p.T / 2;
+    VrState v;
+    v.on = true; v.max_io = c.io0; v.s0 = v.s1 = q64(c.io0);
+    Walk w;
+    w.step = w.s1 = q64(c.io0);
+    uint64_t n_in = 0, k_done = 0;
+    bool crossed = false, exact_end = false;
+    for (int call = 0; call <= c.calls; ++call) {
+        const bool ended = call == c.calls; // the last call is the flush
+        for (const VrEvent &e : c.events)
+            if (e.call == call) { state_set_io_ratio(v, k_done, e.ratio, e.slew_len); w.set_io_ratio(e.ratio, e.slew_len); }
+        if (!ended) n_in += c.ilen;
+        for (int pass = 0; pass < 4; ++pass) { // (emit_passes: another pass only where one stopped at the end of a slew)
+            // expected: walk until an output is not computable, olen is reached, or the slew ends
+            Walk probe = w;
+            const bool slewing = w.n < w.n_slew;
+            const uint64_t slew_left = slewing ? w.n_slew - w.n : 0;
+            size_t want = 0;
+            while (want < c.olen && probe.ok(n_in, H, ended) && !(slewing && want == slew_left)) { probe.advance(); ++want; }
+            const VrState before = v;
+            const size_t n = emit_count(p, v, n_in, k_done, ended, c.olen);
+            CHECK(n == want, "%s: call %d pass %d: emit_count %zu, the walk says %zu (k_done %lu)", c.name, call, pass, n, want, (unsigned long)k_done);
+            if (before.n_slew && k_done < before.k_s + before.n_slew)
+                CHECK(k_done + n <= before.k_s + before.n_slew, "%s: call %d crosses the end of the slew", c.name, call);
+            if (before.n_slew && k_done == before.k_s + before.n_slew) { exact_end = true; CHECK(v.n_slew == 0 && v.k_s == k_done, "%s: no renormalisation at the end of a slew", c.name); }
+            for (uint64_t k = k_done; k < k_done + 300; k += (k < k_done + 70 ? 1 : 23)) // the renormalised state: the same clock
+                CHECK(v.pos(k) == before.pos(k) && v.step(k) == before.step(k), "%s: call %d: the state after emit_count has another clock at k=%lu", c.name, call, (unsigned long)k);
+            // the clock of the launch against the walk: position and step at k_done, increment while the slew lasts
+            const VrPos vp = vr_pos_at(v, k_done);
+            const i128 d = w.n < w.n_slew ? w.delta : 0;
+            CHECK(vp.t_hi == (uint64_t)((u128)w.t >> 64) && vp.t_lo == (uint64_t)(u128)w.t && vp.s_hi == (uint64_t)((u128)w.step >> 64) && vp.s_lo == (uint64_t)(u128)w.step &&
+                  vp.d_hi == (uint64_t)((u128)d >> 64) && vp.d_lo == (uint64_t)(u128)d, "%s: call %d pass %d: vr_pos_at differs from the walk", c.name, call, pass);
+            for (size_t i = 0; i < n; ++i) w.advance();
+            k_done += n;
+            CHECK(v.pos(k_done) == w.t && v.step(k_done) == w.step, "%s: call %d: VrState::pos / step differ from the walk at k=%lu", c.name, call, (unsigned long)k_done);
+            if (!n || !slew_just_ended(v, k_done)) break;
+            crossed = true;
+        }
+    }
+    CHECK(k_done > 0, "%s: nothing was emitted", c.name);
+    CHECK(crossed == c.expect_crossed, "%s: a call %s the end of a slew", c.name, crossed ? "stopped at" : "never stopped at");
+    CHECK(exact_end == c.expect_exact_end, "%s: %s pass began exactly at the end of a slew", c.name, exact_end ? "a" : "no");
+    std::printf("  %-28s %lu outputs from %lu frames%s%s\n", c.name, (unsigned long)k_done, (unsigned long)n_in, crossed ? ", a call crossed a slew end" : "", exact_end ? ", a call began at a slew end" : "");
+}
+
+static void check_emit_count_vr()
+{
+    const std::vector<VrCase> cases = {
+        {"constant", 1.5, 441, 1000, 6, {}, false, false},
+        {"slew crossed inside a call", 1.5, 441, 1000, 8, {{3, 1.2, 50}}, true, true},
+        {"slew ends exactly at k_done", 2.0, 400, 100, 12, {{2, 1.0, 100}}, true, true}, // olen = the slew's length: the call ends where it does
+        {"slew_len 1", 1.5, 441, 1000, 6, {{2, 0.75, 1}, {4, 1.5, 1}}, true, true},
+        {"step change, no slew", 1.5, 441, 64, 10, {{3, 0.5, 0}, {5, 1.5, 0}}, false, false},
+        {"ratio changed inside a slew", 1.0, 300, 120, 10, {{2, 0.7, 500}, {4, 1.0, 50}}, true, true},
+        {"long slew, small olen", 0.9, 441, 37, 30, {{1, 0.45, 333}}, true, true},
+    };
+    for (const VrCase &c : cases) run_vr_case(c);
+}
+
+int main()
+{
+    check_k_avail();
+    check_ring_keep();
+    check_ring_grow();
+    check_emit_count_constant();
+    check_emit_count_vr();
+    std::printf("stream_rules_check: %ld checks, %ld failed\n", g_checks, g_failed);
+    return g_failed ? 1 : 0;
+}

@@ -1,4 +1,4 @@
-"""Test-side restatement of the variable-rate schedule (engine.cpp, VrState) in Python integers.
+"""Test-side restatement of the variable-rate schedule (csrc/stream_rules.h, VrState) in Python integers.
 
 The oracle (oracle/soxr_oracle.c, oracle_vr_*) evaluates one quadratic position law per call; which
 (T0, S0, D) applies to which outputs — i.e. what set_io_ratio does to the output clock, how many
