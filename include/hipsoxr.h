@@ -218,14 +218,19 @@ typedef struct {
      * (~10 us); a device copy supplied by the caller (a prepared job launched many times) is used as it is and must
      * equal the host table — it is not checked.  in_frames / out_frames of the job are then the LARGEST per-clip
      * values.  Whole signals only (in_abs0 == 0, out_k0 == 0).  Unit-stride float columns go out as one launch of
-     * the frequency-domain engine (AUTO: from 2^13 output samples in all, as for equal-length jobs); every other
-     * case is served clip by clip, same results. */
+     * the frequency-domain engine (AUTO: from 2^13 output samples in all, as for equal-length jobs).  Everything else on
+     * an exact-bank plan is ONE launch of the exact engine too: int16 / int32 under the default selector, interleaved
+     * or float64 clips, small jobs, HIPSOXR_KERNEL_EXACT and the tile / gather selectors — the kernel reads its clip's
+     * row, the grid is the longest clip's (more than 65535 columns: one launch per range of clips).  Each clip has the
+     * bits of the clip run alone; out[0, out_frames[c]) of every clip is written and nothing else, not the elements
+     * between packed clips either; clip_counter receives the sum over the clips.  Interpolated-phase plans and
+     * HIPSOXR_KERNEL_WAVE_DOT are served clip by clip from the same call, same results. */
     const int64_t *clip_table;
     const int64_t *clip_table_dev;
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */

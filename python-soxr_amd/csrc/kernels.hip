@@ -61,6 +61,7 @@
 
 #include "device.h"
 #include "pcm_out.h"
+#include "ragged_rules.h"
 
 namespace hipsoxr {
 
@@ -159,22 +160,46 @@ struct GatherArgs {
     int32_t ch_fast; // 1: consecutive threads = consecutive channels of one frame
 };
 
-template <typename IO, typename Real>
-__global__ void __launch_bounds__(256) k_gather(GatherArgs a)
+// RAGGED (a clip table on the exact engine, see kernels_tile.h): the table travels behind the arguments; a lane's clip —
+// uniform over its workgroup — reads its row, and the lane asks idx < out_frames[clip].  The grid is the longest clip's.
+struct GatherArgsR : GatherArgs {
+    const int64_t *rows; // [n_clips][4] = in offset, in frames, out offset, out frames (elements from in / out)
+};
+template <bool RAGGED> struct GatherArgsOf { typedef GatherArgs type; };
+template <> struct GatherArgsOf<true> { typedef GatherArgsR type; };
+__device__ __forceinline__ int64_t uniform64(int64_t v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const GatherArgs &a, uint32_t, GatherArgs &) { return a; }
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const GatherArgsR &r, uint32_t clip, GatherArgs &v)
+{
+    const int64_t *row = r.rows + 4 * (int64_t)__builtin_amdgcn_readfirstlane(clip);
+    v = r;
+    v.in = (const IO *)r.in + uniform64(row[0]); v.in_frames = uniform64(row[1]);
+    v.out = (IO *)r.out + uniform64(row[2]); v.out_frames = uniform64(row[3]);
+    return v;
+}
+
+template <typename IO, typename Real, bool RAGGED = false>
+__global__ void __launch_bounds__(256) k_gather(typename GatherArgsOf<RAGGED>::type a_)
 {
     int64_t idx;
     uint32_t ch, clip;
-    if (a.ch_fast) {
+    if (a_.ch_fast) {
         int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        idx = e / a.n_channels;
-        ch = (uint32_t)(e - idx * a.n_channels);
+        idx = e / a_.n_channels;
+        ch = (uint32_t)(e - idx * a_.n_channels);
         clip = blockIdx.y;
     } else {
         idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        ch = blockIdx.y % a.n_channels;
-        clip = blockIdx.y / a.n_channels;
+        ch = blockIdx.y % a_.n_channels;
+        clip = blockIdx.y / a_.n_channels;
     }
-    if (idx >= a.out_frames) return;
+    [[maybe_unused]] GatherArgs row_view;
+    const GatherArgs &a = clip_args<IO>(a_, clip, row_view);
+    if (RAGGED ? ragged_gather_skip(idx, a.out_frames) : idx >= a.out_frames) return;
     // position: (out_k0 + idx)*M = L*d + p
     const int64_t t = a.p0 + idx * a.M;
     const int64_t q = t / a.L;
@@ -986,6 +1011,57 @@ static const char *launch_gather(Plan *p, const hipsoxr_job_t &j, hipStream_t st
     return nullptr;
 }
 
+// Slab size and unit split of the float32 planar kernel (k_tile_mfma_p) for a job of slabs64 slabs of 64 periods — slabs32
+// of 32 — over all its columns: launch_tile has the account of the model.  A ragged job feeds it the slabs its table really
+// holds (ragged_total_slabs), not longest clip x clips.
+static void planes_form(int64_t slabs64, int64_t slabs32, int n_rt, int *pb_out, int *split_out)
+{
+    int best_pb = 64, best_split = 1;
+    if (slabs64 < 2048 || switches().dbg_slab32) {
+        double best = 1e300;
+        for (int pb = switches().dbg_slab32 ? 32 : 64; pb >= 32; pb -= 32) {
+            const int units = (pb / 32) * n_rt, full = (units + 3) / 4;
+            for (int split : {1, full}) {
+                const int upw = (units + 4 * split - 1) / (4 * split);
+                const double wgs_ = (double)((pb == 64 ? slabs64 : slabs32) * split);
+                double layers = std::ceil(wgs_ / 256.);
+                // (a partly filled last layer of multi-unit workgroups costs less than a full one: half-way;
+                //  64-period slabs split into single units, three per CU: between 1.5 and 3 x 256 workgroups the
+                //  dispatcher stacks them three deep on the CUs it has started on — refit after the round-3 kernels)
+                if (upw > 1) layers = 0.5 * (layers + wgs_ / 256.);
+                else if (pb == 64 && wgs_ > 384. && wgs_ <= 768.) layers = 3.;
+                const double c0 = pb == 32 ? (upw == 1 ? 1.15 : 2.35) : (upw == 1 ? 1.25 : 3.32);
+                const double k = pb == 32 ? (upw == 1 ? 1.153 : 0.958) : (upw == 1 ? 1.41 : 1.052);
+                const double cost = c0 + layers * upw * k;
+                if (cost < best) { best = cost; best_pb = pb; best_split = split; }
+            }
+        }
+    }
+    // HIPSOXR_DEBUG_TILE_FORM (debug builds): 1 = 64 periods whole, 2 = 64 split, 3 = 32 whole, 4 = 32 split — what
+    // tests/test_gpu_launch_forms.py::test_chosen_form_is_near_the_best compares the rule above against.
+    // (Round 4 also built a fifth form — 512 workgroups each WALKING an equal share of a column's units, slab after
+    //  slab — on the theory that 282 slabs on 256 CUs lose a fifth to layer quantisation.  They do not any more: the
+    //  split forms already give every SIMD its 6-7 units, all resident at once; walk 33.7 us vs 28.9 (32 split) on the
+    //  60 s clip, never ahead at any of eight sizes — profiles/r04_ab_experiments.txt §6.  Removed.)
+    const int force = switches().dbg_tile_form;
+    if (force >= 1 && force <= 4) {
+        best_pb = force <= 2 ? 64 : 32;
+        const int units = (best_pb / 32) * n_rt;
+        best_split = (force & 1) ? 1 : (units + 3) / 4;
+    }
+    *pb_out = best_pb; *split_out = best_split;
+}
+// ... and the planar geometry's LDS figures re-derived for slabs of pb periods (same tables)
+template <typename Real>
+static void planes_set_pb(TileGeom &g, int32_t pb)
+{
+    g.pb = pb;
+    g.x_count = (g.pb - 1) * (int32_t)g.Mc + g.span;
+    const int32_t rows_total = (g.x_count + (int32_t)g.Mc - 1) / (int32_t)g.Mc + 3;
+    g.plane = (rows_total * g.rowR + 63) / 64 * 64;
+    g.lds_bytes = ((size_t)g.plane * 4 + g.rowR) * sizeof(Real);
+}
+
 template <typename IO, typename Real>
 static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, const TileGeom &g_in)
 {
@@ -998,11 +1074,7 @@ static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, 
         const int64_t slabs32 = ((j.out_k0 + j.out_frames - 1) / g.Lc - j.out_k0 / g.Lc + 32) / 32 * (int64_t)j.n_clips * j.n_channels;
         if ((slabs32 < 6 * 256 || switches().dbg_mfma64_pb == 16) && switches().dbg_mfma64_pb != 32) {
             f64_pb = 16;
-            g.pb = 16;
-            g.x_count = (g.pb - 1) * (int32_t)g.Mc + g.span;
-            const int32_t rows_total = (g.x_count + (int32_t)g.Mc - 1) / (int32_t)g.Mc + 3;
-            g.plane = (rows_total * g.rowR + 63) / 64 * 64;
-            g.lds_bytes = ((size_t)g.plane * 4 + g.rowR) * sizeof(Real);
+            planes_set_pb<Real>(g, 16);
         }
     }
     // float32 planar kernel: slab size and unit split by job size.  A slab of 64 periods (41 KB of LDS, three workgroups
@@ -1022,45 +1094,10 @@ static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, 
         const int64_t periods = (j.out_k0 + j.out_frames - 1) / g.Lc - j.out_k0 / g.Lc + 1, cols_ = (int64_t)j.n_clips * j.n_channels;
         const int64_t slabs64 = (periods + 63) / 64 * cols_, slabs32 = (periods + 31) / 32 * cols_;
         int best_pb = 64, best_split = 1;
-        if (slabs64 < 2048 || switches().dbg_slab32) {
-            double best = 1e300;
-            for (int pb = switches().dbg_slab32 ? 32 : 64; pb >= 32; pb -= 32) {
-                const int units = (pb / 32) * g.n_rt, full = (units + 3) / 4;
-                for (int split : {1, full}) {
-                    const int upw = (units + 4 * split - 1) / (4 * split);
-                    const double wgs_ = (double)((pb == 64 ? slabs64 : slabs32) * split);
-                    double layers = std::ceil(wgs_ / 256.);
-                    // (a partly filled last layer of multi-unit workgroups costs less than a full one: half-way;
-                    //  64-period slabs split into single units, three per CU: between 1.5 and 3 x 256 workgroups the
-                    //  dispatcher stacks them three deep on the CUs it has started on — refit after the round-3 kernels)
-                    if (upw > 1) layers = 0.5 * (layers + wgs_ / 256.);
-                    else if (pb == 64 && wgs_ > 384. && wgs_ <= 768.) layers = 3.;
-                    const double c0 = pb == 32 ? (upw == 1 ? 1.15 : 2.35) : (upw == 1 ? 1.25 : 3.32);
-                    const double k = pb == 32 ? (upw == 1 ? 1.153 : 0.958) : (upw == 1 ? 1.41 : 1.052);
-                    const double cost = c0 + layers * upw * k;
-                    if (cost < best) { best = cost; best_pb = pb; best_split = split; }
-                }
-            }
-        }
-        // HIPSOXR_DEBUG_TILE_FORM (debug builds): 1 = 64 periods whole, 2 = 64 split, 3 = 32 whole, 4 = 32 split — what
-        // tests/test_gpu_launch_forms.py::test_chosen_form_is_near_the_best compares the rule above against.
-        // (Round 4 also built a fifth form — 512 workgroups each WALKING an equal share of a column's units, slab after
-        //  slab — on the theory that 282 slabs on 256 CUs lose a fifth to layer quantisation.  They do not any more: the
-        //  split forms already give every SIMD its 6-7 units, all resident at once; walk 33.7 us vs 28.9 (32 split) on the
-        //  60 s clip, never ahead at any of eight sizes — profiles/r04_ab_experiments.txt §6.  Removed.)
-        const int force = switches().dbg_tile_form;
-        if (force >= 1 && force <= 4) {
-            best_pb = force <= 2 ? 64 : 32;
-            const int units = (best_pb / 32) * g.n_rt;
-            best_split = (force & 1) ? 1 : (units + 3) / 4;
-        }
+        planes_form(slabs64, slabs32, g.n_rt, &best_pb, &best_split);
         f32_split = best_split;
         if (best_pb == 32) {
-            g.pb = 32;
-            g.x_count = (g.pb - 1) * (int32_t)g.Mc + g.span;
-            const int32_t rows_total = (g.x_count + (int32_t)g.Mc - 1) / (int32_t)g.Mc + 3;
-            g.plane = (rows_total * g.rowR + 63) / 64 * 64;
-            g.lds_bytes = ((size_t)g.plane * 4 + g.rowR) * sizeof(Real);
+            planes_set_pb<Real>(g, 32);
         }
     }
     // float32 MFMA kernel in its general form (k_tile_mfma: input periods that are no multiple of 16, e.g. 44.1k -> 16k):
@@ -1276,6 +1313,203 @@ static const char *launch_typed(Plan *p, const hipsoxr_job_t &j, hipStream_t st,
     return launch_gather<IO, Real>(p, j, st, nullptr, nullptr, cd);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ragged batches on the exact engine: all clips of a clip table (or of one range of it) in ONE launch of a kernel's RAGGED
+// form.  ONE form is picked from the table for the whole launch — any is correct, every exact kernel computes the canonical
+// order — with the plan's own slab geometry: AUTO / EXACT take the MFMA tile family where the plan has one, else k_tile,
+// when the LONGEST clip passes launch_typed's `big` test (short clips ride along), otherwise k_gather; the family
+// selectors force theirs.  Not in ragged form: the small-job forms of launch_tile (halves, z-splits, 16-period float64
+// slabs) and the trace.  *handled stays false for what is still served clip by clip (interpolated-phase plans, the wave-dot
+// kernel, a table with a clip of more than 2^30 outputs: launch_ragged_job).
+// ---------------------------------------------------------------------------------------------
+struct RaggedForm { const char *kernel; int split; size_t lds; dim3 grid, block; };
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per ragged exact launch, in the style of adj_launch_log
+static void ragged_launch_log(size_t width, const Plan &p, const TileGeom *g, const RaggedForm &f, uint32_t n_clips)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    fprintf(fl, "kernel=%s width=%zu L=%lld M=%lld Lc=%lld Mc=%lld pb=%d n_rt=%d split=%d lds=%zu grid=%ux%ux%u block=%u ragged=%u\n", f.kernel, width,
+            (long long)p.L, (long long)p.M, (long long)(g ? g->Lc : 0), (long long)(g ? g->Mc : 0), g ? g->pb : 0, g ? g->n_rt : 0, f.split, f.lds,
+            f.grid.x, f.grid.y, f.grid.z, f.block.x, n_clips);
+    fclose(fl);
+}
+
+// j: the job of one launch — clip_table the host rows of its n_clips clips, clip_table_dev their device copy
+template <typename IO, typename Real>
+static const char *launch_ragged(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled)
+{
+    *handled = false;
+    if (p->phases || j.kernel == HIPSOXR_KERNEL_WAVE_DOT) return nullptr;
+    const int prec = sizeof(Real) == 4 ? 0 : 1;
+    const DeviceBank &d = bank_of<Real>(p);
+    TileGeom gv, gm;
+    {
+        std::lock_guard<std::mutex> lk(g_geom_mu);
+        if (TileGeom *gp = geom_find(p, prec, 0)) gv = *gp;
+        if (TileGeom *gp = geom_find(p, prec, 1)) gm = *gp;
+    }
+    const int64_t longest = ragged_longest(j.clip_table, j.n_clips);
+    int kernel = j.kernel;
+    if (kernel == HIPSOXR_KERNEL_EXACT) kernel = HIPSOXR_KERNEL_AUTO;
+    if (kernel == HIPSOXR_KERNEL_TILE_VALU && !gv.ok) return "tile kernel unavailable for this plan";
+    if (kernel == HIPSOXR_KERNEL_TILE_MFMA && !gm.ok) return "tile kernel unavailable for this plan";
+    if (kernel == HIPSOXR_KERNEL_TILE) {
+        if (!gv.ok && !gm.ok) return "tile kernel unavailable for this plan";
+        kernel = gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
+    }
+    if (kernel == HIPSOXR_KERNEL_AUTO) {
+        const TileGeom &g = gm.ok ? gm : gv;
+        const bool big = g.ok && longest >= 16 * g.Lc && longest >= 4096;
+        kernel = !big ? HIPSOXR_KERNEL_GATHER : gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
+    }
+    if (kernel != HIPSOXR_KERNEL_GATHER && kernel != HIPSOXR_KERNEL_TILE_MFMA && kernel != HIPSOXR_KERNEL_TILE_VALU) return nullptr;
+    *handled = true;
+    if (longest == 0) return nullptr; // nothing to write
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (cols > kMaxGridY) return "too many (clip, channel) columns for one launch (max 65535)";
+    RaggedForm f{};
+
+    if (kernel == HIPSOXR_KERNEL_GATHER) {
+        hipsoxr_job_t jj = j;
+        jj.in_clip_stride = jj.out_clip_stride = 0; // (a clip's place is its row's)
+        GatherArgsR a;
+        (GatherArgs &)a = make_gather_args<IO>(*p, d, jj, 0, longest, 0);
+        a.rows = j.clip_table_dev;
+        const int64_t gx = ragged_gather_grid_x(longest, a.ch_fast ? j.n_channels : 1);
+        if (gx > 2147483647LL) return "job too long for one launch";
+        f.kernel = "gather";
+        f.grid = a.ch_fast ? dim3((unsigned)gx, j.n_clips, 1) : dim3((unsigned)gx, (unsigned)cols, 1);
+        f.block = dim3(256);
+        hipLaunchKernelGGL((k_gather<IO, Real, true>), f.grid, f.block, 0, st, a);
+        HIP_TRY(hipGetLastError());
+        if (switches().dbg_launch_log) ragged_launch_log(sizeof(Real), *p, nullptr, f, j.n_clips);
+        return nullptr;
+    }
+
+    TileGeom g = kernel == HIPSOXR_KERNEL_TILE_MFMA ? gm : gv;
+    void (*kern)(TileArgsR) = nullptr;
+    int nw = g.n_rt; // waves per workgroup: launch_tile's rule
+    if (g.n_rt > 16) {
+        int best = 16, best_waste = 1 << 30;
+        for (int w = 16; w >= 8; --w) {
+            const int rounds = (g.n_rt + w - 1) / w, waste = rounds * w - g.n_rt;
+            if (waste < best_waste) { best_waste = waste; best = w; }
+        }
+        nw = best;
+    }
+    f.split = 1;
+    if (g.variant == 2) {
+        nw = 4;
+        if constexpr (sizeof(Real) == 4) { // slab size and unit split by the slabs the table holds
+            int pb = 64;
+            planes_form(ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, 64), ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, 32),
+                        g.n_rt, &pb, &f.split);
+            if (pb == 32) planes_set_pb<Real>(g, 32);
+            kern = k_tile_mfma_p<IO, true>; f.kernel = "tile_mfma_p";
+        } else { // launch_tile's rule for the float64 planar kernel (32-period slabs, a row tile per unit), on the table's slabs
+            const int64_t wgs = std::max<int64_t>(ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, g.pb), 1);
+            f.split = wgs >= 512 ? 1 : (int)std::min<int64_t>((g.n_rt + 3) / 4, (2 * 3 * 256) / wgs);
+            kern = k_tile_mfma64_p<IO, 2, 32, true>; f.kernel = "tile_mfma64_p";
+        }
+        f.split = std::max(1, f.split);
+    } else if (g.variant == 1) {
+        f.kernel = "tile_mfma";
+        if constexpr (sizeof(Real) == 4) kern = k_tile_mfma<IO, float, 4, true>; // (float32 slabs are 64 periods: build_tile_tables)
+        else kern = g.pb == 32 ? k_tile_mfma<IO, double, 2, true> : k_tile_mfma<IO, double, 1, true>;
+        if (sizeof(Real) == 4 ? g.pb != 64 : (g.pb != 32 && g.pb != 16)) return "internal: tile geometry without a ragged kernel";
+    } else {
+        f.kernel = "tile";
+        kern = g.aligned ? k_tile<IO, Real, 16, true, true> : k_tile<IO, Real, 16, false, true>;
+    }
+    TileArgsR a;
+    a.in = j.in; a.out = j.out;
+    a.tab = g.variant >= 1 ? d.tile_tab_m : d.tile_tab;
+    a.e0 = g.variant >= 1 ? d.tile_i0_m : d.tile_i0;
+    a.Lc = g.Lc; a.Mc = g.Mc; a.n_rt = g.n_rt; a.I_h = g.I_h;
+    a.pad = g.pad; a.i_min = g.i_min; a.x_count = g.x_count; a.pb = g.pb;
+    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
+    a.ics = 0; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride; // (a clip's place is its row's)
+    a.ocs = 0; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.in_abs0 = 0; a.in_frames = 0; a.out_k0 = 0; a.out_frames = 0; a.b_first = 0; // (whole signals; frame counts: the rows')
+    a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
+    a.n_waves = nw; a.dbg = 0; a.trace = nullptr;
+    a.rowR = g.rowR; a.plane = g.plane; a.halves = 0; a.scratch_off = 0;
+    a.rows = j.clip_table_dev;
+    const int64_t n_blocks = ragged_grid_x(longest, g.Lc, g.pb);
+    if (n_blocks > 2147483647LL) return "job too long for one launch";
+    a.xz = 0; a.nx = (int32_t)n_blocks;
+    f.grid = dim3((unsigned)n_blocks, (unsigned)cols, 1);
+    f.block = dim3(64 * nw);
+    if (g.variant == 2 && f.split > 1) {
+        if (!switches().no_xcd_split && (n_blocks + 7) / 8 * 8 * (int64_t)f.split < 2147483647LL) {
+            a.xz = f.split; // XCD-aware 1-D ids instead of the z dimension (launch_tile)
+            f.grid.x = (unsigned)((n_blocks + 7) / 8 * 8 * (int64_t)f.split);
+        } else f.grid.z = (unsigned)f.split;
+    }
+    f.lds = g.lds_bytes;
+    if (const char *e = ensure_dyn_lds((const void *)kern, f.lds)) return e;
+    hipLaunchKernelGGL(kern, f.grid, f.block, f.lds, st, a);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) ragged_launch_log(sizeof(Real), *p, &g, f, j.n_clips);
+    return nullptr;
+}
+
+// The device copy of a ragged job's clip table: the caller's (clip_table_dev, trusted to equal the host table), or — NULL —
+// the host table, already validated, uploaded here in stream order (stream-ordered allocation: the buffer lives until the
+// launches behind it have run).  *tmp: what the caller frees with hipFreeAsync behind its launches.
+static const char *clip_table_device(const hipsoxr_job_t &j, hipStream_t st, const int64_t **rows, void **tmp)
+{
+    *tmp = nullptr;
+    *rows = j.clip_table_dev;
+    if (*rows) return nullptr;
+    const size_t bytes = (size_t)j.n_clips * 4 * sizeof(int64_t);
+    if (hipMallocAsync(tmp, bytes, st) != hipSuccess) { *tmp = nullptr; return "ragged batches: no device memory for the clip table"; }
+    if (hipMemcpyAsync(*tmp, j.clip_table, bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+        (void)hipFreeAsync(*tmp, st);
+        *tmp = nullptr;
+        return "ragged batches: clip table upload failed";
+    }
+    *rows = (const int64_t *)*tmp;
+    return nullptr;
+}
+
+// The ragged exact launch of a whole table: one launch, or — more columns than gridDim.y holds — one per range of clips
+// (a sub-range of the table is a pointer offset, in the host table and in its device copy).
+static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled)
+{
+    *handled = false;
+    if (p->phases || j.kernel == HIPSOXR_KERNEL_WAVE_DOT || ragged_fold_step(j.n_channels) == 0) return nullptr;
+    if (ragged_longest(j.clip_table, j.n_clips) > ((int64_t)1 << 30)) return nullptr; // (launch_gather cuts such a clip into several launches)
+    if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    const int64_t *rows = nullptr;
+    void *tmp = nullptr;
+    if (const char *e = clip_table_device(j, st, &rows, &tmp)) return e;
+    const char *err = nullptr;
+    bool all = true;
+    for (uint32_t r = 0;; ++r) {
+        const RaggedRange rg = ragged_fold_range(j.n_clips, j.n_channels, r);
+        if (!rg.count) break;
+        hipsoxr_job_t part = j;
+        part.n_clips = rg.count;
+        part.clip_table = j.clip_table + 4 * (size_t)rg.first;
+        part.clip_table_dev = rows + 4 * (size_t)rg.first;
+        bool h = false;
+        switch (j.elem) {
+        case HIPSOXR_F32: err = launch_ragged<float, float>(p, part, st, &h); break;
+        case HIPSOXR_F64: err = launch_ragged<double, double>(p, part, st, &h); break;
+        case HIPSOXR_I32: err = launch_ragged<int32_t, double>(p, part, st, &h); break;
+        case HIPSOXR_I16: err = launch_ragged<int16_t, float>(p, part, st, &h); break;
+        default: err = "invalid element type";
+        }
+        if (err) break;
+        if (!h) { all = false; break; } // (decided by plan and selector: the same for every range)
+    }
+    if (tmp) (void)hipFreeAsync(tmp, st);
+    if (err) return err;
+    *handled = all;
+    return nullptr;
+}
+
 bool resident_post(const Plan &p, volatile uint64_t *w, uint32_t seq, int64_t in_abs0, int64_t in_frames, int64_t out_k0, int64_t out_frames,
                    const VrPos *vr)
 {
@@ -1419,8 +1653,9 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     if (want_pcm)
         if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
-    // (the kernel reads its clip's row), else clip by clip through the ordinary path — clips are independent, so the
-    // results are the same either way; bit-exact engines stay bit-exact.
+    // (the kernel reads its clip's row), else one launch of the exact engine's ragged form, else — interpolated-phase plans,
+    // the wave-dot kernel — clip by clip through the ordinary path.  Clips are independent, so the results are the same
+    // either way; bit-exact engines stay bit-exact.
     if (j.clip_table) {
         if (vr || res) return "ragged batches: constant-rate device jobs only";
         if (j.in_abs0 != 0 || j.out_k0 != 0) return "ragged batches: whole signals only (in_abs0 == 0, out_k0 == 0)";
@@ -1443,15 +1678,7 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             // the launch behind it has run).  A caller-supplied device copy is trusted to equal the host table.
             hipsoxr_job_t jj = j;
             void *tmp = nullptr;
-            if (!jj.clip_table_dev) {
-                const size_t bytes = (size_t)j.n_clips * 4 * sizeof(int64_t);
-                if (hipMallocAsync(&tmp, bytes, (hipStream_t)stream) != hipSuccess) return "ragged batches: no device memory for the clip table";
-                if (hipMemcpyAsync(tmp, j.clip_table, bytes, hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) {
-                    (void)hipFreeAsync(tmp, (hipStream_t)stream);
-                    return "ragged batches: clip table upload failed";
-                }
-                jj.clip_table_dev = (const int64_t *)tmp;
-            }
+            if (const char *e = clip_table_device(j, (hipStream_t)stream, &jj.clip_table_dev, &tmp)) return e;
             bool handled = false;
             const char *e = launch_fft(p, jj, stream, &handled, t_ch_base);
             if (tmp) (void)hipFreeAsync(tmp, (hipStream_t)stream);
@@ -1460,6 +1687,13 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         }
         if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (unit-stride float columns of a tabled ratio)";
         if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (unit-stride int16 / int32 columns of a tabled ratio)";
+        // the exact engine: one launch of a kernel's RAGGED form for exact-bank plans (launch_ragged); what that does not
+        // serve — interpolated-phase plans, the wave-dot kernel — clip by clip
+        {
+            bool handled = false;
+            if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;
+            if (handled) return nullptr;
+        }
         const size_t es = elem_size(j.elem);
         for (uint32_t c = 0; c < j.n_clips; ++c) {
             const int64_t *r = j.clip_table + 4 * (size_t)c;

@@ -38,6 +38,30 @@ struct TileArgs {
     int32_t halves, scratch_off; // k_tile_mfma: a row tile's two half-chains on two waves (sum through LDS at scratch_off, in elements)
 };
 
+// RAGGED batches (hipsoxr_job_t::clip_table on the exact engine): every tile kernel has a second instantiation, `bool RAGGED`,
+// whose argument block carries the device copy of the clip table behind the usual arguments (the equal-length kernels keep
+// theirs).  A column's clip reads its row {in offset, in frames, out offset, out frames} — offsets in elements from in / out,
+// 64-bit — in place of clip * ics, in_frames, clip * ocs, out_frames (the launcher passes ics == ocs == 0; in_abs0, out_k0 and
+// b_first are 0: whole signals).  The row address is wave-uniform and its values stay on the scalar side.  The grid's
+// frame axis is sized by the LONGEST clip; a workgroup whose first period starts at or behind its clip's out_frames returns
+// before it stages anything — a decision on block index and row alone, so no barrier is met by part of a workgroup
+// (ragged_rules.h has the integer rules, tests/c/ragged_rules_check.cpp checks them).
+struct TileArgsR : TileArgs {
+    const int64_t *rows; // [n_clips][4]
+};
+template <bool RAGGED> struct TileArgsOf { typedef TileArgs type; };
+template <> struct TileArgsOf<true> { typedef TileArgsR type; };
+// the arguments as one clip's kernel sees them: the equal-length block itself, or a copy with the clip's row put in
+template <typename IO> __device__ __forceinline__ const TileArgs &clip_args(const TileArgs &a, uint32_t, TileArgs &) { return a; }
+template <typename IO> __device__ __forceinline__ const TileArgs &clip_args(const TileArgsR &r, uint32_t clip, TileArgs &v)
+{
+    const int64_t *row = r.rows + 4 * (int64_t)clip;
+    v = r;
+    v.in = (const IO *)r.in + uniform64(row[0]); v.in_frames = uniform64(row[1]);
+    v.out = (IO *)r.out + uniform64(row[2]); v.out_frames = uniform64(row[3]);
+    return v;
+}
+
 // Stage the input slab of one workgroup: samples [bw*Mc + i_min, +x_count) of column (clip, ch)
 // into LDS as Real, row-padded (address n + pad*(n/Mc)), zero outside the signal.  x_count and
 // i_min are multiples of 4 (host geometry).  Each thread first ISSUES up to UNR independent
@@ -110,8 +134,8 @@ __device__ __forceinline__ Quad<double> lds_quad_aligned(const double *p)
     return Quad<double>{{a.x, a.y, b.x, b.y}};
 }
 
-template <typename IO, typename Real, int RT, bool ALIGNED>
-__global__ void __launch_bounds__(1024) k_tile(TileArgs a)
+template <typename IO, typename Real, int RT, bool ALIGNED, bool RAGGED = false>
+__global__ void __launch_bounds__(1024) k_tile(typename TileArgsOf<RAGGED>::type a_)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     Real *xs = reinterpret_cast<Real *>(smem_raw);
@@ -119,9 +143,12 @@ __global__ void __launch_bounds__(1024) k_tile(TileArgs a)
     const uint32_t col = blockIdx.y;
     // run-time division goes through the vector ALU; readfirstlane keeps the results (and every
     // address derived from them) on the scalar side
-    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a.n_channels);
+    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a_.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a_.n_channels);
+    [[maybe_unused]] TileArgs row_view;
+    const TileArgs &a = clip_args<IO>(a_, clip, row_view);
     const int32_t pb = a.pb; // periods per slab: 64, or fewer (the lanes above compute a copy of the last row and store nothing)
     const int64_t bw = a.b_first + (int64_t)blockIdx.x * pb; // first period of this workgroup
+    if (RAGGED && ragged_skip(blockIdx.x, a.Lc, pb, a.out_frames)) return; // (uniform: nothing of this clip lies in the slab)
     const int32_t Mc = (int32_t)a.Mc, pad = a.pad;
 
     stage_slab<IO, Real, ALIGNED>(a, xs, clip, ch, bw);
@@ -263,8 +290,8 @@ template <> struct MfmaOf<double> {
     static __device__ __forceinline__ int row(int kq, int v) { return kq + 4 * v; }
 };
 
-template <typename IO, typename Real = float, int NG = 4>
-__global__ void __launch_bounds__(1024) k_tile_mfma(TileArgs a)
+template <typename IO, typename Real = float, int NG = 4, bool RAGGED = false>
+__global__ void __launch_bounds__(1024) k_tile_mfma(typename TileArgsOf<RAGGED>::type a_)
 {
     typedef typename MfmaOf<Real>::Acc Acc;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -273,8 +300,11 @@ __global__ void __launch_bounds__(1024) k_tile_mfma(TileArgs a)
     const uint32_t col = blockIdx.y;
     // run-time division goes through the vector ALU; readfirstlane keeps the results (and every
     // address derived from them) on the scalar side
-    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a.n_channels);
+    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a_.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a_.n_channels);
+    [[maybe_unused]] TileArgs row_view;
+    const TileArgs &a = clip_args<IO>(a_, clip, row_view);
     const int64_t bw = a.b_first + (int64_t)blockIdx.x * (16 * NG);
+    if (RAGGED && ragged_skip(blockIdx.x, a.Lc, 16 * NG, a.out_frames)) return; // (uniform: nothing of this clip lies in the slab)
     const int32_t Mc = (int32_t)a.Mc, pad = a.pad, S = Mc + pad;
 
     if (!(a.dbg & 1)) stage_slab<IO, Real, false>(a, xs, clip, ch, bw);
@@ -587,18 +617,20 @@ __device__ __forceinline__ void stage_planes(const TileArgs &a, Real *xs, uint32
     }
 }
 
-template <typename IO>
-__global__ void __launch_bounds__(1024, 2) k_tile_mfma_p(TileArgs a)
+template <typename IO, bool RAGGED = false>
+__global__ void __launch_bounds__(1024, 2) k_tile_mfma_p(typename TileArgsOf<RAGGED>::type a_)
 {
     typedef float Real;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int32_t Mc = (int32_t)a.Mc, R = a.rowR, PLANE = a.plane, padR = R - Mc / 4;
+    const int32_t Mc = (int32_t)a_.Mc, R = a_.rowR, PLANE = a_.plane, padR = R - Mc / 4;
     Real *xs = reinterpret_cast<Real *>(smem_raw) + R; // one row of slack below (pipelined reads run one group past the end)
 
     const uint32_t col = blockIdx.y;
     // run-time division goes through the vector ALU; readfirstlane keeps the results (and every
     // address derived from them) on the scalar side
-    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a.n_channels);
+    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a_.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a_.n_channels);
+    [[maybe_unused]] TileArgs row_view;
+    const TileArgs &a = clip_args<IO>(a_, clip, row_view);
     uint32_t bxi = blockIdx.x, bz = blockIdx.z, nz = gridDim.z;
     if (a.xz) {
         const uint32_t slot = blockIdx.x >> 3;
@@ -608,6 +640,7 @@ __global__ void __launch_bounds__(1024, 2) k_tile_mfma_p(TileArgs a)
         if (bxi >= (uint32_t)a.nx) return; // grid.x is padded to a multiple of 8 slabs
     }
     const int64_t bw = a.b_first + (int64_t)bxi * a.pb; // slabs of 64 periods; of 32 for jobs of few slabs (launch_tile)
+    if (RAGGED && ragged_skip(bxi, a.Lc, a.pb, a.out_frames)) return; // (uniform, on the remapped slab: nothing of this clip lies in it)
     const int64_t k_end = a.out_k0 + a.out_frames;
     unsigned long long *tr = a.trace ? a.trace + ((size_t)((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 4 + (threadIdx.x >> 6)) * 16 : nullptr;
     int tri = 0;
@@ -755,16 +788,18 @@ __device__ __forceinline__ void mfma64_half_chain(f64x4 (&acc)[NG], const double
 
 // PB = periods per slab: 32, or 16 for jobs of few slabs (half the LDS, twice the workgroups: 563 slabs of 32 periods on
 // 256 CUs leave a fifth of them with three workgroups and the rest with two — the launch waits for the fifth).
-template <typename IO, int NG, int PB>
-__global__ void __launch_bounds__(640) k_tile_mfma64_p(TileArgs a)
+template <typename IO, int NG, int PB, bool RAGGED = false>
+__global__ void __launch_bounds__(640) k_tile_mfma64_p(typename TileArgsOf<RAGGED>::type a_)
 {
     typedef double Real;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int32_t Mc = (int32_t)a.Mc, R = a.rowR, PLANE = a.plane, padR = R - Mc / 4;
+    const int32_t Mc = (int32_t)a_.Mc, R = a_.rowR, PLANE = a_.plane, padR = R - Mc / 4;
     Real *xs = reinterpret_cast<Real *>(smem_raw) + R; // one row of slack below (pipelined reads run one group past the end)
 
     const uint32_t col = blockIdx.y;
-    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a.n_channels);
+    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a_.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a_.n_channels);
+    [[maybe_unused]] TileArgs row_view;
+    const TileArgs &a = clip_args<IO>(a_, clip, row_view);
     uint32_t bxi = blockIdx.x, bz = blockIdx.z, nz = gridDim.z;
     if (a.xz) { // XCD-aware ids of a unit split (see k_tile_mfma_p)
         const uint32_t slot = blockIdx.x >> 3;
@@ -774,6 +809,7 @@ __global__ void __launch_bounds__(640) k_tile_mfma64_p(TileArgs a)
         if (bxi >= (uint32_t)a.nx) return; // grid.x is padded to a multiple of 8 slabs
     }
     const int64_t bw = a.b_first + (int64_t)bxi * PB;
+    if (RAGGED && ragged_skip(bxi, a.Lc, PB, a.out_frames)) return; // (uniform, on the remapped slab: nothing of this clip lies in it)
     const int64_t k_end = a.out_k0 + a.out_frames;
 
     stage_planes<IO, Real>(a, xs, clip, ch, bw);

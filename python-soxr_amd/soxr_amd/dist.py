@@ -118,6 +118,14 @@ class RaggedJob:
     lowest clip (no packed copy of the input); results go to one packed buffer `[total_out_frames, channels]`.
     `launch()` = one C call.  `outputs()` returns per-clip views of the packed result.
 
+    One call is ONE launch on an exact-bank plan: unit-stride float columns of a tabled ratio go to the frequency-domain
+    engine under KERNEL_AUTO (from 2^13 outputs in all) or by name, as do mono int16 / int32 corpora under KERNEL_FFT_PCM;
+    everything else — int16 / int32 under the default selector, interleaved stereo / multichannel and float64 clips, small
+    jobs, KERNEL_EXACT, the tile and gather selectors — runs the exact engine's ragged kernels (the kernel reads its clip's row of
+    the table; the grid is the longest clip's; more than 65535 clip x channel columns: one launch per range of clips).
+    Each clip has the bits of the clip run alone.  Interpolated-phase plans (`plan.phases != 0`) and KERNEL_WAVE_DOT are
+    served clip by clip inside the same call.
+
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
 
@@ -305,10 +313,12 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
 def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AUTO):
     """Resample a batch of clips of unequal length on one device as one job; returns the list of per-clip outputs (views
     of one packed buffer).  Without `requires_grad` on any clip, or under `no_grad`, this is exactly
-    `RaggedJob(plan, clips, kernel).launch()` and its `outputs()`.
+    `RaggedJob(plan, clips, kernel).launch()` and its `outputs()` — one launch on an exact-bank plan, kernel=KERNEL_EXACT
+    included (see `RaggedJob`).
 
     Differentiable otherwise: the result carries a grad_fn whose backward is ONE ragged launch of the transposed operator
-    (`resample_ragged_adjoint` with `grad_kernel`), whatever the number of clips; gradients of gradients flow too.  A clip
+    (`resample_ragged_adjoint` with `grad_kernel`), whatever the number of clips; gradients of gradients flow too (the double
+    backward is the ragged forward with KERNEL_EXACT: one launch as well).  A clip
     that does not require grad gets none.  As for `device.resample_tensor`, the gradient is the EXACT engine's adjoint
     (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
     interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called."""
@@ -607,7 +617,9 @@ def resample_batch(clips, in_rate, out_rate, quality="VHQ", devices=None, kernel
                is copied over first), on a side stream ordered behind the caller's current streams; the caller's
                current stream on the computing device waits for the results.
                Host arrays: a pinned staging ring per device, blocks of about `block_bytes` of input, with the H2D
-               copy of block k+1, the launch of block k and the D2H copy of block k-1 in flight together.
+               copy of block k+1, the launch of block k and the D2H copy of block k-1 in flight together.  A block is ONE
+               ragged launch whatever the dtype: an int16 / int32 corpus under the default selector — pinned bit for bit
+               to the canonical order — runs the exact engine's ragged kernels, as does KERNEL_EXACT.
     pinned_results : host results as views of page-locked buffers the D2H copies land in (one buffer per block, kept
                alive by its arrays, recycled by torch's caching host allocator once they are all dropped) instead of
                fresh pageable arrays filled by one more CPU copy.  None: yes while the call's results stay under
