@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "device.h"
+#include "poly_rules.h"
 
 namespace hipsoxr {
 
@@ -39,13 +40,18 @@ namespace hipsoxr {
         if (e_ != hipSuccess) return hipGetErrorString(e_); \
     } while (0)
 
+// tap counts the polyphase kernel is instantiated for (poly_design rounds its design up to the next one)
+#define HIPSOXR_POLY_TAPS(X) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) X(48) X(56)
+#define HIPSOXR_POLY2_TAPS(X) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) // k_poly2 (two windows in registers: longer ones spill)
+
 struct TwoStage {
     bool ok = false, up = false;
     Plan fft;                 // the FFT stage's plan: L/M = 2/1 (up) or 1/2 (down), bank from the owner's prototype
     int32_t T2 = 0, P2 = 0, P2f = 0, row = 0; // polyphase stage: taps, table intervals (float64 / float32 table), records per table row (T2 + 1: bank spreading)
     int64_t Ls = 1, Ms = 1;   // polyphase stage: output k sits at k * Ms / Ls of ITS input samples
-    mutable int lane_for[3][16] = {};   // [float32 / float64 / float32 pairs][R]: lane multiplier of k_poly for runs of R outputs per thread (launch_poly; 0 = not simulated yet)
-    mutable float conf_for[3][16] = {}; // ... and its LDS conflict cost (1 = every 16-byte read group in one cycle)
+    // poly_lanes' cache, [float32 / float64 / float32 on k_poly2][R]: the lane order of runs of R outputs per thread
+    // (lane_mul 0 = not simulated yet).  Written behind a const TwoStage & under g_lanes_mu.
+    mutable PolyLane lanes[3][16] = {};
     void *tab_f = nullptr, *tab_d = nullptr; // device: [P2f][row] float4 / [P2][row] double4 records (a0..a3 of the cubic in x in [0, 1))
 };
 
@@ -77,6 +83,92 @@ struct PolyProto {
     }
 };
 
+// the FFT stage's plan: the owner's prototype H(tau) (tau in the OWNER's input samples) on the 2x grid; rho: owner-input
+// samples per sample of the intermediate signal (down)
+static void twostage_fft_plan(const Plan *p, bool up, double rho, Plan &f)
+{
+    const double fi = p->in_rate, fo = p->out_rate;
+    f.recipe = p->recipe; f.q = p->q; f.att_db = p->att_db; f.beta = p->beta; f.phases = 0;
+    if (up) { // u[m] = sum_n x[n] H(m/2 - n): bank[ph][j] = H(ph/2 + T/2 - 1 - j)
+        f.in_rate = fi; f.out_rate = 2. * fi; f.L = 2; f.M = 1; f.T = p->T;
+        f.bank.assign((size_t)2 * f.T, 0.);
+        for (int ph = 0; ph < 2; ++ph)
+            for (int j = 0; j < f.T; ++j) f.bank[(size_t)ph * f.T + j] = plan_proto(*p, .5 * ph + (double)(f.T / 2 - 1 - j));
+    } else {  // y[k] = sum_m v[m] g(2k - m), g(s) = H(s rho) rho (v at 2 f_out: rho owner-input samples per v sample)
+        f.in_rate = 2. * fo; f.out_rate = fo; f.L = 1; f.M = 2;
+        const int64_t tb = (int64_t)std::ceil((double)p->T / rho) + 2;
+        f.T = (int32_t)((tb + 7) / 8 * 8);
+        f.bank.assign((size_t)f.T, 0.);
+        for (int j = 0; j < f.T; ++j) f.bank[j] = plan_proto(*p, (double)(f.T / 2 - 1 - j) * rho) * rho;
+    }
+}
+
+// The polyphase stage: transparent over the band the FFT stage passes, stop band where its images begin.  Fills the
+// stage's numbers in *ts and its prototype *h; false: no stage for this plan (too many taps, a table that would leave LDS,
+// a ratio whose terms leave 2^31).
+static bool poly_design(const Plan *p, TwoStage *ts, PolyProto *h)
+{
+    const double fi = p->in_rate, fo = p->out_rate;
+    // in cycles per sample of ITS input: up: input at 2 f_in: pass 0.25 (= f_in/2), stop 0.75; down: input at f_in: pass
+    // f_out/2, stop 1.5 f_out
+    const double fpass = ts->up ? .25 : .5 * fo / fi, fstop = ts->up ? .75 : 1.5 * fo / fi;
+    const double A = p->att_db + 6.;
+    const double n_taps = (A - 7.95) / (2.285 * 2. * M_PI * (fstop - fpass)) + 1.;
+    ts->T2 = 0;
+#define HIPSOXR_POLY_T(t) if (!ts->T2 && t >= (int)std::ceil(n_taps)) ts->T2 = t;
+    HIPSOXR_POLY_TAPS(HIPSOXR_POLY_T) // the kernel's instances, in rising order: the first that holds the design
+#undef HIPSOXR_POLY_T
+    if (!ts->T2) return false;
+    // intervals of the cubic table: the interpolation error of a Chebyshev cubic over 1/P of a sample of this prototype is
+    // about 0.03 / P^4 of full scale: 1.2e-10 at 128 (float64 table), 1.9e-9 at 64 (float32 table: two orders under the
+    // float32 engine's floor, half the LDS — which is what lets several workgroups share a CU)
+    ts->P2 = 128; ts->P2f = 64;
+    ts->row = ts->T2 + 1;
+    if ((size_t)ts->P2 * ts->row * 16 > 100 * 1024) return false;
+    // output k of the polyphase stage at k * Ms / Ls input samples: up: from 2 f_in to f_out: 2 M / L; down: from f_in to
+    // 2 f_out: M / (2 L)
+    const int64_t a = ts->up ? 2 * p->M : p->M, b = ts->up ? p->L : 2 * p->L, g = gcd64(a, b);
+    ts->Ms = a / g; ts->Ls = b / g;
+    if (ts->Ms > (1LL << 31) || ts->Ls > (1LL << 31)) return false;
+    h->fc = .5 * (fpass + fstop); h->W = .5 * ts->T2; h->beta = .1102 * (A - 8.7); h->inv_i0 = 1. / bessel_i0(h->beta); h->scale = 1.;
+    double sum = 0.;
+    for (int64_t m = -32 * ts->T2; m < 32 * ts->T2; ++m) sum += (*h)((double)m / 64.);
+    h->scale = 64. / sum;
+    return true;
+}
+
+// [P][row] records a0..a3: the cubic per (interval, tap) through the four Chebyshev nodes of the interval, monomials in x
+// in [0, 1).  (plan.cpp fits its interpolated banks the same way but associates the products differently — d012 * p01
+// there, d012 * node[0] * node[1] here — so sharing the fit would move this table's bits: the two stay apart.)
+static std::vector<double> poly_cubic_table(const PolyProto &h, int P, int T2, int row)
+{
+    double node[4];
+    for (int c = 0; c < 4; ++c) node[c] = .5 - .5 * std::cos((double)(2 * c + 1) * M_PI / 8.);
+    std::vector<double> tab((size_t)P * row * 4, 0.);
+    for (int i = 0; i < P; ++i)
+        for (int j = 0; j < T2; ++j) {
+            double v[4];
+            for (int c = 0; c < 4; ++c) v[c] = h(((double)i + node[c]) / P + (double)(T2 / 2 - 1 - j));
+            const double d01 = (v[1] - v[0]) / (node[1] - node[0]), d12 = (v[2] - v[1]) / (node[2] - node[1]), d23 = (v[3] - v[2]) / (node[3] - node[2]);
+            const double d012 = (d12 - d01) / (node[2] - node[0]), d123 = (d23 - d12) / (node[3] - node[1]);
+            const double d3 = (d123 - d012) / (node[3] - node[0]);
+            double *a = &tab[((size_t)i * row + j) * 4];
+            a[3] = d3;
+            a[2] = d012 - d3 * (node[0] + node[1] + node[2]);
+            a[1] = d01 - d012 * (node[0] + node[1]) + d3 * (node[0] * node[1] + node[0] * node[2] + node[1] * node[2]);
+            a[0] = v[0] - d01 * node[0] + d012 * node[0] * node[1] - d3 * node[0] * node[1] * node[2];
+        }
+    return tab;
+}
+
+template <typename T>
+static const char *upload(void **dev, const std::vector<T> &host)
+{
+    HIP_TRY(hipMalloc(dev, host.size() * sizeof(T)));
+    HIP_TRY(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    return nullptr;
+}
+
 static const char *twostage_build(Plan *p)
 {
     TwoStage *ts = new TwoStage;
@@ -86,79 +178,13 @@ static const char *twostage_build(Plan *p)
     ts->up = fo > fi;
     const double rho = ts->up ? 1. : fi / (2. * fo); // polyphase stage: input samples per output sample is rho (down) / Ms/Ls (up)
     if (!ts->up && fi / fo > 4.) return nullptr;      // (long polyphase filters: the table would leave LDS)
-    // ---- the FFT stage's plan: the owner's prototype H(tau) (tau in the OWNER's input samples) on the 2x grid ----
-    Plan &f = ts->fft;
-    f.recipe = p->recipe; f.q = p->q; f.att_db = p->att_db; f.beta = p->beta; f.phases = 0;
-    if (ts->up) { // u[m] = sum_n x[n] H(m/2 - n): bank[ph][j] = H(ph/2 + T/2 - 1 - j)
-        f.in_rate = fi; f.out_rate = 2. * fi; f.L = 2; f.M = 1; f.T = p->T;
-        f.bank.assign((size_t)2 * f.T, 0.);
-        for (int ph = 0; ph < 2; ++ph)
-            for (int j = 0; j < f.T; ++j) f.bank[(size_t)ph * f.T + j] = plan_proto(*p, .5 * ph + (double)(f.T / 2 - 1 - j));
-    } else {      // y[k] = sum_m v[m] g(2k - m), g(s) = H(s rho) rho (v at 2 f_out: rho owner-input samples per v sample)
-        f.in_rate = 2. * fo; f.out_rate = fo; f.L = 1; f.M = 2;
-        const int64_t tb = (int64_t)std::ceil((double)p->T / rho) + 2;
-        f.T = (int32_t)((tb + 7) / 8 * 8);
-        f.bank.assign((size_t)f.T, 0.);
-        for (int j = 0; j < f.T; ++j) f.bank[j] = plan_proto(*p, (double)(f.T / 2 - 1 - j) * rho) * rho;
-    }
-    // ---- the polyphase stage: transparent over the band the FFT stage passes, stop band where its images begin ----
-    // in cycles per sample of ITS input: up: input at 2 f_in: pass 0.25 (= f_in/2), stop 0.75; down: input at f_in: pass
-    // f_out/2, stop 1.5 f_out
-    const double fpass = ts->up ? .25 : .5 * fo / fi, fstop = ts->up ? .75 : 1.5 * fo / fi;
-    const double A = p->att_db + 6.;
-    const double n_taps = (A - 7.95) / (2.285 * 2. * M_PI * (fstop - fpass)) + 1.;
-    ts->T2 = 0;
-    for (int t : {8, 12, 16, 20, 24, 28, 32, 40, 48, 56}) // (HIPSOXR_POLY_TAPS: the kernel's instances)
-        if (!ts->T2 && t >= (int)std::ceil(n_taps)) ts->T2 = t;
-    if (!ts->T2) return nullptr;
-    // intervals of the cubic table: the interpolation error of a Chebyshev cubic over 1/P of a sample of this prototype is
-    // about 0.03 / P^4 of full scale: 1.2e-10 at 128 (float64 table), 1.9e-9 at 64 (float32 table: two orders under the
-    // float32 engine's floor, half the LDS — which is what lets several workgroups share a CU)
-    ts->P2 = 128; ts->P2f = 64;
-    ts->row = ts->T2 + 1;
-    if ((size_t)ts->P2 * ts->row * 16 > 100 * 1024) return nullptr;
-    // output k of the polyphase stage at k * Ms / Ls input samples: up: from 2 f_in to f_out: 2 M / L; down: from f_in to
-    // 2 f_out: M / (2 L)
-    {
-        int64_t a = ts->up ? 2 * p->M : p->M, b = ts->up ? p->L : 2 * p->L;
-        const int64_t g = gcd64(a, b);
-        ts->Ms = a / g; ts->Ls = b / g;
-        if (ts->Ms > (1LL << 31) || ts->Ls > (1LL << 31)) return nullptr;
-    }
+    twostage_fft_plan(p, ts->up, rho, ts->fft);
     PolyProto h;
-    h.fc = .5 * (fpass + fstop); h.W = .5 * ts->T2; h.beta = .1102 * (A - 8.7); h.inv_i0 = 1. / bessel_i0(h.beta); h.scale = 1.;
-    {
-        double sum = 0.;
-        for (int64_t m = -32 * ts->T2; m < 32 * ts->T2; ++m) sum += h((double)m / 64.);
-        h.scale = 64. / sum;
-    }
-    // cubic per (interval, tap) through the four Chebyshev nodes of the interval, monomials in x in [0, 1) (plan.cpp)
-    double node[4];
-    for (int c = 0; c < 4; ++c) node[c] = .5 - .5 * std::cos((double)(2 * c + 1) * M_PI / 8.);
-    auto build = [&](int P) {
-        std::vector<double> tab((size_t)P * ts->row * 4, 0.);
-        for (int i = 0; i < P; ++i)
-            for (int j = 0; j < ts->T2; ++j) {
-                double v[4];
-                for (int c = 0; c < 4; ++c) v[c] = h(((double)i + node[c]) / P + (double)(ts->T2 / 2 - 1 - j));
-                const double d01 = (v[1] - v[0]) / (node[1] - node[0]), d12 = (v[2] - v[1]) / (node[2] - node[1]), d23 = (v[3] - v[2]) / (node[3] - node[2]);
-                const double d012 = (d12 - d01) / (node[2] - node[0]), d123 = (d23 - d12) / (node[3] - node[1]);
-                const double d3 = (d123 - d012) / (node[3] - node[0]);
-                double *a = &tab[((size_t)i * ts->row + j) * 4];
-                a[3] = d3;
-                a[2] = d012 - d3 * (node[0] + node[1] + node[2]);
-                a[1] = d01 - d012 * (node[0] + node[1]) + d3 * (node[0] * node[1] + node[0] * node[2] + node[1] * node[2]);
-                a[0] = v[0] - d01 * node[0] + d012 * node[0] * node[1] - d3 * node[0] * node[1] * node[2];
-            }
-        return tab;
-    };
-    const std::vector<double> tab = build(ts->P2), tab64 = build(ts->P2f);
-    std::vector<float> tabf(tab64.size());
-    for (size_t i = 0; i < tab64.size(); ++i) tabf[i] = (float)tab64[i];
-    HIP_TRY(hipMalloc(&ts->tab_f, tabf.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(ts->tab_f, tabf.data(), tabf.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&ts->tab_d, tab.size() * sizeof(double)));
-    HIP_TRY(hipMemcpy(ts->tab_d, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (!poly_design(p, ts, &h)) return nullptr;
+    const std::vector<double> tab = poly_cubic_table(h, ts->P2, ts->T2, ts->row), tab64 = poly_cubic_table(h, ts->P2f, ts->T2, ts->row);
+    const std::vector<float> tabf(tab64.begin(), tab64.end());
+    if (const char *e = upload(&ts->tab_f, tabf)) return e;
+    if (const char *e = upload(&ts->tab_d, tab)) return e;
     ts->ok = true;
     return nullptr;
 }
@@ -185,9 +211,6 @@ struct PolyArgs {
     int64_t m2_src, m2_dst, m2_shift, m2_n_out;
 };
 
-// tap counts the polyphase kernel is instantiated for (twostage_build rounds its design up to the next one)
-#define HIPSOXR_POLY_TAPS(X) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) X(48) X(56)
-#define HIPSOXR_POLY2_TAPS(X) X(8) X(12) X(16) X(20) X(24) X(28) X(32) X(40) // k_poly2 (two windows in registers: longer ones spill)
 __device__ __forceinline__ int64_t floor_div(int64_t q, int64_t d) // d > 0
 {
     const int64_t n = q / d;
@@ -614,168 +637,192 @@ __global__ void __launch_bounds__(256, TT >= 32 ? 2 : POLY2_OCC) k_poly2(PolyArg
 #endif
 }
 
-template <typename Real>
-static const char *launch_poly(const TwoStage &ts, const void *src, void *dst, int64_t n_lo, int64_t n_src, int64_t k_lo, int64_t n_out, uint32_t n_clips, uint32_t n_channels,
-                               const int64_t sstr[3], const int64_t dstr[3], hipStream_t st)
+// ---------------------------------------------------------------------------------------------
+// The polyphase launch.  Every decision that reads nothing but numbers is a function of poly_rules.h; here: the stage and
+// the job into PolyArgs (poly_args), the lane-order cache (poly_lanes), the kernel instance (poly_kernel), the trace
+// buffer of -DPOLY_TRACE builds, the launch-log line, and launch_poly, which puts them in order.
+// ---------------------------------------------------------------------------------------------
+// one polyphase launch: the source column holds samples [n_lo, n_src) (src points at sample 0; zero outside), outputs
+// [k_lo, k_lo + n_out) go to dst; strides {clip, frame, channel} in elements
+struct PolyJob {
+    const void *src; void *dst;
+    int64_t n_lo, n_src, k_lo, n_out;
+    uint32_t n_clips, n_channels;
+    const int64_t *sstr, *dstr;
+};
+
+static PolyArgs poly_args(const PolyStage &s, const void *tab, const PolyForm &f, const PolyJob &j)
 {
-    if (n_out <= 0) return nullptr;
     PolyArgs a;
-    a.src = src; a.dst = dst; a.tab = sizeof(Real) == 4 ? ts.tab_f : ts.tab_d;
-    const int P = sizeof(Real) == 4 ? ts.P2f : ts.P2;
-    a.T = ts.T2; a.P = P; a.row = ts.row;
-    a.Ls = ts.Ls; a.Ms = ts.Ms; a.Mq = ts.Ms / ts.Ls; a.Mr = ts.Ms % ts.Ls;
-    a.n_lo = n_lo; a.n_src = n_src; a.k_lo = k_lo; a.n_out = n_out;
-    a.lgP = 0;
-    while ((1 << a.lgP) < P) ++a.lgP;
-    a.step_fx = (uint64_t)((((unsigned __int128)(uint64_t)a.Mr) << 64) / (unsigned __int128)(uint64_t)a.Ls);
-    a.fx_per_rem = 18446744073709551616. / (double)a.Ls;
-    a.scs = sstr[0]; a.sfs = sstr[1]; a.schs = sstr[2]; a.dcs = dstr[0]; a.dfs = dstr[1]; a.dchs = dstr[2];
-    a.n_channels = n_channels;
-    // channels per workgroup: neighbouring channels of interleaved data (source or destination) share their lines
-    a.lg_cg = (sstr[2] == 1 || dstr[2] == 1) ? (n_channels % 4 == 0 ? 2 : n_channels % 2 == 0 ? 1 : 0) : 0;
-    // float32, both ends channel-interleaved with an even channel count and 8-byte aligned frames, windows that move by at
-    // most two frames: channel PAIRS on k_poly2 (one pass over the data, table reads shared by the two channels)
-    const bool pair = sizeof(Real) == 4 && (a.Mq == 0 || a.Mq == 1) && n_channels % 2 == 0 && sstr[2] == 1 && dstr[2] == 1 &&
-                      ((sstr[0] | sstr[1] | dstr[0] | dstr[1]) & 1) == 0 && (((uintptr_t)src | (uintptr_t)dst) & 7) == 0 && ts.T2 <= 40 && !switches().poly_no_pair;
-    if (pair) a.lg_cg = n_channels % 8 == 0 ? 2 : n_channels % 4 == 0 ? 1 : 0;
-    // Any other float32 column of more than ~1.7 phase periods (Ls outputs: integer rate pairs have at most 2 f_out of
-    // them per period): split h periods in — output k + h Ls has output k's fraction — and the two segments run as the pair
-    a.m2_src = a.m2_dst = a.m2_shift = 0; a.m2_n_out = n_out;
-    bool split = false;
-    if (!pair && sizeof(Real) == 4 && (a.Mq == 0 || a.Mq == 1) && ts.T2 <= 40 && !switches().poly_no_pair) {
-        const int64_t h = (n_out + 2 * ts.Ls - 1) / (2 * ts.Ls), n1 = h * ts.Ls, n2 = n_out - n1; // (member 1 is the longer one)
-        if (h >= 1 && 10 * n2 >= 7 * n1 && h * ts.Ms < (1LL << 40)) {
-            split = true;
-            a.n_out = n1; a.m2_n_out = n2; a.m2_shift = h * ts.Ms; a.m2_src = a.m2_shift * sstr[1]; a.m2_dst = n1 * dstr[1];
-        }
-    }
-    const bool two = pair || split; // k_poly2
-    n_out = a.n_out;                // (tiles are counted over member 1 of a split column)
-    const int cg = 1 << a.lg_cg;
-    const size_t unit = two ? 2 * sizeof(Real) : sizeof(Real); // bytes per staged source / output element
-    // outputs per thread: as many as keep the tile's source span within the LDS left beside the table (<= 8)
-    const size_t tab_bytes = (size_t)P * ts.row * 4 * sizeof(Real);
-    const size_t lds_cap = (sizeof(Real) == 4 ? (tab_bytes > 40 * 1024 || (two && ts.T2 >= 32) ? 78 : 52) : 96) * 1024; // three or two (float) / one (double) workgroups per CU
-    const double ratio = (double)ts.Ms / (double)ts.Ls;
-    int Rmax = 12;
-    while (Rmax > 1 && (tab_bytes + (size_t)(256. * Rmax * ratio + 257. * Rmax + ts.T2 + 4) * unit > lds_cap || // (source span + staged outputs)
-                        (two && 256. * Rmax * ratio + ts.T2 + 4 > 12. * 256.)))                                      // (k_poly2 holds a whole span in registers)
-        --Rmax;
-    // Thread t owns R consecutive outputs starting ((t * lane_mul) mod 256) * R into the tile (lane_mul odd: a bijection).
-    // Lanes l, l + 1 of a wave are then lane_mul * R outputs apart and their table rows form the arithmetic progression
-    // floor(c + l s), s = frac(lane_mul R Ms / Ls) P.  A 16-byte LDS read serves a lane group in one cycle when its 16 lanes
-    // fall on 16 different bank quads — (row + tap) mod 16 with the table's odd row stride — and takes one more cycle per
-    // extra distinct record on a quad.  Random rows cost 2.5-3 cycles; s within ~0.02 of an odd integer costs 1.
-    // (R, lane_mul) is picked by simulating the four lane groups of the four waves over 16 starting phases.
-    // R: as long as the tiles fill the workgroups the chip holds, the longest run that fits (a tile's fixed cost is about two
-    // outputs' time: job time = a + b / R with b / a = 2.06 — and a partly filled last round costs its share, not a round:
-    // 60 / 90 / 120 s take 56 / 72 / 88 us); below that, runs short enough to give every resident workgroup a tile
-    // (5 / 10 s stereo 24.3 / 25.0 -> 20.0 / 22.2 us, 10 s mono 26.0 -> 20.2; profiles/r05_ab_experiments.txt §7).
-    if (switches().dbg_poly_r > 0) Rmax = std::min(Rmax, switches().dbg_poly_r);
-    const uint64_t cols = (uint64_t)n_clips * n_channels / (uint64_t)(pair ? 2 * cg : cg); // channel groups
-    if (cols > 65535) return "two-stage: too many columns";
-    int dev = 0, n_cu = 256;
-    HIP_TRY(hipGetDevice(&dev));
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    const int occ_limit = two ? (ts.T2 >= 32 ? 2 : 3) : sizeof(Real) == 4 ? 4 : 2; // (registers: k_poly2's launch bounds, k_poly's ~108 / float64's ~200)
-    auto lds_of = [&](int r) { return tab_bytes + ((size_t)(256. * r * ratio + ts.T2 + 4) + 257u * (size_t)r) * unit; };
-    auto slots_of = [&](int r) { // workgroups per column the chip holds at once (launch geometry below)
-        const int per_cu = std::max(1, std::min(occ_limit, (int)((160u * 1024u) / lds_of(r))));
-        return std::max<int64_t>(1, (int64_t)per_cu * n_cu / (int64_t)cols);
-    };
-    int R = Rmax, lane_mul = 1;
-    {
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
-        const int which = two ? 2 : sizeof(Real) == 8;
-        auto lanes_for = [&](int r) -> double { // best lane multiplier for runs of r (cached per plan): its conflict cost, 1 = none
-            if (!ts.lane_for[which][r]) {
-                static const int group[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
-                                                 {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59}, {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
-                const int halves = sizeof(Real) == 8 ? 2 : 1; // a double4 record is two 16-byte reads
-                double best = 1e30;
-                int best_am = 1;
-                for (int am = 1; am < 256 && best > 16. * 16. * halves; am += 2) { // (every group in one cycle: nothing better to look for)
-                    double cost = 0.;
-                    for (int ph = 0; ph < 16 && cost < best; ++ph)
-                        for (int wave = 0; wave < 4; ++wave)
-                            for (int g = 0; g < 4; ++g) {
-                                int rows[16][16], cnt[16] = {0}, mx = 1; // distinct rows seen per quad
-                                for (int q = 0; q < 16; ++q) {
-                                    const int tid = 64 * wave + group[g][q];
-                                    const double f = ph / 16. + .37 + (double)((tid * am) & 255) * r * ratio;
-                                    const int i = (int)((f - std::floor(f)) * P) % P;
-                                    const int quad = (halves * ts.row * i) & 15;
-                                    bool seen = false;
-                                    for (int z = 0; z < cnt[quad]; ++z) seen |= rows[quad][z] == i;
-                                    if (!seen) { rows[quad][cnt[quad]++] = i; mx = std::max(mx, cnt[quad]); }
-                                }
-                                cost += mx;
-                            }
-                    if (cost < best) { best = cost; best_am = am; }
-                }
-                ts.lane_for[which][r] = best_am; ts.conf_for[which][r] = (float)(best / (16. * 16. * halves));
-            }
-            return ts.conf_for[which][r];
-        };
-        const int64_t slots = slots_of(Rmax);
-        if ((n_out + 256LL * Rmax - 1) / (256LL * Rmax) >= slots) { // a round or more: long runs, among them the one whose table reads conflict least
-            double best = 1e30;
-            for (int r = Rmax; r >= std::min(Rmax, std::max(2, Rmax / 3)) && best > 1.; --r) {
-                const double cost = lanes_for(r) * (1. + .02 * (Rmax - r)); // (a shorter run per thread: more tiles per output)
-                if (cost < best) { best = cost; R = r; }
-            }
-        } else // less than one round: shorter runs spread the job over the workgroups the chip holds
-            R = (int)std::max<int64_t>(std::min(Rmax, 2), std::min<int64_t>(Rmax, (n_out + 256 * slots - 1) / (256 * slots)));
-        lanes_for(R);
-        lane_mul = ts.lane_for[which][R];
-    }
-    a.lane_mul = lane_mul;
-    a.R = R;
-    a.span_max = (int)(256. * R * ratio + ts.T2 + 4);
-    const size_t lds = tab_bytes + ((size_t)a.span_max + 257u * (size_t)R) * unit;
-    if (lds > 160 * 1024) return "two-stage: polyphase tile does not fit LDS";
-    const int64_t n_tiles = (n_out + 256LL * R - 1) / (256LL * R);
+    a.src = j.src; a.dst = j.dst; a.tab = tab;
+    a.T = s.T2; a.P = s.P; a.row = s.row;
+    a.Ls = s.Ls; a.Ms = s.Ms; a.Mq = s.Ms / s.Ls; a.Mr = s.Ms % s.Ls;
+    a.n_lo = j.n_lo; a.n_src = j.n_src; a.k_lo = j.k_lo; a.n_out = f.n1;
+    a.lgP = poly_lg(s.P);
+    a.step_fx = poly_step_fx(s.Ms, s.Ls);
+    a.fx_per_rem = poly_fx_per_rem(s.Ls);
+    a.scs = j.sstr[0]; a.sfs = j.sstr[1]; a.schs = j.sstr[2]; a.dcs = j.dstr[0]; a.dfs = j.dstr[1]; a.dchs = j.dstr[2];
+    a.n_channels = j.n_channels;
+    a.lg_cg = f.lg_cg;
+    a.m2_src = f.m2_src; a.m2_dst = f.m2_dst; a.m2_shift = f.m2_shift; a.m2_n_out = f.n2;
+    a.trace = nullptr;
+    return a; // (R, span_max and lane_mul: launch_poly, once the run length is known)
+}
+
+// The lane order for runs of r outputs per thread, simulated once per plan, table (`which`: 0 float32, 1 float64,
+// 2 float32 on k_poly2 — three tables of one TwoStage) and r.  One mutex for every plan and element type.
+static std::mutex g_lanes_mu;
+static PolyLane poly_lanes(const TwoStage &ts, const PolyStage &s, int which, int r)
+{
+    std::lock_guard<std::mutex> lk(g_lanes_mu);
+    PolyLane &l = ts.lanes[which][r];
+    if (!l.lane_mul) l = poly_lane_cost(s.P, s.row, which == 1 ? 2 : 1, r, s.ratio); // (a double4 record is two 16-byte reads)
+    return l;
+}
+
+// the only place the instance lists expand: MQ = Mq where that is 0 or 1, else -1 (k_poly alone)
+template <typename Real>
+static void (*poly_kernel(int T2, int64_t Mq, bool pair, bool split))(PolyArgs)
+{
     void (*kern)(PolyArgs) = nullptr;
-    switch (ts.T2) {
-#define HIPSOXR_POLY_T(t) case t: kern = a.Mq == 0 ? k_poly<Real, t, 0> : a.Mq == 1 ? k_poly<Real, t, 1> : k_poly<Real, t, -1>; break;
+    switch (T2) {
+#define HIPSOXR_POLY_T(t) case t: kern = Mq == 0 ? k_poly<Real, t, 0> : Mq == 1 ? k_poly<Real, t, 1> : k_poly<Real, t, -1>; break;
         HIPSOXR_POLY_TAPS(HIPSOXR_POLY_T)
 #undef HIPSOXR_POLY_T
     }
     if constexpr (sizeof(Real) == 4)
-        if (two) switch (ts.T2) {
-#define HIPSOXR_POLY_T(t) case t: kern = pair ? (a.Mq == 0 ? k_poly2<t, 0, true> : k_poly2<t, 1, true>) : (a.Mq == 0 ? k_poly2<t, 0, false> : k_poly2<t, 1, false>); break;
+        if (pair || split) switch (T2) {
+#define HIPSOXR_POLY_T(t) case t: kern = pair ? (Mq == 0 ? k_poly2<t, 0, true> : k_poly2<t, 1, true>) : (Mq == 0 ? k_poly2<t, 0, false> : k_poly2<t, 1, false>); break;
             HIPSOXR_POLY2_TAPS(HIPSOXR_POLY_T)
 #undef HIPSOXR_POLY_T
         }
+    return kern;
+}
+
+// (-DPOLY_TRACE: per-wave cycle sums [workgroup][wave][8], dumped synchronously behind the launch — a debugging aid)
+#ifdef POLY_TRACE
+static const char *poly_trace_begin(PolyArgs &a, dim3 grid, size_t *n)
+{
+    *n = (size_t)grid.x * grid.y * 4 * 8;
+    if (!switches().dbg_trace) return nullptr;
+    HIP_TRY(hipMalloc((void **)&a.trace, *n * 8));
+    HIP_TRY(hipMemset(a.trace, 0, *n * 8));
+    return nullptr;
+}
+static const char *poly_trace_dump(const PolyArgs &a, size_t n, hipStream_t st)
+{
+    if (!a.trace) return nullptr;
+    std::vector<unsigned long long> h(n);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(h.data(), a.trace, n * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(switches().dbg_trace, "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+    (void)hipFree(a.trace);
+    return nullptr;
+}
+#else
+static const char *poly_trace_begin(PolyArgs &, dim3, size_t *) { return nullptr; }
+static const char *poly_trace_dump(const PolyArgs &, size_t, hipStream_t) { return nullptr; }
+#endif
+
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per polyphase launch, in the style of adjoint.hip's
+// adj_launch_log — what tests/test_gpu_two_stage_forms.py reads the launch form from.
+static void poly_launch_log(size_t width, const PolyArgs &a, const PolyForm &f, const PolyLane &ln, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    fprintf(fl, "kernel=%s width=%zu T=%d MQ=%d il=%d split=%d R=%d lane_mul=%d conf=%.4f lds=%zu lg_cg=%d cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_out=%lld m2_n_out=%lld\n",
+            f.pair || f.split ? "poly2" : "poly", width, a.T, a.Mq == 0 || a.Mq == 1 ? (int)a.Mq : -1, (int)f.pair, (int)f.split, a.R, ln.lane_mul, (double)ln.conf, lds,
+            a.lg_cg, (unsigned long long)cols, (long long)n_tiles, grid.x, grid.y, grid.z, (long long)a.n_out, (long long)a.m2_n_out);
+    fclose(fl);
+}
+
+template <typename Real>
+static const char *launch_poly(const TwoStage &ts, const PolyJob &j, hipStream_t st)
+{
+    if (j.n_out <= 0) return nullptr;
+    constexpr size_t W = sizeof(Real);
+    const PolyStage s = poly_stage(ts.T2, W == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms);
+    const PolyForm f = poly_form(W, s.Ms / s.Ls, j.n_channels, j.sstr, j.dstr, (uintptr_t)j.src | (uintptr_t)j.dst, s.T2, switches().poly_no_pair, j.n_out, s.Ls, s.Ms);
+    PolyArgs a = poly_args(s, W == 4 ? ts.tab_f : ts.tab_d, f, j);
+    const bool two = f.pair || f.split; // k_poly2
+    const size_t unit = poly_unit(W, two), tab_bytes = poly_tab_bytes(s.P, s.row, W);
+    const int Rmax = poly_rmax(W, tab_bytes, two, s.T2, s.ratio, switches().dbg_poly_r);
+    const uint64_t cols = poly_cols(j.n_clips, j.n_channels, f.pair, f.lg_cg);
+    if (cols > kPolyMaxCols) return "two-stage: too many columns";
+    int dev = 0, n_cu = 256;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    // the run length, and the lane order that goes with it
+    const int which = two ? 2 : W == 8;
+    const int64_t slots = poly_slots(Rmax, tab_bytes, s.ratio, s.T2, unit, poly_occ_limit(W, two, s.T2), n_cu, cols);
+    a.R = poly_pick_run(Rmax, a.n_out, slots, [&](int r) -> double { return poly_lanes(ts, s, which, r).conf; });
+    const PolyLane ln = poly_lanes(ts, s, which, a.R);
+    a.lane_mul = ln.lane_mul;
+    a.span_max = poly_span_max(a.R, s.ratio, s.T2);
+    const size_t lds = poly_lds_bytes(tab_bytes, a.R, s.ratio, s.T2, unit);
+    if (lds > kPolyLdsMax) return "two-stage: polyphase tile does not fit LDS";
+    const int64_t n_tiles = poly_tiles(a.n_out, a.R);
+    void (*kern)(PolyArgs) = poly_kernel<Real>(s.T2, a.Mq, f.pair, f.split);
     if (!kern) return "two-stage: no polyphase instance for this tap count";
     if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
-    // workgroups walk tiles (the table is loaded once per workgroup): exactly as many as the chip holds at once — a
-    // partly filled second round of workgroups would double the launch
     int per_cu = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 256, lds));
-    const int64_t want = std::max<int64_t>(1, (int64_t)std::max(per_cu, 1) * n_cu / (int64_t)cols);
-    unsigned gx = (unsigned)std::min<int64_t>(n_tiles, want);
-    if (gx > 8) gx &= ~7u; // columns' workgroups of one tile index on ONE XCD (workgroup b -> XCD b mod 8): interleaved channels share their lines in its L2
-    a.trace = nullptr;
-#ifdef POLY_TRACE
-    const size_t trace_n = (size_t)gx * cols * 4 * 8;
-    if (switches().dbg_trace) {
-        HIP_TRY(hipMalloc((void **)&a.trace, trace_n * 8));
-        HIP_TRY(hipMemset(a.trace, 0, trace_n * 8));
-    }
-#endif
-    hipLaunchKernelGGL(kern, dim3(gx, (unsigned)cols, 1), dim3(256), lds, st, a);
+    const dim3 grid(poly_grid_x(n_tiles, per_cu, n_cu, cols), (unsigned)cols, 1);
+    size_t trace_n = 0;
+    if (const char *e = poly_trace_begin(a, grid, &trace_n)) return e;
+    if (switches().dbg_launch_log) poly_launch_log(W, a, f, ln, lds, cols, n_tiles, grid);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
-#ifdef POLY_TRACE
-    if (a.trace) { // debugging aid only: synchronous dump of the per-wave cycle sums
-        std::vector<unsigned long long> h(trace_n);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h.data(), a.trace, trace_n * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(switches().dbg_trace, "wb")) { fwrite(h.data(), 8, trace_n, f); fclose(f); }
-        (void)hipFree(a.trace);
+    return poly_trace_dump(a, trace_n, st);
+}
+
+// one polyphase launch in the job's element type
+static const char *run_poly(int elem, const TwoStage &ts, const PolyJob &j, hipStream_t st)
+{
+    return elem == HIPSOXR_F32 ? launch_poly<float>(ts, j, st) : launch_poly<double>(ts, j, st);
+}
+
+// The two launches of an admitted job around its intermediate signal `mid` (m: its layout).  The stage that writes the
+// intermediate produces its `pad` samples either side like any others (its own input zero-extended), the stage that reads
+// it sees zeros beyond them — so the composite is the prototype's response to the zero-extended signal at EVERY output,
+// ends included, and no third engine patches the ends.  *handled = false with no error: the FFT engine declined its stage —
+// up: nothing but the intermediate was touched; down: the queued polyphase launch wrote the intermediate only — and the
+// caller's ordinary path computes the job.
+static const char *two_stage_run(Plan *p, const hipsoxr_job_t &j, const TwoStageMid &m, void *mid, void *stream, bool *handled)
+{
+    const TwoStage &ts = *p->two;
+    const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
+    const int64_t n = j.in_frames, n_out = j.out_frames;
+    const int64_t istr[3] = {j.in_clip_stride, j.in_frame_stride, j.in_chan_stride};
+    const int64_t ostr[3] = {j.out_clip_stride, j.out_frame_stride, j.out_chan_stride};
+    hipsoxr_job_t fj = j;
+    fj.kernel = j.kernel == HIPSOXR_KERNEL_FFT_F64 ? HIPSOXR_KERNEL_FFT_F64 : HIPSOXR_KERNEL_FFT;
+    fj.clip_counter = nullptr; fj.dither = 0;
+    PolyJob pj;
+    pj.n_clips = j.n_clips; pj.n_channels = j.n_channels;
+    if (ts.up) { // FFT stage 1:2 over the input delayed by pad / 2 samples (its output m' is u[m' - pad]), then u -> y
+        fj.in_abs0 = m.pad / 2;
+        fj.out = mid; fj.out_clip_stride = m.mstr[0]; fj.out_frame_stride = m.mstr[1]; fj.out_chan_stride = m.mstr[2];
+        fj.in_frames = n; fj.out_frames = m.n_mid;
+        pj.src = (char *)mid + (size_t)(m.pad * m.mstr[1]) * es; // sample 0 of the first column
+        pj.dst = j.out; pj.n_lo = -m.pad; pj.n_src = m.n_core + m.pad; pj.k_lo = 0; pj.n_out = n_out; pj.sstr = m.mstr; pj.dstr = ostr;
+    } else {     // x -> v [-pad, 2 n_out + pad), then the FFT stage 2:1 over it
+        pj.src = j.in; pj.dst = mid; pj.n_lo = 0; pj.n_src = n; pj.k_lo = -m.pad; pj.n_out = m.n_mid; pj.sstr = istr; pj.dstr = m.mstr;
+        fj.in = mid; fj.in_abs0 = -m.pad; fj.in_clip_stride = m.mstr[0]; fj.in_frame_stride = m.mstr[1]; fj.in_chan_stride = m.mstr[2];
+        fj.in_frames = m.n_mid; fj.out_frames = n_out;
     }
-#endif
+    if (const char *err = device_bank_ensure(&p->two->fft, engine_prec(j.elem))) return err;
+    bool fft_done = false;
+    if (ts.up) {
+        const char *err = launch_fft(&p->two->fft, fj, stream, &fft_done);
+        if (err || !fft_done) return err;
+    }
+    if (const char *err = run_poly(j.elem, ts, pj, (hipStream_t)stream)) return err;
+    if (!ts.up) {
+        const char *err = launch_fft(&p->two->fft, fj, stream, &fft_done);
+        if (err || !fft_done) return err;
+    }
+    *handled = true;
     return nullptr;
 }
 
@@ -793,65 +840,17 @@ const char *launch_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream, bool
     }
     const TwoStage &ts = *p->two;
     if (!ts.ok) return nullptr;
-    const int64_t n = j.in_frames, n_out = j.out_frames;
-    if (n_out < 8192 || n < 8192 || n >= (1LL << 30) || n_out >= (1LL << 30)) return nullptr;
-    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-    if (cols > 65535) return nullptr;
     const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
-    // the polyphase table and one tile's source span must fit LDS in the job's precision (long stages in float64 do not:
-    // the exact engine keeps those)
-    if ((size_t)(es == 4 ? ts.P2f : ts.P2) * ts.row * 4 * es + (size_t)(512. * ((double)ts.Ms / (double)ts.Ls + 1.01) + ts.T2 + 4) * es > 150u * 1024u) return nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    // The intermediate signal runs PAST both ends of the job, as far as the second stage reads it: `pad` samples of it
-    // before sample 0 and after the last one (a multiple of 8: 16-byte phases of the columns are kept).  The stage that
-    // writes it produces those samples like any others (its own input zero-extended), the stage that reads it sees zeros
-    // beyond them — so the composite is the prototype's response to the zero-extended signal at EVERY output, ends
-    // included, and no third engine patches the ends.
-    //   down: v[m], m in [-pad, 2 n_out + pad): pad >= polyphase half-width in v samples
-    //   up:   u[m], m in [-pad, 2 n + pad):     pad >= polyphase half-width (T2 / 2 u samples)
-    const double half_mid = ts.up ? .5 * ts.T2 : .5 * ts.T2 * (double)ts.Ls / (double)ts.Ms;
-    const int64_t pad = ((int64_t)std::ceil(half_mid) + 4 + 7) / 8 * 8;
-    const int64_t n_core = ts.up ? 2 * n : 2 * n_out, n_mid = n_core + 2 * pad;
-    void *mid = nullptr;
-    HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)n_mid * es, st));
-    // intermediate layout [clip][channel][frames] — or [clip][frames][channel] when the job's own data is interleaved with an
-    // even channel count: the FFT stage then takes its channel-pair form (one complex word per frame and pair, contiguous
-    // for stereo) instead of pairing blocks over strided columns
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (!two_stage_admits(j.in_frames, j.out_frames, cols, es, poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms))) return nullptr;
     const bool inter = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1;
-    const int64_t mstr[3] = {n_mid * (int64_t)j.n_channels, inter ? (int64_t)j.n_channels : 1, inter ? 1 : n_mid};
-    const int64_t istr[3] = {j.in_clip_stride, j.in_frame_stride, j.in_chan_stride};
-    const int64_t ostr[3] = {j.out_clip_stride, j.out_frame_stride, j.out_chan_stride};
-    auto fail = [&](const char *e) { (void)hipFreeAsync(mid, st); return e; };
-    hipsoxr_job_t fj = j;
-    fj.kernel = j.kernel == HIPSOXR_KERNEL_FFT_F64 ? HIPSOXR_KERNEL_FFT_F64 : HIPSOXR_KERNEL_FFT;
-    fj.clip_counter = nullptr; fj.dither = 0;
-    bool fft_done = false;
-    const char *err = nullptr;
-    void *mid0 = (char *)mid + (size_t)(pad * mstr[1]) * es; // sample 0 of the first column
-    if ((err = device_bank_ensure(&p->two->fft, engine_prec(j.elem)))) return fail(err);
-    if (ts.up) {
-        // 1:2 over the input delayed by pad / 2 samples: its output m' is u[m' - pad]
-        fj.in_abs0 = pad / 2;
-        fj.out = mid; fj.out_clip_stride = mstr[0]; fj.out_frame_stride = mstr[1]; fj.out_chan_stride = mstr[2];
-        fj.in_frames = n; fj.out_frames = n_mid;
-        if ((err = launch_fft(&p->two->fft, fj, stream, &fft_done))) return fail(err);
-        if (!fft_done) { (void)hipFreeAsync(mid, st); return nullptr; }
-        err = j.elem == HIPSOXR_F32 ? launch_poly<float>(ts, mid0, j.out, -pad, n_core + pad, 0, n_out, j.n_clips, j.n_channels, mstr, ostr, st)
-                                    : launch_poly<double>(ts, mid0, j.out, -pad, n_core + pad, 0, n_out, j.n_clips, j.n_channels, mstr, ostr, st);
-        if (err) return fail(err);
-    } else {
-        err = j.elem == HIPSOXR_F32 ? launch_poly<float>(ts, j.in, mid, 0, n, -pad, n_mid, j.n_clips, j.n_channels, istr, mstr, st)
-                                    : launch_poly<double>(ts, j.in, mid, 0, n, -pad, n_mid, j.n_clips, j.n_channels, istr, mstr, st);
-        if (err) return fail(err);
-        fj.in = mid; fj.in_abs0 = -pad; fj.in_clip_stride = mstr[0]; fj.in_frame_stride = mstr[1]; fj.in_chan_stride = mstr[2];
-        fj.in_frames = n_mid; fj.out_frames = n_out;
-        if ((err = launch_fft(&p->two->fft, fj, stream, &fft_done))) return fail(err);
-        if (!fft_done) { (void)hipFreeAsync(mid, st); return nullptr; } // (declined: the queued first stage wrote the intermediate only; the ordinary path computes the job)
-    }
-    (void)hipFreeAsync(mid, st);
-    (void)mid0;
-    *handled = true;
-    return nullptr;
+    const TwoStageMid m = two_stage_mid(ts.up, ts.T2, ts.Ls, ts.Ms, j.in_frames, j.out_frames, j.n_channels, inter);
+    hipStream_t st = (hipStream_t)stream;
+    void *mid = nullptr;
+    HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)m.n_mid * es, st));
+    const char *err = two_stage_run(p, j, m, mid, stream, handled);
+    (void)hipFreeAsync(mid, st); // (behind whatever was queued: success, error and a declined FFT stage alike)
+    return err;
 }
 
 } // namespace hipsoxr
