@@ -54,6 +54,7 @@
 // translation unit still (27 s of the build; the frequency-domain engine's three are the long pole).
 #include <hip/hip_runtime.h>
 
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
@@ -749,6 +750,33 @@ struct GatherLaunch {
     dim3 grid(int per_wg) const { return dim3((unsigned)((nf + per_wg - 1) / per_wg), (unsigned)cols, 1); }
 };
 
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per launch of launch_gather's family, in the style of
+// ragged_launch_log — what tests/test_gpu_interp_forms.py reads the kernel form from.  `form`: the form's own fields.
+#ifdef HIPSOXR_DEBUG_SWITCHES
+template <typename IO, typename Real>
+__attribute__((format(printf, 7, 8)))
+static void gather_launch_log(const char *kernel, const Plan &p, const GatherLaunch &c, dim3 grid, unsigned block, size_t lds, const char *form, ...)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    fprintf(fl, "kernel=%s width=%zu io=%c%zu vr=%d L=%lld M=%lld T=%d P=%d done=%lld nf=%lld cols=%llu k0=%lld in_abs0=%lld grid=%ux%ux%u block=%u lds=%zu", kernel,
+            sizeof(Real), std::is_integral<IO>::value ? 'i' : 'f', sizeof(IO) * 8, c.vr ? 1 : 0, (long long)p.L, (long long)p.M, (int)p.T, (int)p.phases,
+            (long long)c.done, (long long)c.nf, (unsigned long long)c.cols, (long long)c.a.out_k0, (long long)c.a.in_abs0, grid.x, grid.y, grid.z, block, lds);
+    if (*form) {
+        va_list ap;
+        va_start(ap, form);
+        fputc(' ', fl);
+        vfprintf(fl, form, ap);
+        va_end(ap);
+    }
+    fputc('\n', fl);
+    fclose(fl);
+}
+#define GATHER_LAUNCH_LOG(...) do { if (switches().dbg_launch_log) gather_launch_log<IO, Real>(__VA_ARGS__); } while (0)
+#else
+#define GATHER_LAUNCH_LOG(...) ((void)0)
+#endif
+
 // ---- launch: one function per kernel form ----
 template <typename IO, typename Real>
 static const char *launch_gather_wave(Plan *p, const GatherLaunch &c, const WaveGeom &g)
@@ -758,6 +786,7 @@ static const char *launch_gather_wave(Plan *p, const GatherLaunch &c, const Wave
     ga.g = c.a; ga.phase_major = bank_of<Real>(p).phase_major; ga.span_cap = (int32_t)g.span; ga.done_words = nullptr; ga.done_seq = 0;
     const dim3 grid = c.grid(32);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ga.done_words, &ga.done_seq);
+    GATHER_LAUNCH_LOG("gather_wave", *p, c, grid, 256, g.lds, "span_cap=%d", (int)ga.span_cap);
     hipLaunchKernelGGL((k_gather_wave<IO, Real>), grid, dim3(256), g.lds, c.st, ga);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -787,6 +816,7 @@ static const char *launch_chain_resident(Plan *p, const GatherLaunch &c, const C
     ra.idle_ticks = res->idle_us * 100; // wall_clock64: 100 MHz
     ra.n_wgs = (uint32_t)wgs;
     res->n_wgs = ra.n_wgs; res->max_out = (int64_t)grid.x * g.NO;
+    GATHER_LAUNCH_LOG("chain_resident", *p, c, grid, 256, g.lds, "NO=%d span_cap=%d mode=%d", g.NO, (int)g.span_cap, c.vr ? 2 : p->phases ? 1 : 0);
     hipLaunchKernelGGL(rk, grid, dim3(256), g.lds, c.st, ra);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -814,6 +844,7 @@ static const char *launch_chain(Plan *p, const GatherLaunch &c, const ChainGeom 
     if (const char *e = ensure_dyn_lds((const void *)ck, g.lds)) return e;
     const dim3 grid = c.grid(g.NO);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ca.done_words, &ca.done_seq);
+    GATHER_LAUNCH_LOG("chain", *p, c, grid, 256, g.lds, "NO=%d span_cap=%d mode=%d", g.NO, (int)g.span_cap, c.vr ? 2 : p->phases ? 1 : 0);
     hipLaunchKernelGGL(ck, grid, dim3(256), g.lds, c.st, ca);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -821,13 +852,14 @@ static const char *launch_chain(Plan *p, const GatherLaunch &c, const ChainGeom 
 
 // a half-chain per quad of lanes (k_interp_wave)
 template <typename IO, typename Real>
-static const char *launch_interp_wave(const GatherLaunch &c, const InterpArgs &ia, const WaveGeom &g)
+static const char *launch_interp_wave(const Plan &p, const GatherLaunch &c, const InterpArgs &ia, const WaveGeom &g)
 {
     InterpWaveArgs wa;
     wa.ia = ia; wa.span_cap = (int32_t)g.span; wa.done_words = nullptr; wa.done_seq = 0;
     const dim3 grid = c.grid(32);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &wa.done_words, &wa.done_seq);
     void (*wk)(InterpWaveArgs) = c.vr ? k_interp_wave<IO, Real, true> : k_interp_wave<IO, Real, false>;
+    GATHER_LAUNCH_LOG("interp_wave", p, c, grid, 256, g.lds, "span_cap=%d", (int)wa.span_cap);
     hipLaunchKernelGGL(wk, grid, dim3(256), g.lds, c.st, wa);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -923,6 +955,8 @@ static const char *launch_interp_tile(const Plan &p, const GatherLaunch &c, cons
     if constexpr (sizeof(Real) == 4)
         if (f.twin) tk = c.vr ? k_interp_tile<IO, Real, true, true, true> : k_interp_tile<IO, Real, false, true, true>;
     if (const char *e = ensure_dyn_lds((const void *)tk, lds)) return e;
+    GATHER_LAUNCH_LOG("interp_tile", p, c, tgrid, 1024, lds, "KO=%d pair=%d twin=%d h=%lld nf_t=%lld m2_n=%lld span_cap=%d", (int)ta.KO, f.pair_mode, f.twin ? 1 : 0,
+                      (long long)f.split_h, (long long)f.nf_t, (long long)ta.m2_n, (int)ta.span_cap);
     hipLaunchKernelGGL(tk, tgrid, dim3(1024), lds, c.st, ta);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -930,9 +964,10 @@ static const char *launch_interp_tile(const Plan &p, const GatherLaunch &c, cons
 
 // one lane per output: k_interp (ia: interpolated-phase plans and variable rate), else k_gather — every ratio, layout and length
 template <typename IO, typename Real>
-static const char *launch_lane(const GatherLaunch &c, const InterpArgs *ia)
+static const char *launch_lane(const Plan &p, const GatherLaunch &c, const InterpArgs *ia)
 {
     const dim3 block(256), grid = c.a.ch_fast ? dim3((unsigned)((c.nf * (int64_t)c.j.n_channels + 255) / 256), c.j.n_clips, 1) : c.grid(256);
+    GATHER_LAUNCH_LOG(ia ? "interp" : "gather", p, c, grid, 256, (size_t)0, "ch_fast=%d", (int)c.a.ch_fast);
     if (ia && c.vr) hipLaunchKernelGGL((k_interp<IO, Real, true>), grid, block, 0, c.st, *ia);
     else if (ia) hipLaunchKernelGGL((k_interp<IO, Real, false>), grid, block, 0, c.st, *ia);
     else hipLaunchKernelGGL((k_gather<IO, Real>), grid, block, 0, c.st, c.a);
@@ -1000,11 +1035,11 @@ static const char *launch_gather(Plan *p, const hipsoxr_job_t &j, hipStream_t st
             }
             InterpTileForm tf; // large launches: k_interp_tile where its cost model beats the lane-per-output kernels
             if (!switches().no_interp_tile && nf >= 4096 && cols_fit) tf = interp_tile_form<Real>(*p, j, nf, step, vr != nullptr, iw.ok);
-            if (!tf.KO && iw.ok) err = launch_interp_wave<IO, Real>(c, ia, iw);
+            if (!tf.KO && iw.ok) err = launch_interp_wave<IO, Real>(*p, c, ia, iw);
             else if (tf.KO) err = launch_interp_tile<IO, Real>(*p, c, ia, tf);
-            else err = launch_lane<IO, Real>(c, &ia);
+            else err = launch_lane<IO, Real>(*p, c, &ia);
         } else {
-            err = launch_lane<IO, Real>(c, nullptr);
+            err = launch_lane<IO, Real>(*p, c, nullptr);
         }
         if (err) return err;
     }
@@ -1643,6 +1678,7 @@ static const char *fft_pcm_refusal(const Plan &p, const hipsoxr_job_t &j, const 
     return nullptr;
 }
 
+static constexpr int64_t kWideLaneMaxOut = 4095; // outputs per column up to which a wide channel-fast job stays whole (launch_job)
 const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPos *vr, ResidentLaunch *res, ChainDone *cd)
 {
     if (cd) cd->n_wgs = 0;
@@ -1711,7 +1747,13 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     // Kernels index (clip, channel) columns through grid.y (<= 65535).  Wider jobs — the Python surface
     // admits 65536 channels like the reference, src/soxr/__init__.py:22 — are folded into several
     // launches over channel (or clip) ranges; columns are independent, so the result is the same.
-    if (cols > 65535) {
+    // Not folded: a short constant-rate job of an interpolated-phase plan on channel-fast data.  launch_gather serves it whole
+    // with lane-per-output k_interp — consecutive lanes on consecutive channels of one frame, every load coalesced, the clips
+    // in grid.y — where the fold would run k_chain twice over columns a frame apart in memory (kWideLaneMaxOut: measured).
+    const bool wide_lane = cols > 65535 && p->phases && !vr && !res && j.n_clips <= 65535 && j.in_chan_stride == 1 &&
+                           j.out_frames <= kWideLaneMaxOut && (int64_t)j.out_frames * j.n_channels < ((int64_t)1 << 31) &&
+                           (j.kernel == HIPSOXR_KERNEL_AUTO || j.kernel == HIPSOXR_KERNEL_EXACT || j.kernel == HIPSOXR_KERNEL_GATHER);
+    if (cols > 65535 && !wide_lane) {
         const size_t es = elem_size(j.elem);
         hipsoxr_job_t part = j;
         if (j.n_channels == 1 || j.n_clips > 65535) { // one clip range at a time (clips and channels both wide: the channels are folded below it)

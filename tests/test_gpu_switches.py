@@ -2,7 +2,8 @@
 result: every switch, in a process of its own, against the default process — canonical-order results bit for bit,
 frequency-domain results within the engine's 1e-6 of the exact engine (and bit for bit where the switch does not touch
 that engine).  All but four names are compiled in only with -DHIPSOXR_DEBUG_SWITCHES: both processes load that build
-(python-soxr_amd/_variants/dbg/, made by build.sh beside the product) through HIPSOXR_LIBRARY."""
+(python-soxr_amd/_variants/dbg/, made by build.sh beside the product) through HIPSOXR_LIBRARY.  The interpolated-phase
+forms that `dev_interp_tile` only digests are compared with the oracle, form by form, in tests/test_gpu_interp_forms.py."""
 import json
 import os
 import subprocess
