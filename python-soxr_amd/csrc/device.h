@@ -126,7 +126,7 @@ struct Switches {
     bool poly_no_pair = false;    // HIPSOXR_POLY_NO_PAIR     interleaved channel pairs on k_poly (one channel per pass) instead of k_poly2 (A/B)
     int dbg_tile_form = 0;        // HIPSOXR_DEBUG_TILE_FORM  k_tile_mfma_p: force launch form 1..4 (slab 64 whole / 64 split / 32 whole / 32 split)
     const char *dbg_trace = nullptr; // HIPSOXR_DEBUG_TRACE   path for per-wave s_memtime stamps (k_tile_mfma_p; k_fft_pair2 with -DFFT2_TRACE)
-    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape (written by the launcher of the form that took the job, or "none" by the dispatcher); adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape (a ragged launch appends ragged=<n_clips>); launch_ragged (kernels.hip) one line per ragged exact launch — kernel, element width, L M Lc Mc, pb, n_rt, split, LDS bytes, launch shape, ragged=<n_clips> (equal-length exact launches log nothing); adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape; launch_poly (twostage.hip) one line per polyphase launch of the two-stage form — kernel poly | poly2, element width, taps, MQ, il (channel pairs), split, R, lane multiplier and its conflict cost, LDS bytes, channel group, columns, tiles, launch shape, outputs of member 1 and member 2; launch_gather (kernels.hip) one line per launch — kernel gather_wave | chain | chain_resident | interp_wave | interp_tile | interp | gather, element width, io type, vr, L M T P, done nf cols, k0 in_abs0 (the launch's first output and the absolute index of input frame 0), launch shape, LDS bytes, then the form's own fields (chain: NO span_cap mode; wave forms: span_cap; tile: KO pair twin h nf_t m2_n span_cap; lane per output: ch_fast)
+    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape (written by the launcher of the form that took the job, or "none" by the dispatcher); adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape (a ragged launch appends ragged=<n_clips>); launch_tile and launch_ragged (kernels.hip, tile_launch_log) one line per tile launch of the exact engine — kernel tile | tile_mfma | tile_mfma_p | tile_mfma64_p (a ragged launch also: gather), element width, io type, L M Lc Mc, pb, n_rt, nw (waves that compute), split (workgroups per slab), halves, xz, LDS bytes, launch shape; a ragged launch appends ragged=<n_clips> (equal-length launches of launch_gather's family: below); adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape; launch_poly (twostage.hip) one line per polyphase launch of the two-stage form — kernel poly | poly2, element width, taps, MQ, il (channel pairs), split, R, lane multiplier and its conflict cost, LDS bytes, channel group, columns, tiles, launch shape, outputs of member 1 and member 2; launch_gather (kernels.hip) one line per launch — kernel gather_wave | chain | chain_resident | interp_wave | interp_tile | interp | gather, element width, io type, vr, L M T P, done nf cols, k0 in_abs0 (the launch's first output and the absolute index of input frame 0), launch shape, LDS bytes, then the form's own fields (chain: NO span_cap mode; wave forms: span_cap; tile: KO pair twin h nf_t m2_n span_cap; lane per output: ch_fast)
 };
 const Switches &switches();
 

@@ -63,6 +63,7 @@
 #include "device.h"
 #include "pcm_out.h"
 #include "ragged_rules.h"
+#include "tile_rules.h"
 
 namespace hipsoxr {
 
@@ -315,18 +316,9 @@ const char *ensure_dyn_lds(const void *fn, size_t bytes)
 
 static inline int32_t floor4(int32_t v) { return v >= 0 ? (v / 4) * 4 : -(((-v) + 3) / 4) * 4; }
 
-struct TileGeom {
-    int RT = 16, c = 1;
-    int variant = 0; // 0: k_tile (coefficients on the scalar path), 1: k_tile_mfma
-    bool aligned = false;
-    int32_t n_rt = 0, I_h = 0, pad = 0, i_min = 0, x_count = 0;
-    int32_t pb = 64; // periods per slab (k_tile: 32 or 16 when a 64-period slab does not fit LDS — float64, long periods)
-    int64_t Lc = 0, Mc = 0;
-    size_t lds_bytes = 0;
-    int32_t rowR = 0, plane = 0; // variant 2 (k_tile_mfma_p)
-    int32_t span = 0;            // variant 2: inputs one period's tiles reach over (i_max - i_min + 1): x_count = (pb - 1) Mc + span
+// (TileGeom, the geometry as numbers: tile_rules.h) ... and as the builders return it, with the tables' e0 words
+struct TileBuild : TileGeom {
     std::vector<int32_t> e0;
-    bool ok = false;
 };
 
 static inline int32_t floor16(int32_t v) { return v >= 0 ? (v / 16) * 16 : -(((-v) + 15) / 16) * 16; }
@@ -338,9 +330,9 @@ static inline int32_t floor16(int32_t v) { return v >= 0 ? (v / 16) * 16 : -(((-
 // sample — and plane rows of R doubles with R == 2 (mod 4): the 16 rows of a ds_read_b128 group then start in 16
 // different 16-byte bank groups.
 template <typename Real>
-static TileGeom build_mfma_planes(const Plan &p, std::vector<Real> *tab)
+static TileBuild build_mfma_planes(const Plan &p, std::vector<Real> *tab)
 {
-    TileGeom g;
+    TileBuild g;
     g.variant = 2;
     g.pb = sizeof(Real) == 4 ? 64 : 32;
     const int64_t L = p.L, M = p.M;
@@ -417,9 +409,9 @@ static TileGeom build_mfma_planes(const Plan &p, std::vector<Real> *tab)
 
 // Tile geometry + (optionally) tables for one precision.
 template <typename Real>
-static TileGeom build_tile_tables(const Plan &p, std::vector<Real> *tab, int variant = 0)
+static TileBuild build_tile_tables(const Plan &p, std::vector<Real> *tab, int variant = 0)
 {
-    TileGeom g;
+    TileBuild g;
     g.variant = variant;
     const int64_t L = p.L, M = p.M;
     const int32_t T = p.T, H = T / 2;
@@ -551,7 +543,7 @@ static const char *bank_upload(Plan *p, DeviceBank &d, TileGeom *geom_out, TileG
     if (const char *e = upload(&d.tap_major, tm)) return e;
 
     std::vector<Real> tab;
-    TileGeom g = build_tile_tables<Real>(*p, &tab);
+    TileBuild g = build_tile_tables<Real>(*p, &tab);
     if (g.ok) {
         if (const char *e = upload(&d.tile_tab, tab)) return e;
         if (const char *e = upload((void **)&d.tile_i0, g.e0)) return e;
@@ -562,7 +554,7 @@ static const char *bank_upload(Plan *p, DeviceBank &d, TileGeom *geom_out, TileG
     // v_mfma_f64_16x16x4_f64: k_tile_mfma64_p, else k_tile_mfma<IO, double, NG>
     if (geom_m_out && !(sizeof(Real) == 8 && switches().no_mfma64)) {
         std::vector<Real> tabm;
-        TileGeom gm = build_mfma_planes<Real>(*p, &tabm);
+        TileBuild gm = build_mfma_planes<Real>(*p, &tabm);
         if (!gm.ok || switches().no_planes) gm = build_tile_tables<Real>(*p, &tabm, 1);
         if (gm.ok) {
             if (const char *e = upload(&d.tile_tab_m, tabm)) return e;
@@ -751,7 +743,7 @@ struct GatherLaunch {
 };
 
 // HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per launch of launch_gather's family, in the style of
-// ragged_launch_log — what tests/test_gpu_interp_forms.py reads the kernel form from.  `form`: the form's own fields.
+// tile_launch_log — what tests/test_gpu_interp_forms.py reads the kernel form from.  `form`: the form's own fields.
 #ifdef HIPSOXR_DEBUG_SWITCHES
 template <typename IO, typename Real>
 __attribute__((format(printf, 7, 8)))
@@ -1046,239 +1038,151 @@ static const char *launch_gather(Plan *p, const hipsoxr_job_t &j, hipStream_t st
     return nullptr;
 }
 
-// Slab size and unit split of the float32 planar kernel (k_tile_mfma_p) for a job of slabs64 slabs of 64 periods — slabs32
-// of 32 — over all its columns: launch_tile has the account of the model.  A ragged job feeds it the slabs its table really
-// holds (ragged_total_slabs), not longest clip x clips.
-static void planes_form(int64_t slabs64, int64_t slabs32, int n_rt, int *pb_out, int *split_out)
+// ---------------------------------------------------------------------------------------------
+// The tile launch.  Every decision that reads nothing but numbers is a function of tile_rules.h (TileForm: the result of all
+// of them for one launch); here: the switches the rules read (tile_switches), the plan's two geometries (tile_geoms), the
+// job into TileArgs / TileArgsR (tile_args), the kernel instance (tile_kernel), the trace buffer, the launch-log line, and
+// launch_tile, which puts them in order — as launch_ragged does further down for a clip table.
+// ---------------------------------------------------------------------------------------------
+static TileSwitches tile_switches()
 {
-    int best_pb = 64, best_split = 1;
-    if (slabs64 < 2048 || switches().dbg_slab32) {
-        double best = 1e300;
-        for (int pb = switches().dbg_slab32 ? 32 : 64; pb >= 32; pb -= 32) {
-            const int units = (pb / 32) * n_rt, full = (units + 3) / 4;
-            for (int split : {1, full}) {
-                const int upw = (units + 4 * split - 1) / (4 * split);
-                const double wgs_ = (double)((pb == 64 ? slabs64 : slabs32) * split);
-                double layers = std::ceil(wgs_ / 256.);
-                // (a partly filled last layer of multi-unit workgroups costs less than a full one: half-way;
-                //  64-period slabs split into single units, three per CU: between 1.5 and 3 x 256 workgroups the
-                //  dispatcher stacks them three deep on the CUs it has started on — refit after the round-3 kernels)
-                if (upw > 1) layers = 0.5 * (layers + wgs_ / 256.);
-                else if (pb == 64 && wgs_ > 384. && wgs_ <= 768.) layers = 3.;
-                const double c0 = pb == 32 ? (upw == 1 ? 1.15 : 2.35) : (upw == 1 ? 1.25 : 3.32);
-                const double k = pb == 32 ? (upw == 1 ? 1.153 : 0.958) : (upw == 1 ? 1.41 : 1.052);
-                const double cost = c0 + layers * upw * k;
-                if (cost < best) { best = cost; best_pb = pb; best_split = split; }
-            }
-        }
-    }
-    // HIPSOXR_DEBUG_TILE_FORM (debug builds): 1 = 64 periods whole, 2 = 64 split, 3 = 32 whole, 4 = 32 split — what
-    // tests/test_gpu_launch_forms.py::test_chosen_form_is_near_the_best compares the rule above against.
-    // (Round 4 also built a fifth form — 512 workgroups each WALKING an equal share of a column's units, slab after
-    //  slab — on the theory that 282 slabs on 256 CUs lose a fifth to layer quantisation.  They do not any more: the
-    //  split forms already give every SIMD its 6-7 units, all resident at once; walk 33.7 us vs 28.9 (32 split) on the
-    //  60 s clip, never ahead at any of eight sizes — profiles/r04_ab_experiments.txt §6.  Removed.)
-    const int force = switches().dbg_tile_form;
-    if (force >= 1 && force <= 4) {
-        best_pb = force <= 2 ? 64 : 32;
-        const int units = (best_pb / 32) * n_rt;
-        best_split = (force & 1) ? 1 : (units + 3) / 4;
-    }
-    *pb_out = best_pb; *split_out = best_split;
-}
-// ... and the planar geometry's LDS figures re-derived for slabs of pb periods (same tables)
-template <typename Real>
-static void planes_set_pb(TileGeom &g, int32_t pb)
-{
-    g.pb = pb;
-    g.x_count = (g.pb - 1) * (int32_t)g.Mc + g.span;
-    const int32_t rows_total = (g.x_count + (int32_t)g.Mc - 1) / (int32_t)g.Mc + 3;
-    g.plane = (rows_total * g.rowR + 63) / 64 * 64;
-    g.lds_bytes = ((size_t)g.plane * 4 + g.rowR) * sizeof(Real);
+    const Switches &w = switches();
+    TileSwitches s;
+    s.dbg_slab32 = w.dbg_slab32; s.dbg_slab64 = w.dbg_slab64; s.no_halves = w.no_halves; s.no_xcd_split = w.no_xcd_split;
+    s.no_tile_split = w.no_tile_split; s.dbg_mfma64_split = w.dbg_mfma64_split; s.dbg_tile_form = w.dbg_tile_form;
+    s.dbg_mfma64_pb = w.dbg_mfma64_pb; s.dbg_nrt = w.dbg_nrt; s.dbg_nw = w.dbg_nw; s.dbg_split = w.dbg_split; s.dbg_lds = w.dbg_lds;
+    return s;
 }
 
-template <typename IO, typename Real>
-static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, const TileGeom &g_in)
+// a plan's VALU-tile and MFMA-tile geometries (the MFMA one: planes where the period admits them, else the general-period form)
+struct TileGeoms { TileGeom gv, gm; };
+static TileGeoms tile_geoms(const Plan *p, int prec)
 {
-    const DeviceBank &d = p->dev[sizeof(Real) == 4 ? 0 : 1];
-    // float64 planar kernel: a job of few 32-period slabs runs on 16-period ones (k_tile_mfma64_p<.., PB>) — same
-    // tables, half the slab: the geometry's LDS figures are re-derived here
-    TileGeom g = g_in;
-    int f64_pb = 32;
-    if (sizeof(Real) == 8 && g.variant == 2) {
-        const int64_t slabs32 = ((j.out_k0 + j.out_frames - 1) / g.Lc - j.out_k0 / g.Lc + 32) / 32 * (int64_t)j.n_clips * j.n_channels;
-        if ((slabs32 < 6 * 256 || switches().dbg_mfma64_pb == 16) && switches().dbg_mfma64_pb != 32) {
-            f64_pb = 16;
-            planes_set_pb<Real>(g, 16);
-        }
+    TileGeoms t;
+    std::lock_guard<std::mutex> lk(g_geom_mu);
+    if (TileGeom *gp = geom_find(p, prec, 0)) t.gv = *gp;
+    if (TileGeom *gp = geom_find(p, prec, 1)) t.gm = *gp;
+    return t;
+}
+
+static TileSelector tile_selector(int kernel)
+{
+    switch (kernel) {
+    case HIPSOXR_KERNEL_AUTO: return kSelAuto;
+    case HIPSOXR_KERNEL_GATHER: return kSelGather;
+    case HIPSOXR_KERNEL_TILE: return kSelTile;
+    case HIPSOXR_KERNEL_TILE_VALU: return kSelTileValu;
+    case HIPSOXR_KERNEL_TILE_MFMA: return kSelTileMfma;
+    default: return kSelOther;
     }
-    // float32 planar kernel: slab size and unit split by job size.  A slab of 64 periods (41 KB of LDS, three workgroups
-    // per CU) has 2 n_rt units (row tile x 32 periods), one of 32 periods (20 KB, seven per CU) n_rt; either runs as ONE
-    // workgroup (four waves, the units dealt round-robin) or SPLIT over ceil(units / 4) workgroups of one unit per wave,
-    // each staging the slab for itself.  What a job of few slabs costs is decided by how many workgroups deep the CUs
-    // are stacked ("layers": the dispatcher fills 256 CUs evenly only in whole layers) times what one workgroup does
-    // serially, plus staging; the constants are fitted to tools/slab_ab.sh sweeps (10 .. 6016 slabs, 48k -> 44.1k VHQ,
-    // profiles/r03_ab_experiments.txt), in units of one unit's MFMA time:
-    //     cost = c0 + layers x (units per wave) x k;   (pb, one unit per wave): c0, k = 32: 1.15, 1.153 | 64: 1.25, 1.41
-    //                                                  (pb, several)          :         32: 2.35, 0.958 | 64: 3.32, 1.052
-    // e.g. 47 slabs (a 10 s clip): 64/split (235 workgroups, one layer); 20: 32/split (120 workgroups staging half as
-    // much); 376: 32/whole (752 workgroups, 3 layers of 3 units: 35 us where round 2's 64/4 took 51); from 512 slabs of
-    // 64 on the whole-slab form is the rule again (12 waves per CU stream coefficients for 20 units each).
-    int f32_split = 0;
-    if (sizeof(Real) == 4 && g.variant == 2 && !switches().dbg_slab64) {
-        const int64_t periods = (j.out_k0 + j.out_frames - 1) / g.Lc - j.out_k0 / g.Lc + 1, cols_ = (int64_t)j.n_clips * j.n_channels;
-        const int64_t slabs64 = (periods + 63) / 64 * cols_, slabs32 = (periods + 31) / 32 * cols_;
-        int best_pb = 64, best_split = 1;
-        planes_form(slabs64, slabs32, g.n_rt, &best_pb, &best_split);
-        f32_split = best_split;
-        if (best_pb == 32) {
-            planes_set_pb<Real>(g, 32);
-        }
-    }
-    // float32 MFMA kernel in its general form (k_tile_mfma: input periods that are no multiple of 16, e.g. 44.1k -> 16k):
-    // a job of few 64-period slabs — a 96 000-frame stream chunk is four — runs on 16-period ones: four times as many
-    // workgroups, each staging a quarter and walking a chain a quarter as long (one wave does a row tile x ALL the
-    // slab's periods, and its ~880 k-steps cost the same whether they feed four MFMAs or one: the chain is bound by its
-    // per-step address arithmetic).  96 000-frame chunk, int16 44.1k -> 16k: kernel 53.6 -> 26.5 us, the stream call 108 -> 81 us.
-    bool v1_small = false; // the small-job form of the general-period kernel (16-period slabs, half-chains on two waves)
-    if (g.variant == 1 && g.pb > 16 && !switches().dbg_slab64) { // (float64 too: k_tile_mfma<IO, double, 1>)
-        const int64_t periods = (j.out_k0 + j.out_frames - 1) / g.Lc - j.out_k0 / g.Lc + 1;
-        // (up to 96 slabs of 64 periods: 8 x 96 workgroups of 10 waves are what the chip holds at once — tools/slab16_ab.sh:
-        //  50 slabs 54 -> 33 us, 100 slabs 65 -> 63, 127 slabs 66 -> 76)
-        const int64_t s64 = (periods + 63) / 64 * (int64_t)j.n_clips * j.n_channels;
-        v1_small = s64 <= 96 || switches().dbg_slab32;
-        // Beyond that: 16-period slabs WITHOUT the half-chain split where four times as many, four times shorter
-        // workgroups fill the chip's layers better than 64-period ones — a layer of 256 workgroups of the 16-period
-        // form costs 0.276 of a 64-period layer (not 0.25), a last 64-period layer that is at most half full 0.82
-        // (tools/slab16_ab.sh: 127 slabs 45 -> 33 us, 300: 108 -> 77, 800: 213 -> 190; 250 and 500 stay)
-        bool v1_mid = false;
-        if (!v1_small && s64 < 4096 && !switches().no_halves) {
-            // (in layers of the plan's own slab size — 64 periods, or 32 where a float64 slab of 64 does not fit LDS,
-            //  whose layer a 16-period one costs 0.53 of)
-            const double s0 = (double)((periods + g.pb - 1) / g.pb * (int64_t)j.n_clips * j.n_channels);
-            const double l0 = std::ceil(s0 / 256.), frac = s0 / 256. - (l0 - 1.);
-            const double est0 = (l0 - 1.) + (frac <= 0.5 ? 0.82 : 1.0);
-            const double est16 = 0.04 + (g.pb == 64 ? 0.276 : 0.53) * std::ceil((double)((periods + 15) / 16 * (int64_t)j.n_clips * j.n_channels) / 256.);
-            v1_mid = est16 < est0;
-        }
-        if (v1_small || v1_mid) {
-            g.pb = 16;
-            g.x_count = ((g.pb - 1) * (int32_t)g.Mc + g.span + 3) / 4 * 4;
-            g.lds_bytes = ((size_t)g.x_count + (size_t)g.pad * (g.x_count / g.Mc + 1) + 8) * sizeof(Real);
-        }
-    }
-    TileArgs a;
+}
+
+// The arguments of a launch of form f.  An equal-length job: its window and clip strides.  A ragged one (`ragged`): whole
+// signals, a clip's place and frame counts its row's — zero clip strides, zero window fields; the caller adds TileArgsR::rows.
+static void tile_args(TileArgs &a, const DeviceBank &d, const TileGeom &g, const TileForm &f, const hipsoxr_job_t &j, bool ragged)
+{
     a.in = j.in; a.out = j.out;
     a.tab = g.variant >= 1 ? d.tile_tab_m : d.tile_tab;
     a.e0 = g.variant >= 1 ? d.tile_i0_m : d.tile_i0;
-    a.Lc = g.Lc; a.Mc = g.Mc; a.n_rt = g.n_rt; a.I_h = g.I_h;
-    a.pad = g.pad; a.i_min = g.i_min; a.x_count = g.x_count; a.pb = g.pb;
+    a.Lc = g.Lc; a.Mc = g.Mc; a.n_rt = f.n_rt; a.I_h = g.I_h;
+    a.pad = g.pad; a.i_min = g.i_min; a.x_count = f.slab.x_count; a.pb = f.slab.pb;
     a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-    a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
-    a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-    a.in_abs0 = j.in_abs0; a.in_frames = j.in_frames;
-    a.out_k0 = j.out_k0; a.out_frames = j.out_frames;
+    a.ics = ragged ? 0 : j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
+    a.ocs = ragged ? 0 : j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.in_abs0 = ragged ? 0 : j.in_abs0; a.in_frames = ragged ? 0 : j.in_frames;
+    a.out_k0 = ragged ? 0 : j.out_k0; a.out_frames = ragged ? 0 : j.out_frames;
+    a.b_first = ragged ? 0 : tile_first_period(j.out_k0, g.Lc);
     a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
-    // periods touched: floor(k0/Lc) .. floor((k0+n-1)/Lc)
-    const int64_t b_lo = j.out_k0 / g.Lc, b_hi = (j.out_k0 + j.out_frames - 1) / g.Lc;
-    a.b_first = b_lo;
-    const int64_t n_blocks = (b_hi - b_lo + g.pb) / g.pb;
-    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-    if (cols > 65535) return "too many (clip, channel) columns for one launch (max 65535)";
-    if (n_blocks > 2147483647LL) return "job too long for one launch";
-    // waves per workgroup: one tile per wave when n_rt <= 16, else the even split with most waves
-    int nw = g.n_rt;
-    if (g.n_rt > 16) {
-        int best = 16, best_waste = 1 << 30;
-        for (int w = 16; w >= 8; --w) {
-            int rounds = (g.n_rt + w - 1) / w, waste = rounds * w - g.n_rt;
-            if (waste < best_waste) { best_waste = waste; best = w; }
-        }
-        nw = best;
-    }
-    if (g.variant == 2) nw = 4; // k_tile_mfma_p / k_tile_mfma64_p: one wave per SIMD, the slab's units dealt round-robin
-    // (f32: tile x half of 64 periods; float64: tile x all periods of the slab — or tile x 16 periods, HIPSOXR_DEBUG_MFMA64_SPLIT)
-    const int units_per_slab = sizeof(Real) == 4 ? (g.pb / 32) * g.n_rt : (f64_pb == 32 && switches().dbg_mfma64_split) ? 2 * g.n_rt : g.n_rt;
-    if (switches().dbg_nrt) { a.n_rt = switches().dbg_nrt; nw = a.n_rt; }
-    if (switches().dbg_nw) nw = switches().dbg_nw;
-    a.n_waves = nw;
-    {
-        a.dbg = switches().dbg_flags;
-    }
-    // (HIPSOXR_DEBUG_* are timing experiments only; results may be wrong when they are set)
-    void (*kern)(TileArgs) = g.aligned ? k_tile<IO, Real, 16, true> : k_tile<IO, Real, 16, false>;
-    if constexpr (sizeof(Real) == 4) {
-        if (g.variant == 1) kern = g.pb == 64 ? k_tile_mfma<IO, float, 4> : g.pb == 32 ? k_tile_mfma<IO, float, 2> : k_tile_mfma<IO, float, 1>;
-        if (g.variant == 2) kern = k_tile_mfma_p<IO>;
-    } else {
-        if (g.variant == 1) kern = g.pb == 32 ? k_tile_mfma<IO, double, 2> : k_tile_mfma<IO, double, 1>; // (pb = 64 is never chosen for float64: build_tile_tables)
-        if (g.variant == 2) kern = f64_pb == 16 ? k_tile_mfma64_p<IO, 1, 16> : switches().dbg_mfma64_split ? k_tile_mfma64_p<IO, 1, 32> : k_tile_mfma64_p<IO, 2, 32>;
-    }
-    a.rowR = g.rowR; a.plane = g.plane;
-    a.halves = 0; a.scratch_off = 0;
-    dim3 grid((unsigned)n_blocks, (unsigned)cols, 1), block(64 * nw);
-    if (g.variant == 2) {
-        // few slabs (e.g. one 60 s mono clip = 282): spread each slab's 2*n_rt units over up to
-        // ceil(2*n_rt/4) workgroups so that every CU gets an equal share (3 resident per CU)
-        const int64_t wgs = n_blocks * (int64_t)cols;
-        // (from two workgroups per CU on, splitting only adds staging: measured 80 vs 92 us on a 60 s stereo clip)
-        int split = wgs >= 512 ? 1 : (int)std::min<int64_t>((units_per_slab + 3) / 4, (2 * 3 * 256) / std::max<int64_t>(wgs, 1));
-        if (f32_split) split = f32_split; // (float32: chosen with the slab size above)
-        if (switches().dbg_split) split = switches().dbg_split;
-        grid.z = (unsigned)std::max(1, split);
-        a.xz = 0; a.nx = (int32_t)n_blocks;
-        if (grid.z > 1 && !switches().no_xcd_split && (n_blocks + 7) / 8 * 8 * (int64_t)grid.z < 2147483647LL) {
-            a.xz = (int32_t)grid.z; // XCD-aware 1-D ids instead of the z dimension
-            grid.x = (unsigned)((n_blocks + 7) / 8 * 8 * (int64_t)grid.z);
-            grid.z = 1;
-        }
-    } else {
-        a.xz = 0; a.nx = (int32_t)n_blocks;
-        // few slabs (one column of a stream chunk: 96 000 frames at 44.1k -> 16k are 4 slabs on 256 CUs): the
-        // row tiles of a slab go to several workgroups of fewer computing waves, each staging the slab for itself
-        const int64_t wgs = n_blocks * (int64_t)cols;
-        int split = 1;
-        // (as many workgroups as fill the chip once: every one of them stages the whole slab)
-        if (wgs < 128 && g.n_rt > 1 && !switches().dbg_nw && !switches().no_tile_split) split = (int)std::min<int64_t>(g.n_rt, 256 / wgs);
-        if (switches().dbg_split) split = std::min(switches().dbg_split, g.n_rt);
-        if (split > 1) {
-            const int per_wg = std::min(16, (g.n_rt + split - 1) / split); // row tiles (= computing waves) per workgroup: a block holds 16 waves
-            nw = per_wg; a.n_waves = nw;
-            block = dim3((unsigned)std::max(256, 64 * per_wg)); // (at least four waves stage the slab)
-            grid.z = (unsigned)((g.n_rt + per_wg - 1) / per_wg);
-        }
-        // small float32 jobs on 16-period slabs: a row tile's two half-chains on two waves (k_tile_mfma, a.halves)
-        if (g.variant == 1 && g.pb == 16 && g_in.pb != 16 && v1_small && !switches().dbg_nw && !switches().dbg_nrt && !switches().no_halves) {
-            const int want = (int)grid.z > 1 ? nw : g.n_rt, parts = (want + 7) / 8;
-            const int per_wg = (want + parts - 1) / parts; // row tiles per workgroup (at most 8: two waves each), evenly
-            nw = 2 * per_wg; a.n_waves = nw; a.halves = 1;
-            block = dim3((unsigned)std::max(256, 64 * nw));
-            grid.z = (unsigned)((g.n_rt + per_wg - 1) / per_wg);
-            a.scratch_off = (int32_t)((g.lds_bytes / sizeof(Real) + 63) / 64 * 64);
-            g.lds_bytes = ((size_t)a.scratch_off + (size_t)per_wg * (g.pb / 16) * 4 * 64) * sizeof(Real);
-        }
-    }
-    size_t lds_bytes = g.lds_bytes;
-    lds_bytes = std::max<size_t>(lds_bytes, switches().dbg_lds); // occupancy experiments
-    if (const char *e = ensure_dyn_lds((const void *)kern, lds_bytes)) return e;
+    a.n_waves = f.n_waves;
+    a.dbg = ragged ? 0 : switches().dbg_flags;
+    a.rowR = g.rowR; a.plane = f.slab.plane;
+    a.halves = f.halves; a.scratch_off = f.scratch_off;
+    a.xz = f.xz; a.nx = f.nx;
     a.trace = nullptr;
-    const char *trace_path = switches().dbg_trace;
-    size_t trace_n = 0;
-    if (trace_path && g.variant == 2) {
-        trace_n = (size_t)grid.x * cols * grid.z * 4 * 16;
-        HIP_TRY(hipMalloc((void **)&a.trace, trace_n * 8));
-        HIP_TRY(hipMemset(a.trace, 0, trace_n * 8));
+}
+
+// the only place on the launch side that names a tile kernel instance (in the order of first use the object's kernels have
+// had since launch_tile and launch_ragged named them: profiles/NOTES_launch_refactor.md §1)
+template <typename IO, typename Real, bool RAGGED>
+static void (*tile_kernel(const TileForm &f, bool aligned))(typename TileArgsOf<RAGGED>::type)
+{
+    const int pb = f.slab.pb;
+    if constexpr (!RAGGED) {
+        void (*kern)(TileArgs) = aligned ? k_tile<IO, Real, 16, true> : k_tile<IO, Real, 16, false>;
+        if constexpr (sizeof(Real) == 4) {
+            if (f.kind == kTileMfma) kern = pb == 64 ? k_tile_mfma<IO, float, 4> : pb == 32 ? k_tile_mfma<IO, float, 2> : k_tile_mfma<IO, float, 1>;
+            if (f.kind == kTileMfmaP) kern = k_tile_mfma_p<IO>;
+        } else {
+            if (f.kind == kTileMfma) kern = pb == 32 ? k_tile_mfma<IO, double, 2> : k_tile_mfma<IO, double, 1>; // (pb = 64 is never chosen for float64: build_tile_tables)
+            if (f.kind == kTileMfma64P) kern = pb == 16 ? k_tile_mfma64_p<IO, 1, 16> : f.ng == 1 ? k_tile_mfma64_p<IO, 1, 32> : k_tile_mfma64_p<IO, 2, 32>;
+        }
+        return kern;
+    } else { // (the plan's own slabs: float32 64 periods, float64 32 or 16 — tile_form_ragged refuses any other)
+        void (*kern)(TileArgsR) = nullptr;
+        if constexpr (sizeof(Real) == 4) {
+            if (f.kind == kTileMfmaP) kern = k_tile_mfma_p<IO, true>;
+            if (f.kind == kTileMfma) kern = k_tile_mfma<IO, float, 4, true>;
+        } else {
+            if (f.kind == kTileMfma64P) kern = k_tile_mfma64_p<IO, 2, 32, true>;
+            if (f.kind == kTileMfma) kern = pb == 32 ? k_tile_mfma<IO, double, 2, true> : k_tile_mfma<IO, double, 1, true>;
+        }
+        if (f.kind == kTile) kern = aligned ? k_tile<IO, Real, 16, true, true> : k_tile<IO, Real, 16, false, true>;
+        return kern;
     }
-    hipLaunchKernelGGL(kern, grid, block, lds_bytes, st, a);
-    HIP_TRY(hipGetLastError());
-    if (a.trace) { // debugging aid only: synchronous dump of the per-wave time stamps
-        std::vector<unsigned long long> h(trace_n);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(h.data(), a.trace, trace_n * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(trace_path, "wb")) { fwrite(h.data(), 8, trace_n, f); fclose(f); }
-        (void)hipFree(a.trace);
-    }
+}
+
+// (HIPSOXR_DEBUG_TRACE, planar kernels: per-wave time stamps [workgroup][wave][16], dumped synchronously behind the launch —
+//  a debugging aid)
+static const char *tile_trace_begin(TileArgs &a, const TileForm &f, size_t *n)
+{
+    *n = (size_t)f.grid[0] * f.grid[1] * f.grid[2] * 4 * 16;
+    if (!switches().dbg_trace || (f.kind != kTileMfmaP && f.kind != kTileMfma64P)) return nullptr;
+    HIP_TRY(hipMalloc((void **)&a.trace, *n * 8));
+    HIP_TRY(hipMemset(a.trace, 0, *n * 8));
     return nullptr;
+}
+static const char *tile_trace_dump(const TileArgs &a, size_t n, hipStream_t st)
+{
+    if (!a.trace) return nullptr;
+    std::vector<unsigned long long> h(n);
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpy(h.data(), a.trace, n * 8, hipMemcpyDeviceToHost));
+    if (FILE *f = fopen(switches().dbg_trace, "wb")) { fwrite(h.data(), 8, n, f); fclose(f); }
+    (void)hipFree(a.trace);
+    return nullptr;
+}
+
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per tile launch — an equal-length job's, or (ragged_clips >= 0,
+// `ragged=<clips>` at the end; g == nullptr: its k_gather form) a ragged launch's — in the style of adj_launch_log: what
+// tests/test_gpu_tile_forms.py and tests/test_gpu_ragged_exact.py read the launch form from.
+template <typename IO, typename Real>
+static void tile_launch_log(const char *kernel, const Plan &p, const TileGeom *g, const TileForm &f, int64_t ragged_clips)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    fprintf(fl, "kernel=%s width=%zu io=%c%zu L=%lld M=%lld Lc=%lld Mc=%lld pb=%d n_rt=%d nw=%d split=%d halves=%d xz=%d lds=%zu grid=%ux%ux%u block=%u", kernel,
+            sizeof(Real), std::is_integral<IO>::value ? 'i' : 'f', sizeof(IO) * 8, (long long)p.L, (long long)p.M, (long long)(g ? g->Lc : 0),
+            (long long)(g ? g->Mc : 0), g ? (int)f.slab.pb : 0, g ? f.n_rt : 0, f.n_waves, f.split, f.halves, (int)f.xz, f.lds, f.grid[0], f.grid[1], f.grid[2], f.block);
+    if (ragged_clips >= 0) fprintf(fl, " ragged=%lld", (long long)ragged_clips);
+    fputc('\n', fl);
+    fclose(fl);
+}
+
+template <typename IO, typename Real>
+static const char *launch_tile(Plan *p, const hipsoxr_job_t &j, hipStream_t st, const TileGeom &g)
+{
+    const TileForm f = tile_form(sizeof(Real), g, j.out_k0, j.out_frames, (uint64_t)j.n_clips * j.n_channels, tile_switches());
+    if (f.err) return f.err;
+    TileArgs a;
+    tile_args(a, bank_of<Real>(p), g, f, j, false);
+    void (*kern)(TileArgs) = tile_kernel<IO, Real, false>(f, g.aligned);
+    if (const char *e = ensure_dyn_lds((const void *)kern, f.lds)) return e;
+    size_t trace_n = 0;
+    if (const char *e = tile_trace_begin(a, f, &trace_n)) return e;
+    hipLaunchKernelGGL(kern, dim3(f.grid[0], f.grid[1], f.grid[2]), dim3(f.block), f.lds, st, a);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) tile_launch_log<IO, Real>(tile_kind_name(f.kind), *p, &g, f, -1);
+    return tile_trace_dump(a, trace_n, st);
 }
 
 template <typename IO, typename Real>
@@ -1306,46 +1210,32 @@ static const char *launch_typed(Plan *p, const hipsoxr_job_t &j, hipStream_t st,
                                 ChainDone *cd = nullptr)
 {
     if (res) return launch_gather<IO, Real>(p, j, st, vr, res);
-    const int prec = sizeof(Real) == 4 ? 0 : 1;
-    TileGeom gv, gm; // VALU-tile and MFMA-tile geometries (f32: planes / k_tile_mfma; f64: k_tile_mfma<IO, double, NG>)
-    {
-        std::lock_guard<std::mutex> lk(g_geom_mu);
-        if (TileGeom *gp = geom_find(p, prec, 0)) gv = *gp;
-        if (TileGeom *gp = geom_find(p, prec, 1)) gm = *gp;
-    }
+    const TileGeoms t = tile_geoms(p, sizeof(Real) == 4 ? 0 : 1);
     int kernel = j.kernel;
     if (kernel == HIPSOXR_KERNEL_WAVE_DOT) return vr ? "wave-dot kernel does not do variable rate" : launch_wave_dot<IO, Real>(p, j, st);
     if (kernel == HIPSOXR_KERNEL_EXACT || kernel == HIPSOXR_KERNEL_FFT) kernel = HIPSOXR_KERNEL_AUTO;
     if (p->phases) { // interpolated-phase plan: one kernel (k_interp, dispatched by launch_gather)
-        if (kernel != HIPSOXR_KERNEL_AUTO && kernel != HIPSOXR_KERNEL_GATHER)
-            return "tile kernel unavailable for this plan";
+        if (kernel != HIPSOXR_KERNEL_AUTO && kernel != HIPSOXR_KERNEL_GATHER) return kTileUnavailable;
         return launch_gather<IO, Real>(p, j, st, vr, nullptr, cd);
     }
     if (vr) return "variable-rate needs an interpolated-phase plan";
-    if (kernel == HIPSOXR_KERNEL_TILE_VALU && !gv.ok) return "tile kernel unavailable for this plan";
-    if (kernel == HIPSOXR_KERNEL_TILE_MFMA && !gm.ok) return "tile kernel unavailable for this plan";
-    if (kernel == HIPSOXR_KERNEL_TILE) {
-        if (!gv.ok && !gm.ok) return "tile kernel unavailable for this plan";
-        kernel = gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
+    const TileGeom &g = t.gm.ok ? t.gm : t.gv;
+    bool big = tile_big(g.ok, g.Lc, j.out_frames);
+    // ... except for a stream chunk whose result the kernel writes straight into pinned host memory (`cd`: engine.cpp's
+    // direct path) while it is far too small to fill the chip with slabs.  As a kernel k_gather_wave is the slower one
+    // even there (96 000 frames at 44.1k -> 16k: 17.5 against 15.6 us; back to back on device buffers 15.0 against 9.6),
+    // but the CALL is shorter with it — its outputs leave as runs of 16 neighbouring samples, the tiles' as one sample
+    // per lane of a row tile: 20 000-frame int16 calls 35 against 41 us, 48 000-frame 43.5 against 45.6, 96 000-frame
+    // the same (interleaved A/B on one box, tools/gw_time.sh).  Up to kGatherWaveTaps output x tap products.
+    if (big && cd && !switches().no_gather_wave && p->T >= 32 &&
+        (double)j.out_frames * j.n_clips * j.n_channels * p->T < (switches().dbg_gw_taps ? switches().dbg_gw_taps * 1e6 : kGatherWaveTaps))
+        big = false;
+    switch (tile_family(tile_selector(kernel), t.gv.ok, t.gm.ok, big)) {
+    case kFamRefused: return kTileUnavailable;
+    case kFamTileMfma: return launch_tile<IO, Real>(p, j, st, t.gm);
+    case kFamTileValu: return launch_tile<IO, Real>(p, j, st, t.gv);
+    default: return launch_gather<IO, Real>(p, j, st, nullptr, nullptr, cd);
     }
-    if (kernel == HIPSOXR_KERNEL_AUTO) {
-        // a tile kernel pays off once a job spans a few thousand outputs per column
-        const TileGeom &g = gm.ok ? gm : gv;
-        bool big = g.ok && j.out_frames >= 16 * g.Lc && j.out_frames >= 4096;
-        // ... except for a stream chunk whose result the kernel writes straight into pinned host memory (`cd`: engine.cpp's
-        // direct path) while it is far too small to fill the chip with slabs.  As a kernel k_gather_wave is the slower one
-        // even there (96 000 frames at 44.1k -> 16k: 17.5 against 15.6 us; back to back on device buffers 15.0 against 9.6),
-        // but the CALL is shorter with it — its outputs leave as runs of 16 neighbouring samples, the tiles' as one sample
-        // per lane of a row tile: 20 000-frame int16 calls 35 against 41 us, 48 000-frame 43.5 against 45.6, 96 000-frame
-        // the same (interleaved A/B on one box, tools/gw_time.sh).  Up to kGatherWaveTaps output x tap products.
-        if (big && cd && !switches().no_gather_wave && p->T >= 32 &&
-            (double)j.out_frames * j.n_clips * j.n_channels * p->T < (switches().dbg_gw_taps ? switches().dbg_gw_taps * 1e6 : kGatherWaveTaps))
-            big = false;
-        kernel = !big ? HIPSOXR_KERNEL_GATHER : gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
-    }
-    if (kernel == HIPSOXR_KERNEL_TILE_MFMA) return launch_tile<IO, Real>(p, j, st, gm);
-    if (kernel == HIPSOXR_KERNEL_TILE_VALU) return launch_tile<IO, Real>(p, j, st, gv);
-    return launch_gather<IO, Real>(p, j, st, nullptr, nullptr, cd);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1357,16 +1247,24 @@ static const char *launch_typed(Plan *p, const hipsoxr_job_t &j, hipStream_t st,
 // slabs) and the trace.  *handled stays false for what is still served clip by clip (interpolated-phase plans, the wave-dot
 // kernel, a table with a clip of more than 2^30 outputs: launch_ragged_job).
 // ---------------------------------------------------------------------------------------------
-struct RaggedForm { const char *kernel; int split; size_t lds; dim3 grid, block; };
-// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per ragged exact launch, in the style of adj_launch_log
-static void ragged_launch_log(size_t width, const Plan &p, const TileGeom *g, const RaggedForm &f, uint32_t n_clips)
+// k_gather's ragged form: one lane per output of the longest clip
+template <typename IO, typename Real>
+static const char *launch_ragged_gather(Plan *p, const hipsoxr_job_t &j, hipStream_t st, int64_t longest, uint64_t cols)
 {
-    FILE *fl = fopen(switches().dbg_launch_log, "a");
-    if (!fl) return;
-    fprintf(fl, "kernel=%s width=%zu L=%lld M=%lld Lc=%lld Mc=%lld pb=%d n_rt=%d split=%d lds=%zu grid=%ux%ux%u block=%u ragged=%u\n", f.kernel, width,
-            (long long)p.L, (long long)p.M, (long long)(g ? g->Lc : 0), (long long)(g ? g->Mc : 0), g ? g->pb : 0, g ? g->n_rt : 0, f.split, f.lds,
-            f.grid.x, f.grid.y, f.grid.z, f.block.x, n_clips);
-    fclose(fl);
+    hipsoxr_job_t jj = j;
+    jj.in_clip_stride = jj.out_clip_stride = 0; // (a clip's place is its row's)
+    GatherArgsR a;
+    (GatherArgs &)a = make_gather_args<IO>(*p, bank_of<Real>(p), jj, 0, longest, 0);
+    a.rows = j.clip_table_dev;
+    const int64_t gx = ragged_gather_grid_x(longest, a.ch_fast ? j.n_channels : 1);
+    if (gx > kTileMaxGridX) return kTileTooLong;
+    TileForm f;
+    f.grid[0] = (unsigned)gx; f.grid[1] = a.ch_fast ? j.n_clips : (unsigned)cols;
+    f.block = 256; f.split = 0; // (the log line's fields: no slab, no split)
+    hipLaunchKernelGGL((k_gather<IO, Real, true>), dim3(f.grid[0], f.grid[1], 1), dim3(f.block), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) tile_launch_log<IO, Real>("gather", *p, nullptr, f, j.n_clips);
+    return nullptr;
 }
 
 // j: the job of one launch — clip_table the host rows of its n_clips clips, clip_table_dev their device copy
@@ -1375,117 +1273,31 @@ static const char *launch_ragged(Plan *p, const hipsoxr_job_t &j, hipStream_t st
 {
     *handled = false;
     if (p->phases || j.kernel == HIPSOXR_KERNEL_WAVE_DOT) return nullptr;
-    const int prec = sizeof(Real) == 4 ? 0 : 1;
-    const DeviceBank &d = bank_of<Real>(p);
-    TileGeom gv, gm;
-    {
-        std::lock_guard<std::mutex> lk(g_geom_mu);
-        if (TileGeom *gp = geom_find(p, prec, 0)) gv = *gp;
-        if (TileGeom *gp = geom_find(p, prec, 1)) gm = *gp;
-    }
+    const TileGeoms t = tile_geoms(p, sizeof(Real) == 4 ? 0 : 1);
     const int64_t longest = ragged_longest(j.clip_table, j.n_clips);
-    int kernel = j.kernel;
-    if (kernel == HIPSOXR_KERNEL_EXACT) kernel = HIPSOXR_KERNEL_AUTO;
-    if (kernel == HIPSOXR_KERNEL_TILE_VALU && !gv.ok) return "tile kernel unavailable for this plan";
-    if (kernel == HIPSOXR_KERNEL_TILE_MFMA && !gm.ok) return "tile kernel unavailable for this plan";
-    if (kernel == HIPSOXR_KERNEL_TILE) {
-        if (!gv.ok && !gm.ok) return "tile kernel unavailable for this plan";
-        kernel = gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
-    }
-    if (kernel == HIPSOXR_KERNEL_AUTO) {
-        const TileGeom &g = gm.ok ? gm : gv;
-        const bool big = g.ok && longest >= 16 * g.Lc && longest >= 4096;
-        kernel = !big ? HIPSOXR_KERNEL_GATHER : gm.ok ? HIPSOXR_KERNEL_TILE_MFMA : HIPSOXR_KERNEL_TILE_VALU;
-    }
-    if (kernel != HIPSOXR_KERNEL_GATHER && kernel != HIPSOXR_KERNEL_TILE_MFMA && kernel != HIPSOXR_KERNEL_TILE_VALU) return nullptr;
+    const TileGeom &g0 = t.gm.ok ? t.gm : t.gv;
+    const TileFamily fam = tile_family(tile_selector(j.kernel == HIPSOXR_KERNEL_EXACT ? HIPSOXR_KERNEL_AUTO : j.kernel), t.gv.ok, t.gm.ok,
+                                       tile_big(g0.ok, g0.Lc, longest));
+    if (fam == kFamRefused) return kTileUnavailable;
+    if (fam == kFamOther) return nullptr;
     *handled = true;
     if (longest == 0) return nullptr; // nothing to write
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-    if (cols > kMaxGridY) return "too many (clip, channel) columns for one launch (max 65535)";
-    RaggedForm f{};
+    if (cols > kMaxGridY) return kTileTooManyCols;
+    if (fam == kFamGather) return launch_ragged_gather<IO, Real>(p, j, st, longest, cols);
 
-    if (kernel == HIPSOXR_KERNEL_GATHER) {
-        hipsoxr_job_t jj = j;
-        jj.in_clip_stride = jj.out_clip_stride = 0; // (a clip's place is its row's)
-        GatherArgsR a;
-        (GatherArgs &)a = make_gather_args<IO>(*p, d, jj, 0, longest, 0);
-        a.rows = j.clip_table_dev;
-        const int64_t gx = ragged_gather_grid_x(longest, a.ch_fast ? j.n_channels : 1);
-        if (gx > 2147483647LL) return "job too long for one launch";
-        f.kernel = "gather";
-        f.grid = a.ch_fast ? dim3((unsigned)gx, j.n_clips, 1) : dim3((unsigned)gx, (unsigned)cols, 1);
-        f.block = dim3(256);
-        hipLaunchKernelGGL((k_gather<IO, Real, true>), f.grid, f.block, 0, st, a);
-        HIP_TRY(hipGetLastError());
-        if (switches().dbg_launch_log) ragged_launch_log(sizeof(Real), *p, nullptr, f, j.n_clips);
-        return nullptr;
-    }
-
-    TileGeom g = kernel == HIPSOXR_KERNEL_TILE_MFMA ? gm : gv;
-    void (*kern)(TileArgsR) = nullptr;
-    int nw = g.n_rt; // waves per workgroup: launch_tile's rule
-    if (g.n_rt > 16) {
-        int best = 16, best_waste = 1 << 30;
-        for (int w = 16; w >= 8; --w) {
-            const int rounds = (g.n_rt + w - 1) / w, waste = rounds * w - g.n_rt;
-            if (waste < best_waste) { best_waste = waste; best = w; }
-        }
-        nw = best;
-    }
-    f.split = 1;
-    if (g.variant == 2) {
-        nw = 4;
-        if constexpr (sizeof(Real) == 4) { // slab size and unit split by the slabs the table holds
-            int pb = 64;
-            planes_form(ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, 64), ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, 32),
-                        g.n_rt, &pb, &f.split);
-            if (pb == 32) planes_set_pb<Real>(g, 32);
-            kern = k_tile_mfma_p<IO, true>; f.kernel = "tile_mfma_p";
-        } else { // launch_tile's rule for the float64 planar kernel (32-period slabs, a row tile per unit), on the table's slabs
-            const int64_t wgs = std::max<int64_t>(ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, g.pb), 1);
-            f.split = wgs >= 512 ? 1 : (int)std::min<int64_t>((g.n_rt + 3) / 4, (2 * 3 * 256) / wgs);
-            kern = k_tile_mfma64_p<IO, 2, 32, true>; f.kernel = "tile_mfma64_p";
-        }
-        f.split = std::max(1, f.split);
-    } else if (g.variant == 1) {
-        f.kernel = "tile_mfma";
-        if constexpr (sizeof(Real) == 4) kern = k_tile_mfma<IO, float, 4, true>; // (float32 slabs are 64 periods: build_tile_tables)
-        else kern = g.pb == 32 ? k_tile_mfma<IO, double, 2, true> : k_tile_mfma<IO, double, 1, true>;
-        if (sizeof(Real) == 4 ? g.pb != 64 : (g.pb != 32 && g.pb != 16)) return "internal: tile geometry without a ragged kernel";
-    } else {
-        f.kernel = "tile";
-        kern = g.aligned ? k_tile<IO, Real, 16, true, true> : k_tile<IO, Real, 16, false, true>;
-    }
+    const TileGeom &g = fam == kFamTileMfma ? t.gm : t.gv;
+    const TileForm f = tile_form_ragged(sizeof(Real), g, cols, tile_switches(), [&](int32_t pb) { return ragged_grid_x(longest, g.Lc, pb); },
+                                        [&](int32_t pb) { return ragged_total_slabs(j.clip_table, j.n_clips, j.n_channels, g.Lc, pb); });
+    if (f.err) return f.err;
     TileArgsR a;
-    a.in = j.in; a.out = j.out;
-    a.tab = g.variant >= 1 ? d.tile_tab_m : d.tile_tab;
-    a.e0 = g.variant >= 1 ? d.tile_i0_m : d.tile_i0;
-    a.Lc = g.Lc; a.Mc = g.Mc; a.n_rt = g.n_rt; a.I_h = g.I_h;
-    a.pad = g.pad; a.i_min = g.i_min; a.x_count = g.x_count; a.pb = g.pb;
-    a.n_clips = j.n_clips; a.n_channels = j.n_channels;
-    a.ics = 0; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride; // (a clip's place is its row's)
-    a.ocs = 0; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
-    a.in_abs0 = 0; a.in_frames = 0; a.out_k0 = 0; a.out_frames = 0; a.b_first = 0; // (whole signals; frame counts: the rows')
-    a.oc.clip_counter = j.clip_counter; a.oc.dither = j.dither; a.oc.seed = j.dither_seed; a.oc.ch0 = t_ch_base;
-    a.n_waves = nw; a.dbg = 0; a.trace = nullptr;
-    a.rowR = g.rowR; a.plane = g.plane; a.halves = 0; a.scratch_off = 0;
+    tile_args(a, bank_of<Real>(p), g, f, j, true);
     a.rows = j.clip_table_dev;
-    const int64_t n_blocks = ragged_grid_x(longest, g.Lc, g.pb);
-    if (n_blocks > 2147483647LL) return "job too long for one launch";
-    a.xz = 0; a.nx = (int32_t)n_blocks;
-    f.grid = dim3((unsigned)n_blocks, (unsigned)cols, 1);
-    f.block = dim3(64 * nw);
-    if (g.variant == 2 && f.split > 1) {
-        if (!switches().no_xcd_split && (n_blocks + 7) / 8 * 8 * (int64_t)f.split < 2147483647LL) {
-            a.xz = f.split; // XCD-aware 1-D ids instead of the z dimension (launch_tile)
-            f.grid.x = (unsigned)((n_blocks + 7) / 8 * 8 * (int64_t)f.split);
-        } else f.grid.z = (unsigned)f.split;
-    }
-    f.lds = g.lds_bytes;
+    void (*kern)(TileArgsR) = tile_kernel<IO, Real, true>(f, g.aligned);
     if (const char *e = ensure_dyn_lds((const void *)kern, f.lds)) return e;
-    hipLaunchKernelGGL(kern, f.grid, f.block, f.lds, st, a);
+    hipLaunchKernelGGL(kern, dim3(f.grid[0], f.grid[1], f.grid[2]), dim3(f.block), f.lds, st, a);
     HIP_TRY(hipGetLastError());
-    if (switches().dbg_launch_log) ragged_launch_log(sizeof(Real), *p, &g, f, j.n_clips);
+    if (switches().dbg_launch_log) tile_launch_log<IO, Real>(tile_kind_name(f.kind), *p, &g, f, j.n_clips);
     return nullptr;
 }
 

@@ -91,9 +91,11 @@ def test_values_form_and_kind(runs, name):
     assert not got["fails"], got["fails"]
     (L, M), window, want = EXPECT[name][0], EXPECT[name][1], EXPECT[name][2]
     # the log holds every launcher's lines.  launch_fft_impl's begin with form=; the polyphase launch of a two-stage job
-    # (twostage.hip) writes one of its own, which tests/test_gpu_two_stage_forms.py reads
+    # (twostage.hip) writes one of its own, which tests/test_gpu_two_stage_forms.py reads; a job the engine declines under AUTO
+    # is the exact engine's, whose tile launch (kernels.hip) writes one too, which tests/test_gpu_tile_forms.py reads
     other = [l for l in got["lines"] if not l.startswith("form=")]
-    assert len(other) == (1 if name.startswith("two_stage") else 0) and all(l.startswith("kernel=poly") for l in other), other
+    poly, tile = [l for l in other if l.startswith("kernel=poly")], [l for l in other if l.startswith("kernel=tile") and "ragged=" not in l]
+    assert len(poly) == (1 if name.startswith("two_stage") else 0) and len(tile) == (1 if name.endswith("none_f64_auto") else 0) and len(other) == len(poly) + len(tile), other
     lines = [_fields(l) for l in got["lines"] if l.startswith("form=")]
     if want == "+":
         assert lines, "no launch was logged"

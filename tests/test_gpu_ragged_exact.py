@@ -145,7 +145,8 @@ def _lines(log):
 
 
 def _exact_lines(log):
-    return [f for f in _lines(log) if f.get("kernel") in EXACT_KERNELS]
+    """the ragged exact launches among the lines (an equal-length tile launch writes the same line without ragged=)"""
+    return [f for f in _lines(log) if f.get("kernel") in EXACT_KERNELS and "ragged" in f]
 
 
 def _bits(a):
