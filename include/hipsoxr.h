@@ -223,8 +223,12 @@ typedef struct {
      * or float64 clips, small jobs, HIPSOXR_KERNEL_EXACT and the tile / gather selectors — the kernel reads its clip's
      * row, the grid is the longest clip's (more than 65535 columns: one launch per range of clips).  Each clip has the
      * bits of the clip run alone; out[0, out_frames[c]) of every clip is written and nothing else, not the elements
-     * between packed clips either; clip_counter receives the sum over the clips.  Interpolated-phase plans and
-     * HIPSOXR_KERNEL_WAVE_DOT are served clip by clip from the same call, same results. */
+     * between packed clips either; clip_counter receives the sum over the clips.  An interpolated-phase plan (an
+     * arbitrary ratio) is ONE launch in the same way — int16 / int32 under the default selector, every type under
+     * HIPSOXR_KERNEL_EXACT / HIPSOXR_KERNEL_GATHER — on the ragged forms of its own kernels, each clip with the bits of
+     * the clip run alone.  Served clip by clip from the same call, same results: float clips of such a plan under
+     * HIPSOXR_KERNEL_AUTO (the two-stage form, another precision class), HIPSOXR_KERNEL_WAVE_DOT, and a table with a
+     * clip of more than 2^30 outputs. */
     const int64_t *clip_table;
     const int64_t *clip_table_dev;
 } hipsoxr_job_t;

@@ -175,14 +175,16 @@ __device__ __forceinline__ int64_t uniform64(int64_t v)
     return (int64_t)(((uint64_t)hi << 32) | lo);
 }
 template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const GatherArgs &a, uint32_t, GatherArgs &) { return a; }
-template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const GatherArgsR &r, uint32_t clip, GatherArgs &v)
+// the view of one clip: in, in_frames, out, out_frames are its row's
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_view(const GatherArgs &g, const int64_t *rows, uint32_t clip, GatherArgs &v)
 {
-    const int64_t *row = r.rows + 4 * (int64_t)__builtin_amdgcn_readfirstlane(clip);
-    v = r;
-    v.in = (const IO *)r.in + uniform64(row[0]); v.in_frames = uniform64(row[1]);
-    v.out = (IO *)r.out + uniform64(row[2]); v.out_frames = uniform64(row[3]);
+    const int64_t *row = rows + 4 * (int64_t)__builtin_amdgcn_readfirstlane(clip);
+    v = g;
+    v.in = (const IO *)g.in + uniform64(row[0]); v.in_frames = uniform64(row[1]);
+    v.out = (IO *)g.out + uniform64(row[2]); v.out_frames = uniform64(row[3]);
     return v;
 }
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const GatherArgsR &r, uint32_t clip, GatherArgs &v) { return clip_view<IO>(r, r.rows, clip, v); }
 
 template <typename IO, typename Real, bool RAGGED = false>
 __global__ void __launch_bounds__(256) k_gather(typename GatherArgsOf<RAGGED>::type a_)
@@ -737,6 +739,10 @@ struct GatherLaunch {
     int64_t done, nf; // outputs [done, done + nf) of the job
     uint64_t cols;    // (clip, channel) columns
     GatherArgs a;
+    // a ragged launch (launch_ragged_interp): the device rows of the launch's j.n_clips clips — nf is then the longest clip's
+    // out_frames, a.ics == a.ocs == 0 (a clip's place is its row's) — and the clip count the log line carries
+    const int64_t *rows = nullptr;
+    int64_t ragged = -1;
     bool whole_job() const { return done == 0 && nf == j.out_frames; }
     // per_wg outputs of one column per workgroup
     dim3 grid(int per_wg) const { return dim3((unsigned)((nf + per_wg - 1) / per_wg), (unsigned)cols, 1); }
@@ -761,6 +767,7 @@ static void gather_launch_log(const char *kernel, const Plan &p, const GatherLau
         vfprintf(fl, form, ap);
         va_end(ap);
     }
+    if (c.ragged >= 0) fprintf(fl, " ragged=%lld", (long long)c.ragged);
     fputc('\n', fl);
     fclose(fl);
 }
@@ -848,6 +855,16 @@ static const char *launch_interp_wave(const Plan &p, const GatherLaunch &c, cons
 {
     InterpWaveArgs wa;
     wa.ia = ia; wa.span_cap = (int32_t)g.span; wa.done_words = nullptr; wa.done_seq = 0;
+    if (c.rows) { // the ragged form: the frame axis is the longest clip's (c.nf), no completion words
+        InterpWaveArgsR wr;
+        (InterpWaveArgs &)wr = wa;
+        wr.rows = c.rows;
+        const dim3 rgrid((unsigned)ragged_span_grid_x(c.nf, 32), (unsigned)c.cols, 1);
+        GATHER_LAUNCH_LOG("interp_wave", p, c, rgrid, 256, g.lds, "span_cap=%d", (int)wa.span_cap);
+        hipLaunchKernelGGL((k_interp_wave<IO, Real, false, true>), rgrid, dim3(256), g.lds, c.st, wr);
+        HIP_TRY(hipGetLastError());
+        return nullptr;
+    }
     const dim3 grid = c.grid(32);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &wa.done_words, &wa.done_seq);
     void (*wk)(InterpWaveArgs) = c.vr ? k_interp_wave<IO, Real, true> : k_interp_wave<IO, Real, false>;
@@ -866,9 +883,12 @@ struct InterpTileForm {
     int64_t split_h = 0, nf_t = 0; // (outputs the tiles are counted over: member 1's)
 };
 // The form for nf outputs per column at `step` input samples per output, against the lane-per-output kernels' cost
-// (wave_ok: k_interp_wave is the alternative, else k_interp).
+// (wave_ok: k_interp_wave is the alternative, else k_interp).  rows: a ragged launch over the j.n_clips clips of that table —
+// nf is the longest clip's (what sizes KO), the two costs are fed the table's real numbers (the workgroups that do work and
+// the outputs, summed over the clips: ragged_span_total, ragged_total_out), not longest x clips; pair modes {0, 1}.
 template <typename Real>
-static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, int64_t nf, double step, bool vr, bool wave_ok)
+static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, int64_t nf, double step, bool vr, bool wave_ok,
+                                       const int64_t *rows = nullptr)
 {
     InterpTileForm f;
     f.nf_t = nf;
@@ -887,7 +907,7 @@ static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, in
     int64_t cand_h = 0, cand_nf = nf;
     if (!switches().no_interp_pair) {
         if (j.n_channels % 2 == 0) cand_mode = 1;
-        else if (!vr) {
+        else if (!vr && !rows) {
             const int64_t h = (nf + 2 * p.L - 1) / (2 * p.L), n1 = h * p.L;
             if (h >= 1 && n1 < nf && 10 * (nf - n1) >= 7 * n1 && h * p.M < ((int64_t)1 << 40)) { cand_mode = 2; cand_h = h; cand_nf = n1; }
         }
@@ -905,7 +925,8 @@ static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, in
                 const int64_t sc = (int64_t)std::ceil((double)k * step) + p.T + 8;
                 const int64_t bytes = (tw ? 2 * (sc + 4) : sc) * nm * (int64_t)sizeof(Real) + k * 2 + (2 * p.phases + 2) * 4 + 64;
                 if (bytes > 150 * 1024) continue;
-                const double wgs_ = std::ceil((double)nft / (double)k) * cols_m;
+                const double wgs_ = rows ? (double)ragged_span_total(rows, j.n_clips, j.n_channels / (mode == 1 ? 2 : 1), k)
+                                         : std::ceil((double)nft / (double)k) * cols_m;
                 const double cost = std::ceil(wgs_ / 256.) * (double)k * (per >= 30 ? 1. : 30. / per) * (tw ? kTwinWg : mode ? kPairWg : 1.); // (thin buckets: idle lanes)
                 if (cost < best_cost) { best_cost = cost; f.KO = k; f.span_cap = sc; f.pair_mode = mode; f.twin = tw != 0; f.split_h = mode == 2 ? cand_h : 0; f.nf_t = nft; cols_ = cols_m; }
             }
@@ -919,9 +940,11 @@ static InterpTileForm interp_tile_form(const Plan &p, const hipsoxr_job_t &j, in
     // the tile kernel (503 on k_interp); 1 s stereo 75 us on k_interp (127 on the tile kernel).
     constexpr double kWaveUsPerTap = 1.0e-6; // k_interp_wave: us per output x tap, 256 CUs
     if (f.KO) {
-        const double wgs = (double)((f.nf_t + f.KO - 1) / f.KO) * cols_;
+        const double wgs = rows ? (double)ragged_span_total(rows, j.n_clips, j.n_channels / (f.pair_mode == 1 ? 2 : 1), f.KO)
+                                : (double)((f.nf_t + f.KO - 1) / f.KO) * cols_;
         const double t_tile = std::ceil(wgs / 256.) * (double)f.KO * p.T * (vr ? 2.9e-4 : 6.3e-5) * (f.twin ? kTwinWg : f.pair_mode ? kPairWg : 1.);
-        const double t_lane = (wave_ok ? kWaveUsPerTap : 2.5e-6) * (double)nf * ((double)j.n_clips * j.n_channels) * p.T;
+        const double outs = rows ? (double)ragged_total_out(rows, j.n_clips) * j.n_channels : (double)nf * ((double)j.n_clips * j.n_channels);
+        const double t_lane = (wave_ok ? kWaveUsPerTap : 2.5e-6) * outs * p.T;
         if (t_lane < t_tile) f.KO = 0;
     }
     return f;
@@ -946,6 +969,21 @@ static const char *launch_interp_tile(const Plan &p, const GatherLaunch &c, cons
                                              : (c.vr ? k_interp_tile<IO, Real, true, false> : k_interp_tile<IO, Real, false, false>);
     if constexpr (sizeof(Real) == 4)
         if (f.twin) tk = c.vr ? k_interp_tile<IO, Real, true, true, true> : k_interp_tile<IO, Real, false, true, true>;
+    if (c.rows) { // the ragged form (pair modes 0 and 1): the frame axis is the longest clip's (f.nf_t == c.nf)
+        InterpTileArgsR tr;
+        (InterpTileArgs &)tr = ta;
+        tr.rows = c.rows;
+        void (*rk)(InterpTileArgsR) = f.pair_mode ? k_interp_tile<IO, Real, false, true, false, true> : k_interp_tile<IO, Real, false, false, false, true>;
+        if constexpr (sizeof(Real) == 4)
+            if (f.twin) rk = k_interp_tile<IO, Real, false, true, true, true>;
+        if (const char *e = ensure_dyn_lds((const void *)rk, lds)) return e;
+        const dim3 rgrid((unsigned)ragged_span_grid_x(f.nf_t, f.KO), tgrid.y, 1);
+        GATHER_LAUNCH_LOG("interp_tile", p, c, rgrid, 1024, lds, "KO=%d pair=%d twin=%d h=%lld nf_t=%lld m2_n=%lld span_cap=%d", (int)ta.KO, f.pair_mode, f.twin ? 1 : 0,
+                          (long long)f.split_h, (long long)f.nf_t, (long long)ta.m2_n, (int)ta.span_cap);
+        hipLaunchKernelGGL(rk, rgrid, dim3(1024), lds, c.st, tr);
+        HIP_TRY(hipGetLastError());
+        return nullptr;
+    }
     if (const char *e = ensure_dyn_lds((const void *)tk, lds)) return e;
     GATHER_LAUNCH_LOG("interp_tile", p, c, tgrid, 1024, lds, "KO=%d pair=%d twin=%d h=%lld nf_t=%lld m2_n=%lld span_cap=%d", (int)ta.KO, f.pair_mode, f.twin ? 1 : 0,
                       (long long)f.split_h, (long long)f.nf_t, (long long)ta.m2_n, (int)ta.span_cap);
@@ -959,6 +997,19 @@ template <typename IO, typename Real>
 static const char *launch_lane(const Plan &p, const GatherLaunch &c, const InterpArgs *ia)
 {
     const dim3 block(256), grid = c.a.ch_fast ? dim3((unsigned)((c.nf * (int64_t)c.j.n_channels + 255) / 256), c.j.n_clips, 1) : c.grid(256);
+    if (c.rows) { // the ragged form of k_interp (k_gather's: launch_ragged_gather)
+        if (!ia || c.vr) return "ragged batches: no such lane kernel";
+        const int64_t gx = ragged_gather_grid_x(c.nf, c.a.ch_fast ? c.j.n_channels : 1);
+        if (gx > kTileMaxGridX) return kTileTooLong;
+        InterpArgsR ir;
+        (InterpArgs &)ir = *ia;
+        ir.rows = c.rows;
+        const dim3 rgrid((unsigned)gx, grid.y, 1);
+        GATHER_LAUNCH_LOG("interp", p, c, rgrid, 256, (size_t)0, "ch_fast=%d", (int)c.a.ch_fast);
+        hipLaunchKernelGGL((k_interp<IO, Real, false, true>), rgrid, block, 0, c.st, ir);
+        HIP_TRY(hipGetLastError());
+        return nullptr;
+    }
     GATHER_LAUNCH_LOG(ia ? "interp" : "gather", p, c, grid, 256, (size_t)0, "ch_fast=%d", (int)c.a.ch_fast);
     if (ia && c.vr) hipLaunchKernelGGL((k_interp<IO, Real, true>), grid, block, 0, c.st, *ia);
     else if (ia) hipLaunchKernelGGL((k_interp<IO, Real, false>), grid, block, 0, c.st, *ia);
@@ -1244,8 +1295,9 @@ static const char *launch_typed(Plan *p, const hipsoxr_job_t &j, hipStream_t st,
 // order — with the plan's own slab geometry: AUTO / EXACT take the MFMA tile family where the plan has one, else k_tile,
 // when the LONGEST clip passes launch_typed's `big` test (short clips ride along), otherwise k_gather; the family
 // selectors force theirs.  Not in ragged form: the small-job forms of launch_tile (halves, z-splits, 16-period float64
-// slabs) and the trace.  *handled stays false for what is still served clip by clip (interpolated-phase plans, the wave-dot
-// kernel, a table with a clip of more than 2^30 outputs: launch_ragged_job).
+// slabs) and the trace.  Interpolated-phase plans: launch_ragged_interp below.  *handled stays false for what is still served
+// clip by clip (float clips of an interpolated-phase plan under AUTO: the two-stage form; the wave-dot kernel; a table with a
+// clip of more than 2^30 outputs: launch_ragged_job).
 // ---------------------------------------------------------------------------------------------
 // k_gather's ragged form: one lane per output of the longest clip
 template <typename IO, typename Real>
@@ -1267,12 +1319,46 @@ static const char *launch_ragged_gather(Plan *p, const hipsoxr_job_t &j, hipStre
     return nullptr;
 }
 
+// Interpolated-phase plans: ONE form for the whole table, in launch_gather's order — k_interp_tile where its cost model, fed
+// the table's real numbers, beats the lane-per-output kernels, else k_interp_wave, else k_interp.  (k_chain has no ragged
+// form: the wave kernel serves even a single output.)  The debug switches act as on launch_gather.
+template <typename IO, typename Real>
+static const char *launch_ragged_interp(Plan *p, const hipsoxr_job_t &j, hipStream_t st)
+{
+    const int64_t longest = ragged_longest(j.clip_table, j.n_clips);
+    if (longest == 0) return nullptr; // nothing to write
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (cols > kMaxGridY) return kTileTooManyCols;
+    hipsoxr_job_t jj = j;
+    jj.in_clip_stride = jj.out_clip_stride = 0; // (a clip's place is its row's)
+    GatherLaunch c{jj, st, nullptr, nullptr, 0, longest, cols, make_gather_args<IO>(*p, bank_of<Real>(p), jj, 0, longest, 0)};
+    c.rows = j.clip_table_dev; c.ragged = j.n_clips;
+    InterpArgs ia;
+    std::memset(&ia, 0, sizeof ia);
+    ia.g = c.a;
+    set_interp_table(ia, *p, bank_of<Real>(p));
+    const double step = (double)p->M / (double)p->L; // input samples per output
+    WaveGeom iw;
+    if (!switches().no_interp_wave && step < 1e6) iw = wave_geom<Real>((int64_t)std::ceil(31. * step), p->T);
+    InterpTileForm tf; // (launch_gather's threshold, here on the table's outputs per channel)
+    if (!switches().no_interp_tile && ragged_tile_considered(j.clip_table, j.n_clips))
+        tf = interp_tile_form<Real>(*p, jj, longest, step, false, iw.ok, j.clip_table);
+    if (tf.KO) return launch_interp_tile<IO, Real>(*p, c, ia, tf);
+    if (iw.ok) return launch_interp_wave<IO, Real>(*p, c, ia, iw);
+    return launch_lane<IO, Real>(*p, c, &ia);
+}
+
 // j: the job of one launch — clip_table the host rows of its n_clips clips, clip_table_dev their device copy
 template <typename IO, typename Real>
 static const char *launch_ragged(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled)
 {
     *handled = false;
-    if (p->phases || j.kernel == HIPSOXR_KERNEL_WAVE_DOT) return nullptr;
+    if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT) return nullptr;
+    if (p->phases) { // the selectors launch_typed admits for such a plan
+        if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && j.kernel != HIPSOXR_KERNEL_GATHER) return kTileUnavailable;
+        *handled = true;
+        return launch_ragged_interp<IO, Real>(p, j, st);
+    }
     const TileGeoms t = tile_geoms(p, sizeof(Real) == 4 ? 0 : 1);
     const int64_t longest = ragged_longest(j.clip_table, j.n_clips);
     const TileGeom &g0 = t.gm.ok ? t.gm : t.gv;
@@ -1325,7 +1411,10 @@ static const char *clip_table_device(const hipsoxr_job_t &j, hipStream_t st, con
 static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled)
 {
     *handled = false;
-    if (p->phases || j.kernel == HIPSOXR_KERNEL_WAVE_DOT || ragged_fold_step(j.n_channels) == 0) return nullptr;
+    if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT || ragged_fold_step(j.n_channels) == 0) return nullptr;
+    // an interpolated-phase plan: float clips under AUTO belong to the two-stage form (another precision class), clip by clip
+    if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage)
+        return nullptr;
     if (ragged_longest(j.clip_table, j.n_clips) > ((int64_t)1 << 30)) return nullptr; // (launch_gather cuts such a clip into several launches)
     if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
     const int64_t *rows = nullptr;
@@ -1501,8 +1590,9 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     if (want_pcm)
         if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
-    // (the kernel reads its clip's row), else one launch of the exact engine's ragged form, else — interpolated-phase plans,
-    // the wave-dot kernel — clip by clip through the ordinary path.  Clips are independent, so the results are the same
+    // (the kernel reads its clip's row), else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
+    // plans alike), else — float clips of an interpolated-phase plan under AUTO, the wave-dot kernel — clip by clip through
+    // the ordinary path.  Clips are independent, so the results are the same
     // either way; bit-exact engines stay bit-exact.
     if (j.clip_table) {
         if (vr || res) return "ragged batches: constant-rate device jobs only";
@@ -1535,8 +1625,8 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         }
         if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (unit-stride float columns of a tabled ratio)";
         if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (unit-stride int16 / int32 columns of a tabled ratio)";
-        // the exact engine: one launch of a kernel's RAGGED form for exact-bank plans (launch_ragged); what that does not
-        // serve — interpolated-phase plans, the wave-dot kernel — clip by clip
+        // the exact engine: one launch of a kernel's RAGGED form (launch_ragged); what that does not serve — float clips of an
+        // interpolated-phase plan under AUTO (the two-stage form's), the wave-dot kernel — clip by clip
         {
             bool handled = false;
             if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;

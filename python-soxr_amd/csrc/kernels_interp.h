@@ -29,24 +29,38 @@ struct InterpArgs {
     uint64_t t_hi, t_lo, s_hi, s_lo, d_hi, d_lo; // VR: T0, S0, D (two's complement), Q64.64
 };
 
-template <typename IO, typename Real, bool VR>
-__global__ void __launch_bounds__(256) k_interp(InterpArgs ia)
+// RAGGED (a clip table on an interpolated-phase plan; constant rate only, so VR has no such form): as k_gather's — the table
+// travels behind the arguments, a column's clip reads its row (in, in_frames, out, out_frames; wave-uniform), the grid is the
+// longest clip's.  Positions are located from the job's own clock (ia: a ragged job starts at output 0 of every clip).
+struct InterpArgsR : InterpArgs {
+    const int64_t *rows; // [n_clips][4], as GatherArgsR::rows
+};
+template <bool RAGGED> struct InterpArgsOf { typedef InterpArgs type; };
+template <> struct InterpArgsOf<true> { typedef InterpArgsR type; };
+// (clip_view, the view of one clip from its row: kernels.hip, beside k_gather's)
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpArgs &x, uint32_t, GatherArgs &) { return x.g; }
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpArgsR &x, uint32_t clip, GatherArgs &v) { return clip_view<IO>(x.g, x.rows, clip, v); }
+
+template <typename IO, typename Real, bool VR, bool RAGGED = false>
+__global__ void __launch_bounds__(256) k_interp(typename InterpArgsOf<RAGGED>::type ia)
 {
+    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     typedef typename Vec4<Real>::type V4;
-    const GatherArgs &a = ia.g;
     int64_t idx;
     uint32_t ch, clip;
-    if (a.ch_fast) {
+    if (ia.g.ch_fast) {
         int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        idx = e / a.n_channels;
-        ch = (uint32_t)(e - idx * a.n_channels);
+        idx = e / ia.g.n_channels;
+        ch = (uint32_t)(e - idx * ia.g.n_channels);
         clip = blockIdx.y;
     } else {
         idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        ch = blockIdx.y % a.n_channels;
-        clip = blockIdx.y / a.n_channels;
+        ch = blockIdx.y % ia.g.n_channels;
+        clip = blockIdx.y / ia.g.n_channels;
     }
-    if (idx >= a.out_frames) return;
+    [[maybe_unused]] GatherArgs row_view;
+    const GatherArgs &a = clip_args<IO>(ia, clip, row_view);
+    if (RAGGED ? ragged_gather_skip(idx, a.out_frames) : idx >= a.out_frames) return;
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
     const int32_t T = a.T, H = T / 2;
     uint64_t iv, xq;
@@ -272,6 +286,16 @@ struct InterpTileArgs {
     int32_t m2_dch;                  // ... its channel = ch + m2_dch (dither / clip-counter context)
 };
 
+// RAGGED: one output per lane and channel pairs (both members of a lane lie in the same clip); the halves form splits a
+// column at a point computed from its own length and has none.  A workgroup at or behind its clip's end returns first.
+struct InterpTileArgsR : InterpTileArgs {
+    const int64_t *rows;
+};
+template <bool RAGGED> struct InterpTileArgsOf { typedef InterpTileArgs type; };
+template <> struct InterpTileArgsOf<true> { typedef InterpTileArgsR type; };
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpTileArgs &x, uint32_t, GatherArgs &) { return x.ia.g; }
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpTileArgsR &x, uint32_t clip, GatherArgs &v) { return clip_view<IO>(x.ia.g, x.rows, clip, v); }
+
 template <typename Real> struct InterpPos { int64_t n0; uint32_t iv; uint64_t xq; };
 
 template <typename Real, bool VR>
@@ -364,24 +388,37 @@ struct InterpWaveArgs {
     uint32_t *done_words; // (optional, pinned host memory) completion words, as ChainArgs::done_words
     uint32_t done_seq;
 };
+// RAGGED: a workgroup's 32 outputs are its column's clip's; a workgroup at or behind that clip's end (every workgroup of an
+// empty clip) returns before anything is located or published.  No completion words.
+struct InterpWaveArgsR : InterpWaveArgs {
+    const int64_t *rows;
+};
+template <bool RAGGED> struct InterpWaveArgsOf { typedef InterpWaveArgs type; };
+template <> struct InterpWaveArgsOf<true> { typedef InterpWaveArgsR type; };
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpWaveArgs &x, uint32_t, GatherArgs &) { return x.ia.g; }
+template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpWaveArgsR &x, uint32_t clip, GatherArgs &v) { return clip_view<IO>(x.ia.g, x.rows, clip, v); }
 
-template <typename IO, typename Real, bool VR>
-__global__ void __launch_bounds__(256) k_interp_wave(InterpWaveArgs wa)
+template <typename IO, typename Real, bool VR, bool RAGGED = false>
+__global__ void __launch_bounds__(256) k_interp_wave(typename InterpWaveArgsOf<RAGGED>::type wa)
 {
+    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     typedef typename Vec4<Real>::type V4;
     constexpr int U = 8; // steps (of four taps) requested ahead
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     __shared__ int64_t s_loc[4]; // first / last window start of the two output groups
     const InterpArgs &ia = wa.ia;
-    const GatherArgs &a = ia.g;
     const int lane = threadIdx.x & 63, k = lane & 3, quad = lane >> 2;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), half = wave & 1, grp = wave >> 1;
     Real *xs = reinterpret_cast<Real *>(smem_raw);
     Real *accx = xs + wa.span_cap; // [32] the second half-chains' sums
-    const int32_t T = a.T, H = T / 2, NS = H / 4; // T is a multiple of 8
+    const int32_t T = ia.g.T, H = T / 2, NS = H / 4; // T is a multiple of 8
     const uint32_t col = blockIdx.y;
-    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % a.n_channels), clip = __builtin_amdgcn_readfirstlane(col / a.n_channels);
+    const uint32_t ch = __builtin_amdgcn_readfirstlane(col % ia.g.n_channels), clip = __builtin_amdgcn_readfirstlane(col / ia.g.n_channels);
+    [[maybe_unused]] GatherArgs row_view;
+    const GatherArgs &a = clip_args<IO>(wa, clip, row_view);
+    if constexpr (RAGGED)
+        if (ragged_span_skip(blockIdx.x, 32, a.out_frames)) return; // (workgroup-uniform, before the first barrier; out_frames - 1 below is >= 0)
     const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
 
     const int64_t o = (int64_t)blockIdx.x * 32 + grp * 16 + quad;
@@ -463,7 +500,7 @@ __global__ void __launch_bounds__(256) k_interp_wave(InterpWaveArgs wa)
         IO *yo = (IO *)a.out + (int64_t)clip * a.ocs + o * a.ofs + (int64_t)ch * a.ochs;
         store_out<Real>(yo, acc + accx[grp * 16 + quad], a.oc, ch, a.out_k0 + o);
     }
-    if (wa.done_words) {
+    if (!RAGGED && wa.done_words) {
         __threadfence_system();
         __syncthreads();
         if (threadIdx.x == 0)
@@ -471,16 +508,16 @@ __global__ void __launch_bounds__(256) k_interp_wave(InterpWaveArgs wa)
     }
 }
 
-template <typename IO, typename Real, bool VR, bool PAIR, bool TWIN = false>
-__global__ void __launch_bounds__(1024) k_interp_tile(InterpTileArgs ta)
+template <typename IO, typename Real, bool VR, bool PAIR, bool TWIN = false, bool RAGGED = false>
+__global__ void __launch_bounds__(1024) k_interp_tile(typename InterpTileArgsOf<RAGGED>::type ta)
 {
     static_assert(!TWIN || (PAIR && sizeof(Real) == 4), "TWIN: float pairs only");
+    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     constexpr int NM = PAIR ? 2 : 1; // members per lane; the staged span is [sample][member]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const InterpArgs &ia = ta.ia;
-    const GatherArgs &a = ia.g;
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
-    const int32_t KO = ta.KO, P = ia.P, T = a.T, H = T / 2;
+    const int32_t KO = ta.KO, P = ia.P, T = ia.g.T, H = T / 2;
     // (round 3: no per-output record in LDS any more — 8 of the 10 bytes of bookkeeping per output; an output's position
     //  is located again where it is needed, ~50 vector-ALU instructions against the ~1500 of its taps.  LDS then holds
     //  twice the outputs per workgroup, a bucket — the outputs of one phase interval, served 64 at a time — 60 instead
@@ -504,7 +541,11 @@ __global__ void __launch_bounds__(1024) k_interp_tile(InterpTileArgs ta)
     // run-time division goes through the vector ALU; readfirstlane keeps the results (and every
     // address derived from them) on the scalar side
     const uint32_t ch = __builtin_amdgcn_readfirstlane((col % ta.cols_per_clip) * ta.ch_step), clip = __builtin_amdgcn_readfirstlane(col / ta.cols_per_clip);
+    [[maybe_unused]] GatherArgs row_view;
+    const GatherArgs &a = clip_args<IO>(ta, clip, row_view);
     const int64_t o_base = (int64_t)blockIdx.x * KO;
+    if constexpr (RAGGED)
+        if (ragged_span_skip(blockIdx.x, KO, a.out_frames)) return; // (workgroup-uniform, before the first barrier: n_here >= 1 below)
     const int32_t n_here = (int32_t)((a.out_frames - o_base) < KO ? (a.out_frames - o_base) : KO);
     const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
     IO *yo = (IO *)a.out + (int64_t)clip * a.ocs + (int64_t)ch * a.ochs;

@@ -123,8 +123,11 @@ class RaggedJob:
     everything else — int16 / int32 under the default selector, interleaved stereo / multichannel and float64 clips, small
     jobs, KERNEL_EXACT, the tile and gather selectors — runs the exact engine's ragged kernels (the kernel reads its clip's row of
     the table; the grid is the longest clip's; more than 65535 clip x channel columns: one launch per range of clips).
-    Each clip has the bits of the clip run alone.  Interpolated-phase plans (`plan.phases != 0`) and KERNEL_WAVE_DOT are
-    served clip by clip inside the same call.
+    Each clip has the bits of the clip run alone.  Interpolated-phase plans (`plan.phases != 0`, the arbitrary ratios) are
+    ONE launch as well — int16 / int32 under the default selector, every type under KERNEL_EXACT / KERNEL_GATHER — on the
+    ragged form of k_interp_tile, k_interp_wave or k_interp, chosen from the table; float clips of such a plan under
+    KERNEL_AUTO (the two-stage form, another precision class) and KERNEL_WAVE_DOT are served clip by clip inside the same
+    call.
 
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
@@ -313,12 +316,12 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
 def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AUTO):
     """Resample a batch of clips of unequal length on one device as one job; returns the list of per-clip outputs (views
     of one packed buffer).  Without `requires_grad` on any clip, or under `no_grad`, this is exactly
-    `RaggedJob(plan, clips, kernel).launch()` and its `outputs()` — one launch on an exact-bank plan, kernel=KERNEL_EXACT
-    included (see `RaggedJob`).
+    `RaggedJob(plan, clips, kernel).launch()` and its `outputs()` — one launch on an exact-bank plan and, with
+    kernel=KERNEL_EXACT, on an interpolated-phase plan too (see `RaggedJob`).
 
     Differentiable otherwise: the result carries a grad_fn whose backward is ONE ragged launch of the transposed operator
     (`resample_ragged_adjoint` with `grad_kernel`), whatever the number of clips; gradients of gradients flow too (the double
-    backward is the ragged forward with KERNEL_EXACT: one launch as well).  A clip
+    backward is the ragged forward with KERNEL_EXACT: one launch as well, on interpolated-phase plans too).  A clip
     that does not require grad gets none.  As for `device.resample_tensor`, the gradient is the EXACT engine's adjoint
     (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
     interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called."""
