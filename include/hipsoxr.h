@@ -226,15 +226,28 @@ typedef struct {
      * between packed clips either; clip_counter receives the sum over the clips.  An interpolated-phase plan (an
      * arbitrary ratio) is ONE launch in the same way — int16 / int32 under the default selector, every type under
      * HIPSOXR_KERNEL_EXACT / HIPSOXR_KERNEL_GATHER — on the ragged forms of its own kernels, each clip with the bits of
-     * the clip run alone.  Served clip by clip from the same call, same results: float clips of such a plan under
-     * HIPSOXR_KERNEL_AUTO (the two-stage form, another precision class), HIPSOXR_KERNEL_WAVE_DOT, and a table with a
-     * clip of more than 2^30 outputs. */
+     * the clip run alone.  float32 / float64 clips of such a plan under HIPSOXR_KERNEL_AUTO belong to the two-stage
+     * form (another precision class), and a table with in_frame_stride == out_frame_stride == 1 (mono clips, planar
+     * channels at any channel stride) is a CONSTANT number of launches whatever the number of clips: the table is
+     * partitioned by the question asked of each clip alone — a clip of 8192 frames or more on both sides that the form
+     * admits runs the two-stage form, every other non-empty clip the exact engine, so engine choice per clip does not
+     * depend on the table — into one ragged polyphase launch and one ragged FFT-stage launch over the (clip, channel)
+     * columns of the admitted clips, and one ragged launch of the interpolated kernels over the others.  Only two cuts
+     * multiply that: more than 65535 admitted columns, or more than 1 GiB of intermediate signal (each range of columns
+     * is one stream-ordered allocation, one launch pair and one free).  Precision: admitted clips are within the two-stage
+     * class of the float64 direct form (1e-6 float32, 2e-9 float64, relative RMS), NOT bit-equal to the clip run alone (a
+     * mono float32 clip alone takes another kernel form of the polyphase stage: other rounding, same class); the short
+     * clips ARE bit-equal to the clip alone.  The inner launches read tables the library derives (columns, offsets into the
+     * intermediate; one upload per call), so clip_table_dev cannot serve this path and is not read by it.
+     * Served clip by clip from the same call, same results: such float clips with interleaved channels (frame strides
+     * other than 1: the ragged FFT kernels have no strided form), HIPSOXR_KERNEL_WAVE_DOT, and a table with a clip of more
+     * than 2^30 outputs.  HIPSOXR_KERNEL_FFT / _FFT_F64 on a table of an interpolated-phase plan stay refused. */
     const int64_t *clip_table;
     const int64_t *clip_table_dev;
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */

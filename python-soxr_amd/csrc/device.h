@@ -119,6 +119,7 @@ struct Switches {
     size_t dbg_mfma64_lds = 0;    // HIPSOXR_DEBUG_MFMA64_LDS LDS budget (bytes) that picks the float64 MFMA kernel's slab: 64, 32 or 16 periods
     size_t dbg_fft_lds = 0;       // HIPSOXR_DEBUG_FFT_LDS    the same for the frequency-domain kernels
     int dbg_poly_r = 0;           // HIPSOXR_DEBUG_POLY_R     k_poly: force the outputs per thread and tile
+    int dbg_poly_mid_budget = 0;  // HIPSOXR_DEBUG_POLY_MID_BUDGET  a clip table on the two-stage form: bytes of intermediate per range of columns (default kPolyMidBudget, 1 GiB) — forces the range cut on small tables (tests; same bits)
     bool no_interp_pair = false;  // HIPSOXR_NO_INTERP_PAIR   k_interp_tile: one output per lane (A/B)
     bool dbg_interp_no_twin = false;     // HIPSOXR_DEBUG_INTERP_NO_TWIN      ... float pairs on ONE copy of the staged span (8-byte reads) always (A/B, tests)
     bool dbg_interp_pair_always = false; // HIPSOXR_DEBUG_INTERP_PAIR_ALWAYS  ... two per lane wherever a pair exists, whatever the cost model says (tests)
@@ -126,7 +127,7 @@ struct Switches {
     bool poly_no_pair = false;    // HIPSOXR_POLY_NO_PAIR     interleaved channel pairs on k_poly (one channel per pass) instead of k_poly2 (A/B)
     int dbg_tile_form = 0;        // HIPSOXR_DEBUG_TILE_FORM  k_tile_mfma_p: force launch form 1..4 (slab 64 whole / 64 split / 32 whole / 32 split)
     const char *dbg_trace = nullptr; // HIPSOXR_DEBUG_TRACE   path for per-wave s_memtime stamps (k_tile_mfma_p; k_fft_pair2 with -DFFT2_TRACE)
-    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape (written by the launcher of the form that took the job, or "none" by the dispatcher); adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape (a ragged launch appends ragged=<n_clips>); launch_tile and launch_ragged (kernels.hip, tile_launch_log) one line per tile launch of the exact engine — kernel tile | tile_mfma | tile_mfma_p | tile_mfma64_p (a ragged launch also: gather), element width, io type, L M Lc Mc, pb, n_rt, nw (waves that compute), split (workgroups per slab), halves, xz, LDS bytes, launch shape; a ragged launch appends ragged=<n_clips> (equal-length launches of launch_gather's family: below); adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape; launch_poly (twostage.hip) one line per polyphase launch of the two-stage form — kernel poly | poly2, element width, taps, MQ, il (channel pairs), split, R, lane multiplier and its conflict cost, LDS bytes, channel group, columns, tiles, launch shape, outputs of member 1 and member 2; launch_gather (kernels.hip) one line per launch — kernel gather_wave | chain | chain_resident | interp_wave | interp_tile | interp | gather, element width, io type, vr, L M T P, done nf cols, k0 in_abs0 (the launch's first output and the absolute index of input frame 0), launch shape, LDS bytes, then the form's own fields (chain: NO span_cap mode; wave forms: span_cap; tile: KO pair twin h nf_t m2_n span_cap; lane per output: ch_fast)
+    const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape (written by the launcher of the form that took the job, or "none" by the dispatcher); adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape (a ragged launch appends ragged=<n_clips>); launch_tile and launch_ragged (kernels.hip, tile_launch_log) one line per tile launch of the exact engine — kernel tile | tile_mfma | tile_mfma_p | tile_mfma64_p (a ragged launch also: gather), element width, io type, L M Lc Mc, pb, n_rt, nw (waves that compute), split (workgroups per slab), halves, xz, LDS bytes, launch shape; a ragged launch appends ragged=<n_clips> (equal-length launches of launch_gather's family: below); adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape; launch_poly (twostage.hip) one line per polyphase launch of the two-stage form — kernel poly | poly2, element width, taps, MQ, il (channel pairs), split, R, lane multiplier and its conflict cost, LDS bytes, channel group, columns, tiles, launch shape, outputs of member 1 and member 2 (a launch over a clip table's columns appends ragged=<columns>, tiles and n_out then being the longest column's — as does the FFT line of a launch over a table); launch_gather (kernels.hip) one line per launch — kernel gather_wave | chain | chain_resident | interp_wave | interp_tile | interp | gather, element width, io type, vr, L M T P, done nf cols, k0 in_abs0 (the launch's first output and the absolute index of input frame 0), launch shape, LDS bytes, then the form's own fields (chain: NO span_cap mode; wave forms: span_cap; tile: KO pair twin h nf_t m2_n span_cap; lane per output: ch_fast)
 };
 const Switches &switches();
 
@@ -178,6 +179,14 @@ const char *launch_fft_window(Plan *p, const hipsoxr_job_t &job, void *stream, b
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+// ... on a clip table (job.clip_table, validated by launch_job; float32 / float64, HIPSOXR_KERNEL_AUTO, unit frame strides):
+// a constant number of launches — per range of columns one ragged polyphase launch and one ragged FFT-stage launch, plus
+// one launch_ragged_short for the clips the two-stage form does not admit.  *handled = false: not a table this path serves,
+// or the FFT stage declined — the caller's clip-by-clip loop computes every clip.
+const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+// (kernels.hip) the short clips of such a table — job.clip_table / clip_table_dev: the compacted sub-table — in one ragged
+// launch of the exact engine's interpolated kernels, the engine and the bits of each clip alone; *handled as launch_ragged_job's
+const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
 // transposed operator of the exact engine (adjoint.hip; hipsoxr_run_device_adjoint): job.in = gy (in_frames of it), job.out = gx
 // (out_frames of it); validates the job itself.  HIPSOXR_KERNEL_ADJOINT: interpolated-phase plans too (k_adj_interp on the
 // forward's own table, device_bank_ensure).  adjoint_release drops the plan's transposed tables (rebuilt on next use).

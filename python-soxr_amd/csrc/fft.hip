@@ -1319,14 +1319,17 @@ const char *fft_stream_refusal(const Plan &p, int elem, uint32_t ch, int32_t *le
 // was launched for the job (tests/test_gpu_fft_table.py asserts it).  form: pair2 / strided2_cp / strided2_st (a row of
 // fft_pairs: L M k small are the row's), wave (k_fft_wave: its own k; grid = block pairs x columns, the work items of its
 // persistent waves), block (k_fft_block: the geometry's k), none (nothing launched, *handled == false; the row chosen so
-// far, if any).  small = -1: not a row of the table.
+// far, if any).  small = -1: not a row of the table.  A launch over a clip table appends ragged=<columns>; lines of
+// equal-length jobs are as they were.
 static void fft_launch_log(const char *form, int64_t L, int64_t M, int k, int small, const char *kind, unsigned nt, size_t lds,
-                           dim3 grid, int64_t hop_out, int64_t n_blocks, bool window)
+                           dim3 grid, int64_t hop_out, int64_t n_blocks, bool window, uint64_t ragged = 0)
 {
     FILE *f = fopen(switches().dbg_launch_log, "a");
     if (!f) return;
-    fprintf(f, "form=%s L=%lld M=%lld k=%d small=%d kind=%s nt=%u lds=%zu grid=%ux%ux%u hop_out=%lld n_blocks=%lld window=%d\n", form,
+    fprintf(f, "form=%s L=%lld M=%lld k=%d small=%d kind=%s nt=%u lds=%zu grid=%ux%ux%u hop_out=%lld n_blocks=%lld window=%d", form,
             (long long)L, (long long)M, k, small, kind, nt, lds, grid.x, grid.y, grid.z, (long long)hop_out, (long long)n_blocks, window ? 1 : 0);
+    if (ragged) fprintf(f, " ragged=%llu", (unsigned long long)ragged); // (a clip table: its columns; n_blocks: the longest column's)
+    fprintf(f, "\n");
     fclose(f);
 }
 
@@ -1605,7 +1608,7 @@ static const char *fft_try_wave(Plan *p, const hipsoxr_job_t &j, const FftJobVie
     fft_args_geom(a, gw);
     if (const char *e = fft_wave_launch(wk, a, (unsigned)pairs_w, (unsigned)v.cols, stream)) return e;
     if (switches().dbg_launch_log)
-        fft_launch_log("wave", p->L, p->M, wk.k, -1, v.kind, 64, 0, dim3((unsigned)pairs_w, (unsigned)v.cols, 1), gw.hop_out, 2 * pairs_w, v.window);
+        fft_launch_log("wave", p->L, p->M, wk.k, -1, v.kind, 64, 0, dim3((unsigned)pairs_w, (unsigned)v.cols, 1), gw.hop_out, 2 * pairs_w, v.window, a.clip_tab ? v.cols : 0);
     *handled = true;
     return nullptr;
 }
@@ -1622,7 +1625,7 @@ static const char *fft_launch_paired(const PairEntry &e, const FftGeom &g, const
     hipLaunchKernelGGL(kern, lay.grid, dim3(e.nt), lay.lds, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     if (switches().dbg_launch_log)
-        fft_launch_log(lay.v2ok ? "pair2" : lay.cp2ok ? "strided2_cp" : "strided2_st", e.L, e.M, e.k, e.small, v.kind, e.nt, lay.lds, lay.grid, g.hop_out, lay.n_blocks, v.window);
+        fft_launch_log(lay.v2ok ? "pair2" : lay.cp2ok ? "strided2_cp" : "strided2_st", e.L, e.M, e.k, e.small, v.kind, e.nt, lay.lds, lay.grid, g.hop_out, lay.n_blocks, v.window, a.clip_tab ? v.cols : 0);
     if (const char *err = fft_trace_dump(a, trace_n, stream)) return err;
     *handled = true;
     return nullptr;

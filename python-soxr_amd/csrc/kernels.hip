@@ -89,7 +89,7 @@ const Switches &switches()
         w.dbg_slab32 = on("HIPSOXR_DEBUG_SLAB32"); w.no_halves = on("HIPSOXR_DEBUG_NO_HALVES"); w.dbg_pad = on("HIPSOXR_DEBUG_PAD");
         w.dbg_slab64 = on("HIPSOXR_DEBUG_SLAB64"); w.dbg_mfma64_pb = num("HIPSOXR_DEBUG_MFMA64_PB"); w.dbg_mfma64_split = on("HIPSOXR_DEBUG_MFMA64_SPLIT");
         w.dbg_mfma64_lds = (size_t)num("HIPSOXR_DEBUG_MFMA64_LDS"); w.dbg_fft_lds = (size_t)num("HIPSOXR_DEBUG_FFT_LDS");
-        w.dbg_tile_form = num("HIPSOXR_DEBUG_TILE_FORM"); w.dbg_poly_r = num("HIPSOXR_DEBUG_POLY_R"); w.no_interp_pair = on("HIPSOXR_NO_INTERP_PAIR"); w.dbg_interp_pair_always = on("HIPSOXR_DEBUG_INTERP_PAIR_ALWAYS"); w.dbg_interp_no_twin = on("HIPSOXR_DEBUG_INTERP_NO_TWIN"); w.poly_no_pair = on("HIPSOXR_POLY_NO_PAIR"); w.adj_interp_per_lane = on("HIPSOXR_DEBUG_ADJ_INTERP_PER_LANE"); w.dbg_trace = getenv("HIPSOXR_DEBUG_TRACE"); w.dbg_launch_log = getenv("HIPSOXR_DEBUG_LAUNCH_LOG");
+        w.dbg_tile_form = num("HIPSOXR_DEBUG_TILE_FORM"); w.dbg_poly_r = num("HIPSOXR_DEBUG_POLY_R"); w.dbg_poly_mid_budget = num("HIPSOXR_DEBUG_POLY_MID_BUDGET"); w.no_interp_pair = on("HIPSOXR_NO_INTERP_PAIR"); w.dbg_interp_pair_always = on("HIPSOXR_DEBUG_INTERP_PAIR_ALWAYS"); w.dbg_interp_no_twin = on("HIPSOXR_DEBUG_INTERP_NO_TWIN"); w.poly_no_pair = on("HIPSOXR_POLY_NO_PAIR"); w.adj_interp_per_lane = on("HIPSOXR_DEBUG_ADJ_INTERP_PER_LANE"); w.dbg_trace = getenv("HIPSOXR_DEBUG_TRACE"); w.dbg_launch_log = getenv("HIPSOXR_DEBUG_LAUNCH_LOG");
 #endif
         return w;
     }();
@@ -1295,9 +1295,10 @@ static const char *launch_typed(Plan *p, const hipsoxr_job_t &j, hipStream_t st,
 // order — with the plan's own slab geometry: AUTO / EXACT take the MFMA tile family where the plan has one, else k_tile,
 // when the LONGEST clip passes launch_typed's `big` test (short clips ride along), otherwise k_gather; the family
 // selectors force theirs.  Not in ragged form: the small-job forms of launch_tile (halves, z-splits, 16-period float64
-// slabs) and the trace.  Interpolated-phase plans: launch_ragged_interp below.  *handled stays false for what is still served
-// clip by clip (float clips of an interpolated-phase plan under AUTO: the two-stage form; the wave-dot kernel; a table with a
-// clip of more than 2^30 outputs: launch_ragged_job).
+// slabs) and the trace.  Interpolated-phase plans: launch_ragged_interp below.  *handled stays false for what is not this
+// path's (float clips of an interpolated-phase plan under AUTO: the two-stage form's — twostage.hip launch_two_stage_ragged,
+// which hands its short clips back through launch_ragged_short — or, interleaved, the clip-by-clip loop's; the wave-dot
+// kernel; a table with a clip of more than 2^30 outputs: launch_ragged_job).
 // ---------------------------------------------------------------------------------------------
 // k_gather's ragged form: one lane per output of the longest clip
 template <typename IO, typename Real>
@@ -1408,12 +1409,14 @@ static const char *clip_table_device(const hipsoxr_job_t &j, hipStream_t st, con
 
 // The ragged exact launch of a whole table: one launch, or — more columns than gridDim.y holds — one per range of clips
 // (a sub-range of the table is a pointer offset, in the host table and in its device copy).
-static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled)
+static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_t st, bool *handled, bool two_stage_short = false)
 {
     *handled = false;
     if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT || ragged_fold_step(j.n_channels) == 0) return nullptr;
-    // an interpolated-phase plan: float clips under AUTO belong to the two-stage form (another precision class), clip by clip
-    if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage)
+    // an interpolated-phase plan: float clips under AUTO belong to the two-stage form (another precision class) — all but
+    // the sub-table of clips that form does not admit (two_stage_short: launch_two_stage_ragged's), which are the exact engine's
+    if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage &&
+        !two_stage_short)
         return nullptr;
     if (ragged_longest(j.clip_table, j.n_clips) > ((int64_t)1 << 30)) return nullptr; // (launch_gather cuts such a clip into several launches)
     if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
@@ -1444,6 +1447,10 @@ static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_
     if (err) return err;
     *handled = all;
     return nullptr;
+}
+const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+{
+    return launch_ragged_job(p, j, (hipStream_t)stream, handled, true);
 }
 
 bool resident_post(const Plan &p, volatile uint64_t *w, uint32_t seq, int64_t in_abs0, int64_t in_frames, int64_t out_k0, int64_t out_frames,
@@ -1590,10 +1597,10 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     if (want_pcm)
         if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
-    // (the kernel reads its clip's row), else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
-    // plans alike), else — float clips of an interpolated-phase plan under AUTO, the wave-dot kernel — clip by clip through
-    // the ordinary path.  Clips are independent, so the results are the same
-    // either way; bit-exact engines stay bit-exact.
+    // (the kernel reads its clip's row), else — float clips of an interpolated-phase plan under AUTO with unit frame strides —
+    // the two-stage form over the table, else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
+    // plans alike), else — such float clips with interleaved channels, the wave-dot kernel — clip by clip through the
+    // ordinary path.  Clips are independent and each keeps the engine it has alone: bit-exact engines stay bit-exact.
     if (j.clip_table) {
         if (vr || res) return "ragged batches: constant-rate device jobs only";
         if (j.in_abs0 != 0 || j.out_k0 != 0) return "ragged batches: whole signals only (in_abs0 == 0, out_k0 == 0)";
@@ -1625,8 +1632,18 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         }
         if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (unit-stride float columns of a tabled ratio)";
         if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (unit-stride int16 / int32 columns of a tabled ratio)";
+        // float clips of an interpolated-phase plan under AUTO with unit frame strides: the two-stage form over the table —
+        // one ragged polyphase launch and one ragged FFT-stage launch per range of columns, one ragged launch of the exact
+        // engine for the clips too short for the form (twostage.hip launch_two_stage_ragged; engine choice per clip is the
+        // clip's alone)
+        if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage) {
+            bool handled = false;
+            if (const char *e = launch_two_stage_ragged(p, j, stream, &handled)) return e;
+            if (handled) return nullptr;
+        }
         // the exact engine: one launch of a kernel's RAGGED form (launch_ragged); what that does not serve — float clips of an
-        // interpolated-phase plan under AUTO (the two-stage form's), the wave-dot kernel — clip by clip
+        // interpolated-phase plan under AUTO on other layouts (interleaved channels: the two-stage form's, clip by clip), the
+        // wave-dot kernel — clip by clip
         {
             bool handled = false;
             if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;

@@ -1,8 +1,10 @@
 // poly_rules.h — the rules of the two-stage form's polyphase launch (twostage.hip: launch_poly, launch_two_stage) that read
 // nothing but numbers: which kernel form a job takes, how large a tile is in LDS, how long a thread's run may be, which
 // lane order reads the table with the fewest bank conflicts, how many workgroups a column gets, which jobs the form admits
-// and how its intermediate signal is laid out.  Each thing once.  No HIP, no globals
-// (tests/c/poly_rules_check.cpp checks them against slow independent statements).
+// and how its intermediate signal is laid out; and, for a clip table (launch_two_stage_ragged), how the clips are
+// partitioned, where each column's intermediate lies, what rows both stages read and how the columns are cut into ranges.
+// Each thing once.  No HIP, no globals (tests/c/poly_rules_check.cpp and tests/c/ragged_poly_rules_check.cpp check them
+// against slow independent statements).
 //
 // What k_poly / k_poly2 rely on and these rules provide (the check program holds each):
 //   * span_max covers every tile's source span nB - nA + 1 (xs[] in LDS ends where ys[] begins);
@@ -14,6 +16,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace hipsoxr {
 
@@ -229,5 +232,119 @@ inline TwoStageMid two_stage_mid(bool up, int32_t T2, int64_t Ls, int64_t Ms, in
     m.mstr[0] = m.n_mid * (int64_t)n_channels; m.mstr[1] = inter ? (int64_t)n_channels : 1; m.mstr[2] = inter ? 1 : m.n_mid;
     return m;
 }
+
+// The outputs the intermediate is SIZED for.  Down, the FFT stage's filter (fft_T taps at the intermediate's rate) reads
+// fft_T / 2 samples of the intermediate past output k's position 2 k: a job truncated below the plan's output length
+// (n_out < the out_len of its n input frames) needs the intermediate that far past 2 n_out, where the signal goes on — sized
+// by n_out alone, the intermediate ended pad samples behind 2 n_out and the last ~fft_T / 4 outputs were the response to a
+// signal cut short (2e-5 relative RMS on the last 3000 outputs of a clip truncated by 7).  A whole job (n_out = out_len) gets
+// n_out back: nothing moves for it.  Up, the intermediate follows the input: n_out as it is.
+// (Ms / Ls = M / (2 L) down, so the plan's out_len(n) = floor(n L / M + 1/2) = floor((n Ls + Ms) / (2 Ms)).)
+inline int64_t two_stage_mid_outputs(bool up, int64_t Ls, int64_t Ms, int64_t n, int64_t n_out, int32_t fft_T)
+{
+    if (up) return n_out;
+    const int64_t full = (n * Ls + Ms) / (2 * Ms);
+    return std::max(n_out, std::min(full, n_out + (fft_T + 3) / 4));
+}
+
+// ---- a clip table on the two-stage form (twostage.hip launch_two_stage_ragged) ------------------------------------------
+// A float clip table of an interpolated-phase plan with unit frame strides: a constant number of launches whatever the
+// number of clips.  The table's rows are {in offset, in frames, out offset, out frames} (elements from in / out).
+//   * partition: a clip is EMPTY (out frames == 0: nothing is launched for it), TWO-STAGE (two_stage_admits says yes for its
+//     own frame counts with its own channels as the column count — the question launch_two_stage asks of the clip alone, so
+//     the engine of a clip does not depend on the table around it) or SHORT (every other clip: ONE ragged launch of the exact
+//     engine's interpolated kernels over the compacted sub-table short_rows — the engine, and the bits, of the clip alone);
+//   * columns, not clips, are the rows of the inner launches: both stages run with one channel and one table row per
+//     (clip, channel) column of a two-stage clip, clip-major, at the caller's row offset + ch * channel stride;
+//   * the intermediate of a column is its own: two_stage_mid of the clip alone (pad, n_core, n_mid — one channel, planar;
+//     sized, as for the clip alone, for two_stage_mid_outputs of its frame counts),
+//     packed [column][n_mid rounded up to 8 elements: the 16-byte phases of the columns are kept];
+//   * ranges: the columns are cut into runs of at most kPolyMaxCols columns and at most `budget` bytes of intermediate (a
+//     single column above the budget is a range of its own) — one allocation, one launch pair and one free per range, where
+//     the clip-by-clip loop held one clip's intermediate at a time (1024 clips of 1-10 s mono: about 2 GB in one piece);
+//   * the rows of both stages, in the kernels' own coordinates:
+//       poly row {src offset of sample 0, n_src, dst offset of output k_lo, n_out}      (k_poly<.., RAGGED>; n_lo, k_lo job-wide)
+//         down: {caller's input column, n,         mid column,              n_mid}      n_lo = 0,    k_lo = -pad
+//         up:   {mid column + pad,      n_core + pad, caller's output column, n_out}    n_lo = -pad, k_lo = 0
+//       FFT row {offset of the first stored sample, END of the column as an absolute sample index, out offset, out frames}
+//         — k_fft_pair2 compares absolute indices against FftArgs::in_lo (= the job's in_abs0) and the row's second word —
+//         down: {mid column,            n_core + pad, caller's output column, n_out}    in_abs0 = -pad
+//         up:   {caller's input column, pad / 2 + n,  mid column,             n_mid}    in_abs0 = pad / 2
+constexpr int64_t kPolyMidBudget = (int64_t)1 << 30; // bytes of intermediate per range: a design choice, not a measurement
+enum RaggedPolyClass { kRaggedPolyEmpty = 0, kRaggedPolyTwo = 1, kRaggedPolyShort = 2 };
+inline RaggedPolyClass ragged_poly_class(int64_t n, int64_t n_out, uint32_t n_channels, size_t width, const PolyStage &s)
+{
+    if (n_out <= 0) return kRaggedPolyEmpty;
+    return two_stage_admits(n, n_out, n_channels, width, s) ? kRaggedPolyTwo : kRaggedPolyShort;
+}
+inline int64_t ragged_poly_col_elems(int64_t n_mid) { return (n_mid + 7) / 8 * 8; }
+
+struct RaggedPolyRange {
+    uint32_t first, count;                   // columns [first, first + count) of the two-stage columns
+    int64_t mid_elems;                       // elements of the range's intermediate
+    int64_t poly_longest;                    // the longest n_out of its poly rows: what R and the grid's frame axis are sized by
+    int64_t fft_in_longest, fft_out_longest; // the FFT stage's job-wide frame counts (the longest column's)
+};
+struct RaggedPolyPlan {
+    int64_t pad = 0;                           // the plan's, the same for every clip
+    std::vector<uint8_t> cls;                  // [clips]
+    std::vector<int64_t> short_rows;           // [short clips][4]: the caller's rows, compacted, table order
+    std::vector<uint32_t> col_clip, col_ch;    // [columns]: clip-major, channels inside
+    std::vector<TwoStageMid> col_mid;          // [columns]: two_stage_mid of the clip alone
+    std::vector<int64_t> col_off;              // [columns]: element offset of the column in ITS RANGE's intermediate
+    std::vector<int64_t> poly_rows, fft_rows;  // [columns][4]
+    std::vector<RaggedPolyRange> ranges;
+    uint32_t n_short() const { return (uint32_t)(short_rows.size() / 4); }
+    uint32_t n_cols() const { return (uint32_t)col_clip.size(); }
+};
+// rows: the caller's table; in_chs / out_chs: its channel strides (frame strides are 1); fft_T: the FFT stage's taps; budget:
+// kPolyMidBudget (the debug-switch build may lower it)
+inline RaggedPolyPlan ragged_poly_plan(const int64_t *rows, uint32_t n_clips, uint32_t n_channels, int64_t in_chs, int64_t out_chs, size_t width, bool up,
+                                       const PolyStage &s, int32_t fft_T, int64_t budget)
+{
+    RaggedPolyPlan r;
+    r.pad = two_stage_mid(up, s.T2, s.Ls, s.Ms, 0, 0, 1, false).pad;
+    r.cls.resize(n_clips);
+    for (uint32_t c = 0; c < n_clips; ++c) {
+        const int64_t *row = rows + 4 * (size_t)c;
+        r.cls[c] = (uint8_t)ragged_poly_class(row[1], row[3], n_channels, width, s);
+        if (r.cls[c] == kRaggedPolyShort) r.short_rows.insert(r.short_rows.end(), row, row + 4);
+        if (r.cls[c] != kRaggedPolyTwo) continue;
+        for (uint32_t ch = 0; ch < n_channels; ++ch) {
+            r.col_clip.push_back(c); r.col_ch.push_back(ch);
+            r.col_mid.push_back(two_stage_mid(up, s.T2, s.Ls, s.Ms, row[1], two_stage_mid_outputs(up, s.Ls, s.Ms, row[1], row[3], fft_T), 1, false));
+        }
+    }
+    const uint32_t n = r.n_cols();
+    r.col_off.resize(n); r.poly_rows.resize(4 * (size_t)n); r.fft_rows.resize(4 * (size_t)n);
+    RaggedPolyRange g{0, 0, 0, 0, 0, 0};
+    for (uint32_t i = 0; i < n; ++i) {
+        const TwoStageMid &m = r.col_mid[i];
+        const int64_t *row = rows + 4 * (size_t)r.col_clip[i];
+        const int64_t elems = ragged_poly_col_elems(m.n_mid);
+        if (g.count && (g.count == kPolyMaxCols || (g.mid_elems + elems) * (int64_t)width > budget)) {
+            r.ranges.push_back(g);
+            g = RaggedPolyRange{i, 0, 0, 0, 0, 0};
+        }
+        const int64_t off = g.mid_elems, in_col = row[0] + (int64_t)r.col_ch[i] * in_chs, out_col = row[2] + (int64_t)r.col_ch[i] * out_chs;
+        r.col_off[i] = off;
+        int64_t *pr = &r.poly_rows[4 * (size_t)i], *fr = &r.fft_rows[4 * (size_t)i];
+        if (up) {
+            fr[0] = in_col; fr[1] = m.pad / 2 + row[1]; fr[2] = off; fr[3] = m.n_mid;
+            pr[0] = off + m.pad; pr[1] = m.n_core + m.pad; pr[2] = out_col; pr[3] = row[3];
+        } else {
+            pr[0] = in_col; pr[1] = row[1]; pr[2] = off; pr[3] = m.n_mid;
+            fr[0] = off; fr[1] = m.n_core + m.pad; fr[2] = out_col; fr[3] = row[3];
+        }
+        ++g.count; g.mid_elems += elems;
+        g.poly_longest = std::max(g.poly_longest, pr[3]);
+        g.fft_in_longest = std::max(g.fft_in_longest, up ? row[1] : m.n_mid);
+        g.fft_out_longest = std::max(g.fft_out_longest, fr[3]);
+    }
+    if (g.count) r.ranges.push_back(g);
+    return r;
+}
+// the form of a ragged polyphase launch: k_poly, one column per grid row (k_poly2 has no ragged form)
+inline PolyForm poly_form_ragged(int64_t longest) { return PolyForm{false, false, 0, longest, longest, 0, 0, 0}; }
 
 } // namespace hipsoxr

@@ -31,6 +31,7 @@
 
 #include "device.h"
 #include "poly_rules.h"
+#include "ragged_rules.h" // ragged_span_skip
 
 namespace hipsoxr {
 
@@ -211,6 +212,28 @@ struct PolyArgs {
     int64_t m2_src, m2_dst, m2_shift, m2_n_out;
 };
 
+struct PolyArgsR : PolyArgs {
+    const int64_t *rows; // [columns][4] = src offset of sample 0, n_src, dst offset, n_out (device; elements from src / dst)
+};
+template <bool RAGGED> struct PolyArgsOf { typedef PolyArgs type; };
+template <> struct PolyArgsOf<true> { typedef PolyArgsR type; };
+__device__ __forceinline__ int64_t uniform64(int64_t v)
+{
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// the arguments as one column's kernel sees them: the equal-length block itself, or a copy with the column's row put in
+// (the launcher passes one channel, no channel group and clip strides of 0: column = blockIdx.y)
+template <typename Real> __device__ __forceinline__ const PolyArgs &poly_column_args(const PolyArgs &a, PolyArgs &) { return a; }
+template <typename Real> __device__ __forceinline__ const PolyArgs &poly_column_args(const PolyArgsR &r, PolyArgs &v)
+{
+    const int64_t *row = r.rows + 4 * (int64_t)blockIdx.y;
+    v = r;
+    v.src = (const Real *)r.src + uniform64(row[0]); v.n_src = uniform64(row[1]);
+    v.dst = (Real *)r.dst + uniform64(row[2]); v.n_out = uniform64(row[3]);
+    return v;
+}
+
 __device__ __forceinline__ int64_t floor_div(int64_t q, int64_t d) // d > 0
 {
     const int64_t n = q / d;
@@ -225,10 +248,24 @@ template <> struct Rec4<double> { typedef double4 type; };
 // outputs' source windows then differ by MQ or MQ + 1 samples, and the thread keeps its window in REGISTERS, shifted by
 // v_cndmask between outputs, with two fresh samples read per output instead of TT — the table records are then the only
 // per-tap LDS traffic.  MQ = -1: the window is re-read from LDS for every output.
-template <typename Real, int TT, int MQ>
-__global__ void __launch_bounds__(256) k_poly(PolyArgs a)
+//
+// RAGGED (a clip table on the two-stage form, launch_two_stage_ragged): a second instantiation, `bool RAGGED`, whose argument
+// block carries a device table behind the usual arguments (the equal-length instances keep theirs, instruction for
+// instruction).  The launch has one channel and one grid row per (clip, channel) COLUMN; a workgroup's column reads its row
+// {src offset of sample 0, n_src, dst offset, n_out} — four int64, elements, built by the library (poly_rules.h
+// ragged_poly_plan) — in place of the job-wide n_src / n_out and the clip and channel strides; n_lo and k_lo stay job-wide
+// (they depend on the plan's pad alone).  The row address is wave-uniform (blockIdx.y) and its values stay on the scalar
+// side.  R, the lane order and the LDS size are the launch's, chosen from the LONGEST column, and so is the grid's x: the
+// tile count is the column's own, the persistent walk breaks at it, and a workgroup whose first tile lies at or behind its
+// column's end leaves before the table is copied to LDS and before the first barrier — a decision on block index and row
+// alone, so no barrier is met by part of a workgroup.
+template <typename Real, int TT, int MQ, bool RAGGED = false>
+__global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type a_)
 {
     typedef typename Rec4<Real>::type R4;
+    PolyArgs a_row;
+    const PolyArgs &a = poly_column_args<Real>(a_, a_row);
+    if (RAGGED && ragged_span_skip(blockIdx.x, 256LL * a.R, a.n_out)) return; // (uniform: none of this column's tiles is this workgroup's)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     R4 *tab = reinterpret_cast<R4 *>(smem);
     Real *xs = reinterpret_cast<Real *>(smem + (size_t)a.P * a.row * sizeof(R4));
@@ -649,6 +686,9 @@ struct PolyJob {
     int64_t n_lo, n_src, k_lo, n_out;
     uint32_t n_clips, n_channels;
     const int64_t *sstr, *dstr;
+    // a ragged launch (launch_two_stage_ragged): the device rows of its n_clips COLUMNS (n_channels == 1, clip strides 0, unit
+    // frame strides) — n_src / n_out are then the longest column's
+    const int64_t *rows = nullptr;
 };
 
 static PolyArgs poly_args(const PolyStage &s, const void *tab, const PolyForm &f, const PolyJob &j)
@@ -680,17 +720,18 @@ static PolyLane poly_lanes(const TwoStage &ts, const PolyStage &s, int which, in
     return l;
 }
 
-// the only place the instance lists expand: MQ = Mq where that is 0 or 1, else -1 (k_poly alone)
-template <typename Real>
-static void (*poly_kernel(int T2, int64_t Mq, bool pair, bool split))(PolyArgs)
+// the only place the instance lists expand: MQ = Mq where that is 0 or 1, else -1 (k_poly alone).  RAGGED: k_poly's ragged
+// instances — every tap count, MQ and element type (k_poly2 has none: pair and split are false there)
+template <typename Real, bool RAGGED = false>
+static void (*poly_kernel(int T2, int64_t Mq, bool pair, bool split))(typename PolyArgsOf<RAGGED>::type)
 {
-    void (*kern)(PolyArgs) = nullptr;
+    void (*kern)(typename PolyArgsOf<RAGGED>::type) = nullptr;
     switch (T2) {
-#define HIPSOXR_POLY_T(t) case t: kern = Mq == 0 ? k_poly<Real, t, 0> : Mq == 1 ? k_poly<Real, t, 1> : k_poly<Real, t, -1>; break;
+#define HIPSOXR_POLY_T(t) case t: kern = Mq == 0 ? k_poly<Real, t, 0, RAGGED> : Mq == 1 ? k_poly<Real, t, 1, RAGGED> : k_poly<Real, t, -1, RAGGED>; break;
         HIPSOXR_POLY_TAPS(HIPSOXR_POLY_T)
 #undef HIPSOXR_POLY_T
     }
-    if constexpr (sizeof(Real) == 4)
+    if constexpr (sizeof(Real) == 4 && !RAGGED)
         if (pair || split) switch (T2) {
 #define HIPSOXR_POLY_T(t) case t: kern = pair ? (Mq == 0 ? k_poly2<t, 0, true> : k_poly2<t, 1, true>) : (Mq == 0 ? k_poly2<t, 0, false> : k_poly2<t, 1, false>); break;
             HIPSOXR_POLY2_TAPS(HIPSOXR_POLY_T)
@@ -698,7 +739,6 @@ static void (*poly_kernel(int T2, int64_t Mq, bool pair, bool split))(PolyArgs)
         }
     return kern;
 }
-
 // (-DPOLY_TRACE: per-wave cycle sums [workgroup][wave][8], dumped synchronously behind the launch — a debugging aid)
 #ifdef POLY_TRACE
 static const char *poly_trace_begin(PolyArgs &a, dim3 grid, size_t *n)
@@ -726,13 +766,16 @@ static const char *poly_trace_dump(const PolyArgs &, size_t, hipStream_t) { retu
 
 // HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per polyphase launch, in the style of adjoint.hip's
 // adj_launch_log — what tests/test_gpu_two_stage_forms.py reads the launch form from.
-static void poly_launch_log(size_t width, const PolyArgs &a, const PolyForm &f, const PolyLane &ln, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid)
+// A ragged launch appends ragged=<columns> (tiles, n_out: the longest column's).
+static void poly_launch_log(size_t width, const PolyArgs &a, const PolyForm &f, const PolyLane &ln, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid, bool ragged)
 {
     FILE *fl = fopen(switches().dbg_launch_log, "a");
     if (!fl) return;
-    fprintf(fl, "kernel=%s width=%zu T=%d MQ=%d il=%d split=%d R=%d lane_mul=%d conf=%.4f lds=%zu lg_cg=%d cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_out=%lld m2_n_out=%lld\n",
+    fprintf(fl, "kernel=%s width=%zu T=%d MQ=%d il=%d split=%d R=%d lane_mul=%d conf=%.4f lds=%zu lg_cg=%d cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_out=%lld m2_n_out=%lld",
             f.pair || f.split ? "poly2" : "poly", width, a.T, a.Mq == 0 || a.Mq == 1 ? (int)a.Mq : -1, (int)f.pair, (int)f.split, a.R, ln.lane_mul, (double)ln.conf, lds,
             a.lg_cg, (unsigned long long)cols, (long long)n_tiles, grid.x, grid.y, grid.z, (long long)a.n_out, (long long)a.m2_n_out);
+    if (ragged) fprintf(fl, " ragged=%llu", (unsigned long long)cols);
+    fprintf(fl, "\n");
     fclose(fl);
 }
 
@@ -742,7 +785,8 @@ static const char *launch_poly(const TwoStage &ts, const PolyJob &j, hipStream_t
     if (j.n_out <= 0) return nullptr;
     constexpr size_t W = sizeof(Real);
     const PolyStage s = poly_stage(ts.T2, W == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms);
-    const PolyForm f = poly_form(W, s.Ms / s.Ls, j.n_channels, j.sstr, j.dstr, (uintptr_t)j.src | (uintptr_t)j.dst, s.T2, switches().poly_no_pair, j.n_out, s.Ls, s.Ms);
+    const PolyForm f = j.rows ? poly_form_ragged(j.n_out)
+                              : poly_form(W, s.Ms / s.Ls, j.n_channels, j.sstr, j.dstr, (uintptr_t)j.src | (uintptr_t)j.dst, s.T2, switches().poly_no_pair, j.n_out, s.Ls, s.Ms);
     PolyArgs a = poly_args(s, W == 4 ? ts.tab_f : ts.tab_d, f, j);
     const bool two = f.pair || f.split; // k_poly2
     const size_t unit = poly_unit(W, two), tab_bytes = poly_tab_bytes(s.P, s.row, W);
@@ -762,16 +806,25 @@ static const char *launch_poly(const TwoStage &ts, const PolyJob &j, hipStream_t
     const size_t lds = poly_lds_bytes(tab_bytes, a.R, s.ratio, s.T2, unit);
     if (lds > kPolyLdsMax) return "two-stage: polyphase tile does not fit LDS";
     const int64_t n_tiles = poly_tiles(a.n_out, a.R);
-    void (*kern)(PolyArgs) = poly_kernel<Real>(s.T2, a.Mq, f.pair, f.split);
-    if (!kern) return "two-stage: no polyphase instance for this tap count";
-    if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
+    // (a ragged launch: R, the lane order and the LDS size above and the grid below are the LONGEST column's)
+    void (*kern)(PolyArgs) = j.rows ? nullptr : poly_kernel<Real>(s.T2, a.Mq, f.pair, f.split);
+    void (*kern_r)(PolyArgsR) = j.rows ? poly_kernel<Real, true>(s.T2, a.Mq, false, false) : nullptr;
+    const void *fn = j.rows ? (const void *)kern_r : (const void *)kern;
+    if (!fn) return "two-stage: no polyphase instance for this tap count";
+    if (const char *e = ensure_dyn_lds(fn, lds)) return e;
     int per_cu = 0;
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 256, lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
     const dim3 grid(poly_grid_x(n_tiles, per_cu, n_cu, cols), (unsigned)cols, 1);
     size_t trace_n = 0;
     if (const char *e = poly_trace_begin(a, grid, &trace_n)) return e;
-    if (switches().dbg_launch_log) poly_launch_log(W, a, f, ln, lds, cols, n_tiles, grid);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+    if (switches().dbg_launch_log) poly_launch_log(W, a, f, ln, lds, cols, n_tiles, grid, j.rows != nullptr);
+    if (j.rows) {
+        PolyArgsR ar;
+        (PolyArgs &)ar = a;
+        ar.rows = j.rows;
+        hipLaunchKernelGGL(kern_r, grid, dim3(256), lds, st, ar);
+    } else
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
     return poly_trace_dump(a, trace_n, st);
 }
@@ -844,13 +897,131 @@ const char *launch_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream, bool
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
     if (!two_stage_admits(j.in_frames, j.out_frames, cols, es, poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms))) return nullptr;
     const bool inter = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1;
-    const TwoStageMid m = two_stage_mid(ts.up, ts.T2, ts.Ls, ts.Ms, j.in_frames, j.out_frames, j.n_channels, inter);
+    // (a truncated job down: the intermediate as far as its last outputs' FFT-stage filter reaches — two_stage_mid_outputs)
+    const TwoStageMid m = two_stage_mid(ts.up, ts.T2, ts.Ls, ts.Ms, j.in_frames, two_stage_mid_outputs(ts.up, ts.Ls, ts.Ms, j.in_frames, j.out_frames, ts.fft.T),
+                                        j.n_channels, inter);
     hipStream_t st = (hipStream_t)stream;
     void *mid = nullptr;
     HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)m.n_mid * es, st));
     const char *err = two_stage_run(p, j, m, mid, stream, handled);
     (void)hipFreeAsync(mid, st); // (behind whatever was queued: success, error and a declined FFT stage alike)
     return err;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A clip table on the two-stage form: a constant number of launches whatever the number of clips.  Every decision that
+// reads only numbers — the partition into empty, two-stage and short clips, each column's intermediate (two_stage_mid of
+// the clip alone), its place in the packed intermediate, the rows of both stages, the ranges — is poly_rules.h
+// ragged_poly_plan; here: the served layouts, ONE upload of every derived table, and per range one allocation, the two
+// launches in the direction's order and one free, in stream order; the short clips' launch last.
+// Served: float32 / float64, HIPSOXR_KERNEL_AUTO, unit frame strides both sides (mono clips, planar channels at any channel
+// stride) — what the ragged k_fft_pair2 reads.  The caller's clip_table_dev cannot serve: the inner launches read derived
+// tables (columns, not clips; intermediate offsets), and the short clips a compacted one.
+// *handled = false with no error — a layout not served, a plan without the form, a short clip the ragged exact launch does not
+// take, or the FFT stage declined — and the caller's clip-by-clip loop computes every clip.  (The FFT stage's answer follows
+// the plan, the layout and the range's sizes: it is expected in the first range, before the caller's output is touched, but a
+// later range is not excluded.  Either way the loop rewrites every clip, and the inner jobs carry no clip counter.)
+// ---------------------------------------------------------------------------------------------
+// A range's intermediate (up to kPolyMidBudget) comes from the device's default stream-ordered pool, whose release threshold is
+// 0 by default: memory it holds unused may go back to the system, and the next launch then acquires it anew.  The pool is asked
+// to keep as much as the largest range seen needs (never lowered; one query per call, one set when it grows).
+static void mid_pool_retain(uint64_t bytes)
+{
+    static std::mutex mu;
+    static uint64_t kept[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return;
+    std::lock_guard<std::mutex> lk(mu);
+    if (kept[dev] >= bytes) return;
+    hipMemPool_t pool = nullptr;
+    uint64_t cur = 0;
+    if (hipDeviceGetDefaultMemPool(&pool, dev) != hipSuccess || hipMemPoolGetAttribute(pool, hipMemPoolAttrReleaseThreshold, &cur) != hipSuccess) return;
+    if (cur < bytes && hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &bytes) != hipSuccess) return;
+    kept[dev] = std::max(cur, bytes);
+}
+const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+{
+    *handled = false;
+    if (!p->phases || !j.clip_table || (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) || j.kernel != HIPSOXR_KERNEL_AUTO) return nullptr;
+    if (j.in_frame_stride != 1 || j.out_frame_stride != 1 || j.in_abs0 != 0 || j.out_k0 != 0 || j.n_channels > kPolyMaxCols) return nullptr;
+    {
+        std::lock_guard<std::mutex> lk(p->mu);
+        if (!p->two)
+            if (const char *e = twostage_build(p)) return e;
+    }
+    const TwoStage &ts = *p->two;
+    if (!ts.ok) return nullptr;
+    const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
+    const PolyStage s = poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms);
+    const int64_t budget = switches().dbg_poly_mid_budget > 0 ? (int64_t)switches().dbg_poly_mid_budget : kPolyMidBudget;
+    const RaggedPolyPlan rp = ragged_poly_plan(j.clip_table, j.n_clips, j.n_channels, j.in_chan_stride, j.out_chan_stride, es, ts.up, s, ts.fft.T, budget);
+    const uint32_t n_short = rp.n_short(), n_cols = rp.n_cols();
+    if (!n_short && !n_cols) { *handled = true; return nullptr; } // nothing to write
+    if (ragged_longest(rp.short_rows.data(), n_short) > ((int64_t)1 << 30)) return nullptr; // (launch_ragged_job leaves such a clip to the loop)
+    hipStream_t st = (hipStream_t)stream;
+    if (n_cols)
+        if (const char *err = device_bank_ensure(&p->two->fft, engine_prec(j.elem))) return err;
+    {
+        int64_t peak = 0;
+        for (const RaggedPolyRange &g : rp.ranges) peak = std::max(peak, g.mid_elems);
+        mid_pool_retain((uint64_t)peak * es);
+    }
+    // every derived table in one host buffer and one upload: [short rows][poly rows][FFT rows].  (`host` is pageable and dies
+    // at return: this relies on hipMemcpyAsync having read pageable host memory into its staging buffers before it returns —
+    // clip_table_device relies on the same for a caller's table that may be a temporary.)
+    std::vector<int64_t> host(rp.short_rows);
+    host.insert(host.end(), rp.poly_rows.begin(), rp.poly_rows.end());
+    host.insert(host.end(), rp.fft_rows.begin(), rp.fft_rows.end());
+    int64_t *tabs = nullptr;
+    if (hipMallocAsync((void **)&tabs, host.size() * sizeof(int64_t), st) != hipSuccess) return "ragged batches: no device memory for the two-stage form's tables";
+    const int64_t *short_dev = tabs, *poly_dev = tabs + 4 * (size_t)n_short, *fft_dev = poly_dev + 4 * (size_t)n_cols;
+    const char *err = nullptr;
+    bool all = true;
+    if (hipMemcpyAsync(tabs, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) err = "ragged batches: table upload failed";
+    const int64_t unit[3] = {0, 1, 0}; // columns: no clip stride, unit frames, one channel
+    for (size_t r = 0; r < rp.ranges.size() && !err && all; ++r) {
+        const RaggedPolyRange &g = rp.ranges[r];
+        void *mid = nullptr;
+        if (hipMallocAsync(&mid, (size_t)g.mid_elems * es, st) != hipSuccess) { err = "two-stage: no device memory for the intermediate signal"; break; }
+        PolyJob pj;
+        pj.n_clips = g.count; pj.n_channels = 1; pj.sstr = unit; pj.dstr = unit;
+        pj.rows = poly_dev + 4 * (size_t)g.first; pj.n_out = g.poly_longest;
+        hipsoxr_job_t fj = j;
+        fj.kernel = HIPSOXR_KERNEL_FFT; fj.clip_counter = nullptr; fj.dither = 0;
+        fj.n_clips = g.count; fj.n_channels = 1;
+        fj.in_clip_stride = fj.out_clip_stride = 0; fj.in_chan_stride = fj.out_chan_stride = 0;
+        fj.clip_table = rp.fft_rows.data() + 4 * (size_t)g.first; fj.clip_table_dev = fft_dev + 4 * (size_t)g.first;
+        fj.in_frames = g.fft_in_longest; fj.out_frames = g.fft_out_longest;
+        if (ts.up) { // x --FFT 1:2--> mid --poly--> y
+            fj.in_abs0 = rp.pad / 2; fj.out = mid;
+            pj.src = mid; pj.dst = j.out; pj.n_lo = -rp.pad; pj.k_lo = 0; pj.n_src = 0;
+        } else {     // x --poly--> mid --FFT 2:1--> y
+            pj.src = j.in; pj.dst = mid; pj.n_lo = 0; pj.k_lo = -rp.pad; pj.n_src = 0;
+            fj.in = mid; fj.in_abs0 = -rp.pad;
+        }
+        bool fft_done = false;
+        if (ts.up) {
+            err = launch_fft(&p->two->fft, fj, stream, &fft_done);
+            if (!err && !fft_done) all = false;
+        }
+        if (!err && all) err = run_poly(j.elem, ts, pj, st);
+        if (!err && all && !ts.up) {
+            err = launch_fft(&p->two->fft, fj, stream, &fft_done);
+            if (!err && !fft_done) all = false;
+        }
+        (void)hipFreeAsync(mid, st); // (behind whatever was queued)
+    }
+    if (!err && all && n_short) { // the clips the form does not admit: the exact engine's ragged launch over the compacted sub-table
+        hipsoxr_job_t sj = j;
+        sj.n_clips = n_short; sj.clip_table = rp.short_rows.data(); sj.clip_table_dev = short_dev;
+        bool h = false;
+        err = launch_ragged_short(p, sj, stream, &h);
+        if (!err && !h) all = false;
+    }
+    (void)hipFreeAsync(tabs, st);
+    if (err) return err;
+    *handled = all;
+    return nullptr;
 }
 
 } // namespace hipsoxr

@@ -125,9 +125,15 @@ class RaggedJob:
     the table; the grid is the longest clip's; more than 65535 clip x channel columns: one launch per range of clips).
     Each clip has the bits of the clip run alone.  Interpolated-phase plans (`plan.phases != 0`, the arbitrary ratios) are
     ONE launch as well — int16 / int32 under the default selector, every type under KERNEL_EXACT / KERNEL_GATHER — on the
-    ragged form of k_interp_tile, k_interp_wave or k_interp, chosen from the table; float clips of such a plan under
-    KERNEL_AUTO (the two-stage form, another precision class) and KERNEL_WAVE_DOT are served clip by clip inside the same
-    call.
+    ragged form of k_interp_tile, k_interp_wave or k_interp, chosen from the table.  float32 / float64 clips of such a plan
+    under KERNEL_AUTO belong to the two-stage form (another precision class): MONO clips are a constant number of launches
+    whatever the number of clips — the table is partitioned by the question asked of each clip alone: clips of 8192 frames
+    or more on both sides run the two-stage form (one ragged polyphase launch + one ragged FFT-stage launch over all of
+    them; more than 65535 of them, or more than 1 GiB of intermediate signal, cut that into ranges), every other non-empty
+    clip the exact engine (one ragged launch).  Admitted clips are within the two-stage class of the float64 direct form
+    (1e-6 float32 / 2e-9 float64 relative RMS), not bit-equal to the clip run alone; the short clips are bit-equal to it.
+    Interleaved multichannel float clips under KERNEL_AUTO (the ragged FFT kernels have no strided form) and
+    KERNEL_WAVE_DOT are served clip by clip inside the same call.
 
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
@@ -317,7 +323,9 @@ def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AU
     """Resample a batch of clips of unequal length on one device as one job; returns the list of per-clip outputs (views
     of one packed buffer).  Without `requires_grad` on any clip, or under `no_grad`, this is exactly
     `RaggedJob(plan, clips, kernel).launch()` and its `outputs()` — one launch on an exact-bank plan and, with
-    kernel=KERNEL_EXACT, on an interpolated-phase plan too (see `RaggedJob`).
+    kernel=KERNEL_EXACT, on an interpolated-phase plan too; under the default selector mono float clips of an
+    interpolated-phase plan are three launches (the two-stage form over the clips of 8192 frames or more, the exact engine over
+    the shorter ones: 1e-6-class and bit-equal to the clip alone respectively — see `RaggedJob`).
 
     Differentiable otherwise: the result carries a grad_fn whose backward is ONE ragged launch of the transposed operator
     (`resample_ragged_adjoint` with `grad_kernel`), whatever the number of clips; gradients of gradients flow too (the double
@@ -630,7 +638,11 @@ def resample_batch(clips, in_rate, out_rate, quality="VHQ", devices=None, kernel
     kernel   : engine selector for the device jobs (AUTO: the frequency-domain engine for large float jobs,
                1e-6-class; KERNEL_EXACT: the canonical-order engine, bit-identical to `soxr_amd.resample`;
                KERNEL_FFT_PCM: the frequency-domain engine for an int16 / int32 corpus — mono clips, one launch per
-               block, within 1 LSB of the canonical order).
+               block, within 1 LSB of the canonical order).  A float32 / float64 corpus of MONO clips at an arbitrary
+               ratio (an interpolated-phase plan) under AUTO is three launches per block: the two-stage form over the
+               block's clips of 8192 frames or more (1e-6 / 2e-9 class, not bit-equal to the clip alone), the exact engine
+               over its shorter clips (bit-equal to `soxr_amd.resample`); interleaved multichannel float clips at such a
+               ratio are still served clip by clip inside the block's call.
     Returns a list of arrays of the same kind (numpy in -> numpy out; tensor in -> tensor on the device that
     computed it), in the order given."""
     import torch
