@@ -749,7 +749,7 @@ struct GatherLaunch {
 };
 
 // HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): one line per launch of launch_gather's family, in the style of
-// tile_launch_log — what tests/test_gpu_interp_forms.py reads the kernel form from.  `form`: the form's own fields.
+// tile_launch_log — what tests/test_gpu_interp_forms.py and test_gpu_gather_forms.py read the form from.  `form`: its own fields.
 #ifdef HIPSOXR_DEBUG_SWITCHES
 template <typename IO, typename Real>
 __attribute__((format(printf, 7, 8)))
@@ -785,7 +785,7 @@ static const char *launch_gather_wave(Plan *p, const GatherLaunch &c, const Wave
     ga.g = c.a; ga.phase_major = bank_of<Real>(p).phase_major; ga.span_cap = (int32_t)g.span; ga.done_words = nullptr; ga.done_seq = 0;
     const dim3 grid = c.grid(32);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ga.done_words, &ga.done_seq);
-    GATHER_LAUNCH_LOG("gather_wave", *p, c, grid, 256, g.lds, "span_cap=%d", (int)ga.span_cap);
+    GATHER_LAUNCH_LOG("gather_wave", *p, c, grid, 256, g.lds, "span_cap=%d cw=%d", (int)ga.span_cap, ga.done_words ? 1 : 0);
     hipLaunchKernelGGL((k_gather_wave<IO, Real>), grid, dim3(256), g.lds, c.st, ga);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -843,7 +843,7 @@ static const char *launch_chain(Plan *p, const GatherLaunch &c, const ChainGeom 
     if (const char *e = ensure_dyn_lds((const void *)ck, g.lds)) return e;
     const dim3 grid = c.grid(g.NO);
     claim_done_words(c.cd, c.whole_job(), (uint64_t)grid.x * grid.y, &ca.done_words, &ca.done_seq);
-    GATHER_LAUNCH_LOG("chain", *p, c, grid, 256, g.lds, "NO=%d span_cap=%d mode=%d", g.NO, (int)g.span_cap, c.vr ? 2 : p->phases ? 1 : 0);
+    GATHER_LAUNCH_LOG("chain", *p, c, grid, 256, g.lds, "NO=%d span_cap=%d mode=%d cw=%d", g.NO, (int)g.span_cap, c.vr ? 2 : p->phases ? 1 : 0, ca.done_words ? 1 : 0);
     hipLaunchKernelGGL(ck, grid, dim3(256), g.lds, c.st, ca);
     HIP_TRY(hipGetLastError());
     return nullptr;
@@ -1517,6 +1517,31 @@ const char *launch_copy(void *dst, const void *src, size_t bytes, void *stream)
     return nullptr;
 }
 
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): the line of a k_chain_multi launch, in the style of gather_launch_log
+// (there is no GatherLaunch here: the items are the streams' own) — what tests/test_gpu_gather_forms.py reads.  moving: items
+// whose ring moves in this launch (ring_dst != ring); empty: items without an output due, which still append their chunk.
+#ifdef HIPSOXR_DEBUG_SWITCHES
+template <typename IO, typename Real>
+static void chain_multi_launch_log(const Plan &p, const ChainItem *items, uint32_t n_items, uint32_t nch, int64_t max_out, dim3 grid, unsigned block,
+                                   const ChainGeom &g)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    unsigned moving = 0, empty = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        if (items[i].ring_dst != items[i].ring) ++moving;
+        if (items[i].out_frames == 0) ++empty;
+    }
+    fprintf(fl, "kernel=chain_multi width=%zu io=%c%zu L=%lld M=%lld T=%d P=%d items=%u nch=%u max_out=%lld grid=%ux%ux%u block=%u lds=%zu NO=%d span_cap=%d mode=%d moving=%u empty=%u\n",
+            sizeof(Real), std::is_integral<IO>::value ? 'i' : 'f', sizeof(IO) * 8, (long long)p.L, (long long)p.M, (int)p.T, (int)p.phases, n_items, nch,
+            (long long)max_out, grid.x, grid.y, grid.z, block, g.lds, g.NO, (int)g.span_cap, p.phases ? 1 : 0, moving, empty);
+    fclose(fl);
+}
+#define CHAIN_MULTI_LAUNCH_LOG(...) do { if (switches().dbg_launch_log) chain_multi_launch_log<IO, Real>(__VA_ARGS__); } while (0)
+#else
+#define CHAIN_MULTI_LAUNCH_LOG(...) ((void)0)
+#endif
+
 template <typename IO, typename Real>
 static const char *launch_chain_items_typed(Plan *p, uint32_t nch, bool dither, const ChainItem *items, const ChainItem *items_dev, uint32_t n_items,
                                             hipStream_t st, bool *handled)
@@ -1552,6 +1577,7 @@ static const char *launch_chain_items_typed(Plan *p, uint32_t nch, bool dither, 
     else m.items = items_dev;
     if (const char *e = ensure_dyn_lds((const void *)ck, g.lds)) return e;
     const unsigned gx = (unsigned)std::max<int64_t>(1, (max_out + g.NO - 1) / g.NO);
+    CHAIN_MULTI_LAUNCH_LOG(*p, items, n_items, nch, max_out, dim3(gx, (unsigned)(n_items * nch), 1), 256, g);
     hipLaunchKernelGGL(ck, dim3(gx, (unsigned)(n_items * nch), 1), dim3(256), g.lds, st, m);
     HIP_TRY(hipGetLastError());
     *handled = true;
