@@ -12,7 +12,9 @@ so the persistent walk and the skip test work at the smallest admitted size); HI
 cut: several launch pairs, the same bits).
 Plans: 48000 -> 44101 (down: polyphase stage first, MQ 0), 44101 -> 48000 (up: FFT stage first, MQ 1), 44100 -> 16001 (down, MQ 1)
 on HQ, float32; 48000 -> 44101 and 44101 -> 48000 on VHQ, float64.  (MQ = floor(Ms / Ls) of the polyphase stage is 0 or 1 for
-every ratio the form takes: the MQ -1 instances are not reachable through a plan.  Each job's log line is checked for its MQ.)
+every ratio the form takes: the MQ -1 instances are not reachable through a plan.  Each job's log line is checked for its MQ
+and its tap count T.)  And, default environment only, one job for every other ragged instance a plan can launch — twenty (T, MQ,
+type) in all, the census of tests/test_gpu_poly_instances.py; float64 on an HQ plan at 1e-6, its float32 form's bar.
 
 Launch count (fails on the parent, which writes two lines per admitted clip and none with ragged=): exactly one kernel=poly
 line with ragged=<admitted columns>, exactly one FFT line with the same ragged=, exactly one interp* line with ragged=<short
@@ -26,6 +28,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -36,6 +39,7 @@ DBG_LIB = os.path.join(os.path.dirname(HERE), "python-soxr_amd", "_variants", "d
 SENTINEL = 12345.0
 NP = {"f32": np.float32, "f64": np.float64}
 TOL = {"f32": 1e-6, "f64": 2e-9}
+TOL_F64_HQ = 1e-6  # float64 on an HQ plan (a 20-bit recipe): the bar its float32 form meets on the same filter
 
 DOWN, UP, STEEP = (48000, 44101), (44101, 48000), (44100, 16001)
 CUT_BUDGET = 300000  # bytes of intermediate per range in the "cut" environment: two to four of the tables' columns
@@ -47,7 +51,7 @@ ENVS = {
 }
 TIMEOUT = {"default": 240, "r1": 180, "cut": 120}
 
-JOBS = {}  # (env, name) -> job for the probe (+ "mq": the MQ its poly line must show)
+JOBS = {}  # (env, name) -> job for the probe (+ "mq", "t2": the MQ and the tap count T its poly line must show)
 
 
 def _job(env, name, rates, quality, dtype, ch, layout, mq, seed=None, **kw):
@@ -56,21 +60,31 @@ def _job(env, name, rates, quality, dtype, ch, layout, mq, seed=None, **kw):
     JOBS[(env, name)] = j
 
 
-_job("default", "down_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0)
-_job("default", "up_f32_split2", UP, "HQ", "f32", 2, "split", 1)
-_job("default", "steep_f32_rows", STEEP, "HQ", "f32", 1, "rows", 1)
-_job("default", "down_f64_split2", DOWN, "VHQ", "f64", 2, "split", 0)
-_job("default", "up_f64_packed", UP, "VHQ", "f64", 1, "packed", 1)
-_job("r1", "down_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0)
-_job("r1", "up_f32_split2", UP, "HQ", "f32", 2, "split", 1)
-_job("r1", "steep_f32_rows", STEEP, "HQ", "f32", 1, "rows", 1)
-_job("r1", "up_f64_packed", UP, "VHQ", "f64", 1, "packed", 1)
+_job("default", "down_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0, t2=12)
+_job("default", "up_f32_split2", UP, "HQ", "f32", 2, "split", 1, t2=20)
+_job("default", "steep_f32_rows", STEEP, "HQ", "f32", 1, "rows", 1, t2=28)
+_job("default", "down_f64_split2", DOWN, "VHQ", "f64", 2, "split", 0, t2=16)
+_job("default", "up_f64_packed", UP, "VHQ", "f64", 1, "packed", 1, t2=28)
+_job("r1", "down_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0, t2=12)
+_job("r1", "up_f32_split2", UP, "HQ", "f32", 2, "split", 1, t2=20)
+_job("r1", "steep_f32_rows", STEEP, "HQ", "f32", 1, "rows", 1, t2=28)
+_job("r1", "up_f64_packed", UP, "VHQ", "f64", 1, "packed", 1, t2=28)
 # ... with 40 more clips of the smallest admitted size: 46 columns share the chip, so a column has fewer workgroups than tiles
-_job("r1", "walk_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0, extra=40)
+_job("r1", "walk_f32_packed", DOWN, "HQ", "f32", 1, "packed", 0, t2=12, extra=40)
 # the range cut: the default environment's jobs again (same seed, same table), the intermediate budget lowered
 for _n in ("down_f32_packed", "up_f32_split2", "down_f64_split2"):
     _j = JOBS[("default", _n)]
-    _job("cut", _n, _j["case"][:2], _j["case"][2], _j["dtype"], _j["ch"], _j["layout"], _j["mq"], seed=_j["seed"], solo_auto=False)
+    _job("cut", _n, _j["case"][:2], _j["case"][2], _j["dtype"], _j["ch"], _j["layout"], _j["mq"], seed=_j["seed"], t2=_j["t2"], solo_auto=False)
+
+# every other ragged instance a plan can launch — k_poly<float | double, T, MQ, RAGGED> for the (T, MQ) and types that
+# tests/test_gpu_poly_instances.py lists as reachable, whose census reads these jobs' log lines: the same table, layouts and checks
+for _t2, _mq, _rates, _quality, _dtypes in (
+        (16, 0, (48000, 44101), "VHQ", ("f32",)), (20, 0, (48000, 32001), "VHQ", ("f32", "f64")), (24, 0, (48000, 27941), "VHQ", ("f32", "f64")),
+        (28, 0, (48000, 96734), "VHQ", ("f32", "f64")), (12, 0, (48000, 45887), "HQ", ("f64",)), (20, 1, (44101, 48000), "HQ", ("f64",)),
+        (24, 1, (48000, 20962), "HQ", ("f32", "f64")), (32, 1, (44100, 12986), "HQ", ("f32", "f64")), (40, 1, (48000, 12986), "HQ", ("f32",)),
+        (48, 1, (48000, 13983), "VHQ", ("f32",))):
+    for _dtype in _dtypes:
+        _job("default", "t%d_mq%d_%s" % (_t2, _mq, _dtype), _rates, _quality, _dtype, 1, "rows" if _t2 % 8 else "packed", _mq, t2=_t2)
 
 PY_JOBS = [
     dict(kind="py_ragged", name="py_ragged", case=[DOWN[0], DOWN[1], "HQ"], seed=11, lengths=[9000, 150, 0, 12000, 8500], grad_lengths=[300, 0, 120]),
@@ -87,37 +101,43 @@ def _nothing_after_a_failed_child():
         pytest.fail("a probe process failed (%s): no further GPU work from this file" % _child_failed[0])
 
 
+def run_child(env_name, tmp_path_factory):
+    """-> the results of one environment's child process (started on first use, once per session: tests/test_gpu_poly_instances.py
+    reads the default child's log lines for its census)"""
+    if env_name in _results:
+        return _results[env_name]
+    if _child_failed:
+        pytest.fail("a probe process failed (%s): no further GPU work from this file" % _child_failed[0])
+    tmp = tmp_path_factory.mktemp("ragged_two_stage_" + env_name)
+    assert os.path.exists(DBG_LIB), "build.sh makes the debug-switch build beside the product"
+    jobs = [dict(j) for (e, _), j in JOBS.items() if e == env_name]
+    if env_name == "cut":  # the uncut job's own table: its tile size (a launch over fewer columns may pick another R)
+        for j in jobs:
+            j["u"] = int(run_child("default", tmp_path_factory)["geom_" + j["name"]][0])
+    with open(tmp / "jobs.json", "w") as f:
+        json.dump(jobs + (PY_JOBS if env_name == "default" else []), f)
+    env = {key: v for key, v in os.environ.items() if not key.startswith("HIPSOXR_")}
+    env.update({"HIPSOXR_LIBRARY": DBG_LIB, "HIPSOXR_DEBUG_LAUNCH_LOG": str(tmp / "launch.log")})
+    env.update(ENVS[env_name])
+    t0 = time.time()
+    try:
+        r = subprocess.run([sys.executable, os.path.join(HERE, "_ragged_two_stage_probe.py"), str(tmp / "jobs.json"), str(tmp / "out.npz")],
+                           env=env, capture_output=True, text=True, timeout=TIMEOUT[env_name])
+    except subprocess.TimeoutExpired:
+        _child_failed.append("%s: time limit" % env_name)
+        raise
+    if r.returncode != 0:
+        _child_failed.append("%s: exit status %d" % (env_name, r.returncode))
+    assert r.returncode == 0, r.stderr[-3000:]
+    print("ragged two-stage child %s: %d jobs, %.1f s (time limit %d s)" % (env_name, len(jobs), time.time() - t0, TIMEOUT[env_name]))
+    _results[env_name] = np.load(tmp / "out.npz")
+    return _results[env_name]
+
+
 @pytest.fixture(scope="module")
 def run_env(tmp_path_factory):
     """-> the results of one environment's child process (started on first use, once)"""
-    def get(env_name):
-        if env_name in _results:
-            return _results[env_name]
-        if _child_failed:
-            pytest.fail("a probe process failed (%s): no further GPU work from this file" % _child_failed[0])
-        tmp = tmp_path_factory.mktemp("ragged_two_stage_" + env_name)
-        assert os.path.exists(DBG_LIB), "build.sh makes the debug-switch build beside the product"
-        jobs = [dict(j) for (e, _), j in JOBS.items() if e == env_name]
-        if env_name == "cut":  # the uncut job's own table: its tile size (a launch over fewer columns may pick another R)
-            for j in jobs:
-                j["u"] = int(get("default")["geom_" + j["name"]][0])
-        with open(tmp / "jobs.json", "w") as f:
-            json.dump(jobs + (PY_JOBS if env_name == "default" else []), f)
-        env = {key: v for key, v in os.environ.items() if not key.startswith("HIPSOXR_")}
-        env.update({"HIPSOXR_LIBRARY": DBG_LIB, "HIPSOXR_DEBUG_LAUNCH_LOG": str(tmp / "launch.log")})
-        env.update(ENVS[env_name])
-        try:
-            r = subprocess.run([sys.executable, os.path.join(HERE, "_ragged_two_stage_probe.py"), str(tmp / "jobs.json"), str(tmp / "out.npz")],
-                               env=env, capture_output=True, text=True, timeout=TIMEOUT[env_name])
-        except subprocess.TimeoutExpired:
-            _child_failed.append("%s: time limit" % env_name)
-            raise
-        if r.returncode != 0:
-            _child_failed.append("%s: exit status %d" % (env_name, r.returncode))
-        assert r.returncode == 0, r.stderr[-3000:]
-        _results[env_name] = np.load(tmp / "out.npz")
-        return _results[env_name]
-    return get
+    return lambda env_name: run_child(env_name, tmp_path_factory)
 
 
 def _lines(log):
@@ -220,6 +240,7 @@ def _check_launches(key, res, pairs):
     kinds = ["fft" if "form" in f else "poly" if f.get("kernel") == "poly" else "interp" for f in lines]
     assert kinds == (["fft", "poly"] if up else ["poly", "fft"]) * pairs + ["interp"], kinds
     for f in poly:
+        assert int(f["T"]) == job["t2"], f
         assert int(f["MQ"]) == job["mq"] and int(f["width"]) == {"f32": 4, "f64": 8}[job["dtype"]] and f["il"] == "0" and f["split"] == "0", f
         assert 256 * int(f["R"]) == u or key[0] == "cut", "the table was made for the launcher's own R"
     return poly, admitted
@@ -269,7 +290,7 @@ def test_admitted_columns_match_the_oracle_and_memory_is_kept(key, run_env, orac
     got = _clips(key, res)
     u = int(res["geom_" + job["name"]][0])
     pl = oracle.plan(*job["case"])
-    tol, worst = TOL[job["dtype"]], 0.
+    tol, worst = TOL_F64_HQ if (job["dtype"], job["case"][2]) == ("f64", "HQ") else TOL[job["dtype"]], 0.
     for c, (x, y) in enumerate(got):
         if not _admitted(res["table_" + job["name"]][c]):
             continue
