@@ -100,7 +100,27 @@ typedef enum {
                                   int32 with more than one channel, int16 with an odd channel count above one. */
 
 /* Element types used by device jobs (layout is given by strides, not by the type). */
-typedef enum { HIPSOXR_F32 = 0, HIPSOXR_F64 = 1, HIPSOXR_I32 = 2, HIPSOXR_I16 = 3 } hipsoxr_elem_t;
+typedef enum {
+    HIPSOXR_F32 = 0, HIPSOXR_F64 = 1, HIPSOXR_I32 = 2, HIPSOXR_I16 = 3,
+    /* IEEE binary16 and bfloat16 samples, DEVICE JOBS ONLY (hipsoxr_run_device, hipsoxr_run_device_adjoint): input and output
+     * have the same type, the arithmetic is float32 throughout.  The result is, bit for bit, the HIPSOXR_F32 job of the same
+     * selector and layout on the exactly widened samples, followed by ONE round-to-nearest-even conversion: NaN stays NaN,
+     * +-inf stays +-inf, a float32 result beyond the type's range becomes +-inf (no saturation), float16 subnormals are exact
+     * on the way in and correctly rounded on the way out; dither and clip_counter are ignored, as for float jobs.  Where the
+     * float32 job runs the frequency-domain engine's paired kernels on unit-stride columns or interleaved channel pairs (and
+     * under a clip_table: unit-stride columns, one ragged launch) the conversion is fused into that kernel — 2-byte loads,
+     * 16-byte stores of eight samples; everywhere else (small jobs, recipes below HQ, ratios outside the schedule table,
+     * interpolated-phase plans, other layouts, HIPSOXR_KERNEL_EXACT / _GATHER / _TILE*, job windows, the adjoint entry) the
+     * job is one widening pass into stream-ordered float32 temporaries packed in the caller's dimension order, the float32
+     * job, and one narrowing pass that writes exactly the job's output elements (ranges of clips — with one clip, of
+     * channels — keep the temporaries of a range at or below 1 GiB; each range is then the float32 job of that range).
+     * One difference in engine choice: 44.1k -> 48k from 8192 block pairs, where float32 takes the one-wave kernel, stays
+     * on the fused paired kernel (1e-6 class either way).  A clip_table the fused path does not take runs clip by clip.
+     * Refused by name: HIPSOXR_KERNEL_FFT_PCM, _FFT_F64 and _WAVE_DOT on these types, hipsoxr_run_device_adjoint_ragged,
+     * and every stream entry — hipsoxr_datatype_t has no such member (its values 4 and 5 are the split float layouts, and a
+     * stream reads them as that). */
+    HIPSOXR_F16 = 4, HIPSOXR_BF16 = 5
+} hipsoxr_elem_t;
 
 /* Kernel selector for hipsoxr_run_device. */
 typedef enum {
@@ -247,7 +267,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form; no new field — the element types HIPSOXR_F16 / HIPSOXR_BF16).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
@@ -258,7 +278,8 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *, const hipsoxr_j
  * the adjoint's own direction: `in` is gy with in_frames = n_y frames, `out` is gx with out_frames = n_x frames, strides as
  * usual; in_frames <= hipsoxr_plan_out_len(plan, out_frames) (a truncated forward output has a truncated cotangent).  Every
  * element of gx is written (0 where no output reads the input), nothing outside it; gather form, no atomics: results are
- * bitwise reproducible and independent of layout.  HIPSOXR_F32 / HIPSOXR_F64 on exact-bank plans; kernel = HIPSOXR_KERNEL_AUTO
+ * bitwise reproducible and independent of layout.  HIPSOXR_F32 / HIPSOXR_F64 (HIPSOXR_F16 / HIPSOXR_BF16: the float32 adjoint on
+ * the widened cotangent, rounded once) on exact-bank plans; kernel = HIPSOXR_KERNEL_AUTO
  * or _EXACT; in_abs0 == 0, out_k0 == 0, clip_table == NULL; anything else is an error that names the reason, never a run of
  * another path.  kernel = HIPSOXR_KERNEL_ADJOINT: the same on every constant-rate plan, interpolated-phase plans included
  * (A is then the forward HIPSOXR_KERNEL_EXACT computes from the plan's interpolation table).  Zero frames, clips or channels: success, nothing launched.  Asynchronous on `hip_stream`. */
@@ -274,7 +295,7 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *, const h
  * own clip only, what it reaches in the kernel form the ragged launch took).  Selectors: HIPSOXR_KERNEL_AUTO, _EXACT (exact-bank
  * plans) and HIPSOXR_KERNEL_ADJOINT (every constant-rate plan).  Refused by name, before anything is launched: a NULL
  * clip_table, a negative offset or count, a row above the job's in_frames / out_frames, n_y[c] above the plan's output length
- * for n_x[c], integer element types, in_abs0 / out_k0 != 0, variable-rate plans, any other selector.  No clips, no channels
+ * for n_x[c], integer element types, HIPSOXR_F16 / HIPSOXR_BF16, in_abs0 / out_k0 != 0, variable-rate plans, any other selector.  No clips, no channels
  * or out_frames == 0: success, nothing launched.  Asynchronous on `hip_stream`. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
 

@@ -30,6 +30,8 @@ mkdir -p "$OBJ"
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/soxr_abi.cpp" -o "$OBJ/soxr_abi.o" & P5=$!
 # (adjoint.hip: the transposed operator of the exact engine — explicit fma chains, like kernels.hip)
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/adjoint.hip" -o "$OBJ/adjoint.o" & P14=$!
+# (half.hip: the widening / narrowing passes of float16 / bfloat16 jobs no fused kernel takes — copies, no arithmetic)
+"$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/half.hip" -o "$OBJ/half.o" & P15=$!
 # The A/B and timing-experiment switches (device.h `Switches`, everything but four product names) are read from the
 # environment only by a build with -DHIPSOXR_DEBUG_SWITCHES.  The reader lives in kernels.hip alone, so the debug build is
 # that one object compiled a second time and linked with the product's other objects: _variants/dbg/libhipsoxr.so
@@ -38,8 +40,8 @@ P8=""
 if [ -z "$HIPSOXR_VARIANT" ]; then
   "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -DHIPSOXR_DEBUG_SWITCHES -c "$SRC/kernels.hip" -o "$OBJ/kernels_dbg.o" & P8=$!
 fi
-# (fft.hip in six translation units: see "Three translation units" there; 3 and 4 hold the integer-sample kernels, 5 the
-#  float32-only block sizes of one-round jobs)
+# (fft.hip in nine translation units: see "Three translation units" there; 3 and 4 hold the integer-sample kernels, 5 the
+#  float32-only block sizes of one-round jobs, 6 and 7 the float16 / bfloat16 kernels, 8 those of the one-round block sizes)
 FFTFLAGS="${HIPSOXR_FFTFLAGS:--ffp-contract=fast -fno-slp-vectorize}"
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=0 -c "$SRC/fft.hip" -o "$OBJ/fft.o" & P4=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=1 -c "$SRC/fft.hip" -o "$OBJ/fft1.o" & P6=$!
@@ -47,10 +49,13 @@ FFTFLAGS="${HIPSOXR_FFTFLAGS:--ffp-contract=fast -fno-slp-vectorize}"
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=3 -c "$SRC/fft.hip" -o "$OBJ/fft3.o" & P11=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=4 -c "$SRC/fft.hip" -o "$OBJ/fft4.o" & P12=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=5 -c "$SRC/fft.hip" -o "$OBJ/fft5.o" & P13=$!
+"$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=6 -c "$SRC/fft.hip" -o "$OBJ/fft6.o" & P16=$!
+"$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=7 -c "$SRC/fft.hip" -o "$OBJ/fft7.o" & P17=$!
+"$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=8 -c "$SRC/fft.hip" -o "$OBJ/fft8.o" & P18=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/twostage.hip" -o "$OBJ/twostage.o" & P9=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/fftwave.hip" -o "$OBJ/fftwave.o" & P10=$!
-wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13; wait $P14   # set -e: any failed compile aborts here
-OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/adjoint.o $OBJ/soxr_abi.o"
+wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13; wait $P14; wait $P15; wait $P16; wait $P17; wait $P18   # set -e: any failed compile aborts here
+OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/fft6.o $OBJ/fft7.o $OBJ/fft8.o $OBJ/half.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/adjoint.o $OBJ/soxr_abi.o"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC $OBJS -o "$OUT"
 # The same engine under libsoxr's name: what `find_library(SOXR_LIBRARY NAMES soxr)` of the
 # reference's USE_SYSTEM_LIBSOXR build picks up (reference CMakeLists.txt:83-93).

@@ -625,6 +625,17 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
     const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT; // every constant-rate plan: k_adj_interp where there is no exact bank
+    if (elem_is_half(j.elem)) {
+        // float16 / bfloat16: the float32 adjoint on the widened cotangent, rounded once (half.hip) — under every selector
+        // this entry serves for float32.  The refusals by name and the empty job first, asked of the float32 job without clips.
+        hipsoxr_job_t f = j;
+        f.elem = HIPSOXR_F32; f.n_clips = 0;
+        if (const char *e = launch_adjoint(p, f, stream)) return e;
+        if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
+        if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+        if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+        return launch_half(p, j, stream, true);
+    }
     if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
     if (by_name && p->vr) return "adjoint job: variable-rate plans are not served (HIPSOXR_KERNEL_ADJOINT takes constant-rate plans)";
     if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
@@ -653,6 +664,8 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT;
+    if (elem_is_half(j.elem))
+        return "adjoint job: ragged: float16 / bfloat16 clip tables are not served (float32 or float64; half cotangents clip by clip through hipsoxr_run_device_adjoint)";
     if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
     if (p->vr) return "adjoint job: variable-rate plans are not served (ragged batches take constant-rate plans)";
     if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans are served by name, HIPSOXR_KERNEL_ADJOINT)";

@@ -10,8 +10,9 @@ namespace hipsoxr {
 const char *device_bank_ensure(Plan *p, int prec);
 void device_bank_release(Plan *p);
 
-// Engine precision used for an element type: f32 for f32/i16, f64 for f64/i32.
-inline int engine_prec(int elem) { return (elem == HIPSOXR_F32 || elem == HIPSOXR_I16) ? 0 : 1; }
+// Engine precision used for an element type: f32 for f32/i16/f16/bf16, f64 for f64/i32.
+inline bool elem_is_half(int elem) { return elem == HIPSOXR_F16 || elem == HIPSOXR_BF16; }
+inline int engine_prec(int elem) { return (elem == HIPSOXR_F32 || elem == HIPSOXR_I16 || elem_is_half(elem)) ? 0 : 1; }
 inline size_t elem_size(int elem)
 {
     return elem == HIPSOXR_F32 ? 4 : elem == HIPSOXR_F64 ? 8 : elem == HIPSOXR_I32 ? 4 : 2;
@@ -166,8 +167,9 @@ const char *launch_chain_items(Plan *p, int elem, uint32_t n_channels, bool dith
 const char *launch_copy(void *dst, const void *src, size_t bytes, void *stream);
 
 // frequency-domain engine (fft.hip): whole-signal float32 / float64 jobs; int16 / int32 jobs that name it
-// (HIPSOXR_KERNEL_FFT_PCM).  ch0: index of the job's channel 0 in the caller's whole signal (the dither key of jobs
-// folded over channel ranges)
+// (HIPSOXR_KERNEL_FFT_PCM); float16 / bfloat16 jobs where a fused form exists (unit-stride columns, channel pairs: *handled
+// stays false otherwise and launch_job runs half.hip's passes).  ch0: index of the job's channel 0 in the caller's whole
+// signal (the dither key of jobs folded over channel ranges)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &job);
 const char *launch_fft(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled, uint32_t ch0 = 0);
 // Streams on that engine (HIPSOXR_STREAM_FFT, engine.cpp): fft_stream_refusal names what it cannot serve (nullptr: served)
@@ -193,5 +195,10 @@ const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &job, void *stream,
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &job, void *stream);
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &job, void *stream); // hipsoxr_run_device_adjoint_ragged: job.clip_table, one launch
 void adjoint_release(const Plan *p);
+// float16 / bfloat16 jobs that no fused kernel takes (half.hip): one widening pass into stream-ordered float32 temporaries
+// packed in the caller's dimension order, the float32 job of the same selector (adjoint: through launch_adjoint, else
+// launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_job's clip-by-clip loop
+// re-enters with each clip as a plain job).
+const char *launch_half(Plan *p, const hipsoxr_job_t &job, void *stream, bool adjoint);
 
 } // namespace hipsoxr

@@ -453,7 +453,7 @@ uint64_t hipsoxr_plan_out_len(const hipsoxr_plan_t *h, uint64_t in_len)
 hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, void *hip_stream)
 {
     if (!h || !job) return "null argument";
-    if (job->elem < 0 || job->elem > 3) return "invalid element type";
+    if (job->elem < 0 || job->elem > HIPSOXR_BF16) return "invalid element type";
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT)
         return "HIPSOXR_KERNEL_ADJOINT selects the transposed operator: it is valid on hipsoxr_run_device_adjoint only (forward jobs have AUTO, EXACT and the engines' own names)";
     if (job->out_frames < 0 || job->in_frames < 0 || job->out_k0 < 0) return "invalid job extent";

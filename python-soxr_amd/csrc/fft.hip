@@ -26,7 +26,8 @@
 //                   three-pass schedules for the standard audio ratios; unit-stride columns (mono, planar, batches):
 //                   raw buffer loads with the hardware range check, output runs staged through LDS and stored as
 //                   16-byte granules.  float32, float64 and float32-on-float64 instances; int16-on-float32 and
-//                   int32-on-float64 ones (HIPSOXR_KERNEL_FFT_PCM) with the exact engine's output stage in the store loop.
+//                   int32-on-float64 ones (HIPSOXR_KERNEL_FFT_PCM) with the exact engine's output stage in the store loop;
+//                   float16- and bfloat16-on-float32 ones (HIPSOXR_F16 / HIPSOXR_BF16 jobs) with one rounding there.
 //   k_fft_strided2  the same chain for columns with a frame stride: interleaved data paired by channel (CP = true:
 //                   one (Real, Real) word per frame) or strided columns paired by block (CP = false).
 // Build switches: -DFFT2_TRACE (per-wave s_memtime stamps of k_fft_pair2, tools/trace_pair2.py).  The experiments of
@@ -49,6 +50,7 @@
 #endif
 #include "fft_dev.h"
 #include "pcm_out.h"
+#include "half_rules.h"
 
 namespace hipsoxr {
 
@@ -533,8 +535,11 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     C *buf = reinterpret_cast<C *>(smem_raw);
     // integer samples: the run is staged as the arithmetic's own values — up to there the kernel is the float kernel,
     // line for line — and converted on its way out of LDS (the store loop below)
-    constexpr bool PCM = std::is_integral<IO>::value;
-    typedef typename std::conditional<PCM, Real, IO>::type ST;
+    // float16 / bfloat16 samples (HALF; float arithmetic): the same staging — the kernel is the float32 kernel up to the
+    // store loop, which rounds each staged value once to the half type: no dither, no clip count
+    constexpr bool PCM = std::is_integral<IO>::value, HALF = is_half_io<IO>::value, CONV = PCM || HALF;
+    static_assert(!HALF || std::is_same<Real, float>::value, "float16 / bfloat16 samples: float32 arithmetic");
+    typedef typename std::conditional<CONV, Real, IO>::type ST;
     ST *stage = reinterpret_cast<ST *>(smem_raw);
 #ifdef FFT2_TRACE
     unsigned long long *g_tr = a.trace ? a.trace + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (NT / 64) + threadIdx.x / 64) * 16 : nullptr;
@@ -625,7 +630,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     // and ends with the run, so the hardware range check drops what lies beyond the column (and the trips past the
     // run: no trip count, no branches — every LDS read and every store of the thread is in flight at once).  The
     // first granule's sh leading elements belong to the previous run: that one granule goes element by element.
-    if constexpr (!PCM) {
+    if constexpr (!CONV) {
         if (lo != 0) {
             for (int e = lo + (int)threadIdx.x; e < valid; e += NT) ybase[e] = stage[e + sh];
         } else {
@@ -651,7 +656,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     } else {
         // Integer samples: the same granules of the column — EPS staged values (32 bytes of LDS) become one 16-byte store
         // through the exact engine's output stage (pcm_out.h): staged element e is run element e - sh, output
-        // outa + v0 + e - sh of the column.  Only run elements [0, valid) exist: the others are converted like the rest
+        // outa + v0 + e - sh of the column.  float16 / bfloat16 samples: the same walk with a plain cast for the stage.  Only run elements [0, valid) exist: the others are converted like the rest
         // (whatever the LDS holds there), dropped by the range check, and not counted as clips.
         // 2-byte elements: the range check works on whole dwords, so the descriptor ends with the last WHOLE dword of
         // the run and an odd last element goes out by itself — never half a dword more or less than the run.
@@ -665,12 +670,15 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
         const uint32_t dch = ch + a.ch0;
         unsigned nclip = 0;
         auto conv = [&](ST v, int e) -> IO {
-            bool clip;
-            IO r;
-            if constexpr (ES == 2) r = pcm_quantize_i16(v, dither, a.seed, dch, k_run + e, clip);
-            else r = pcm_quantize_i32(v, clip);
-            nclip += (clip && e >= sh + lo && e - sh < valid) ? 1u : 0u; // (only stored elements count)
-            return r;
+            if constexpr (HALF) return (IO)v;
+            else {
+                bool clip;
+                IO r;
+                if constexpr (ES == 2) r = pcm_quantize_i16(v, dither, a.seed, dch, k_run + e, clip);
+                else r = pcm_quantize_i32(v, clip);
+                nclip += (clip && e >= sh + lo && e - sh < valid) ? 1u : 0u; // (only stored elements count)
+                return r;
+            }
         };
         if (lo != 0) { // the pair that holds the job's lower bound: element by element (see `lo`)
             for (int e = lo + (int)threadIdx.x; e < valid; e += NT) ybase[e] = conv(stage[e + sh], e + sh);
@@ -704,7 +712,8 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
                 }
             }
         }
-        if (nclip && a.clip_counter) atomicAdd((unsigned long long *)a.clip_counter, (unsigned long long)nclip);
+        if constexpr (PCM)
+            if (nclip && a.clip_counter) atomicAdd((unsigned long long *)a.clip_counter, (unsigned long long)nclip);
     }
 #ifdef FFT2_TRACE
     if (g_tr && (threadIdx.x & 63) == 0) { // where the wave ran: HW_ID (wave/simd/cu/sh/se fields) and the XCC id
@@ -763,13 +772,14 @@ template <> struct CpIo<double> {
 };
 
 // IO = int16_t (CP only, HIPSOXR_KERNEL_FFT_PCM): the common [frames, 2 c] int16 layout — one aligned 4-byte (l, r) word
-// per frame in, the output stage of pcm_stage on both halves and one 4-byte word out.
+// per frame in, the output stage of pcm_stage on both halves and one 4-byte word out.  IO = _Float16 / __bf16 (CP only,
+// HIPSOXR_F16 / HIPSOXR_BF16 jobs): the same word, under the same alignment rule, each half rounded once.
 template <typename Spec, typename Real, bool CP, typename IO = Real>
 __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 {
     typedef typename PairTabs<Real>::C C;
-    constexpr bool PCM = !std::is_same<IO, Real>::value;
-    static_assert(!PCM || (CP && std::is_same<IO, int16_t>::value && std::is_same<Real, float>::value), "integer samples: int16 channel pairs");
+    constexpr bool PCM = !std::is_same<IO, Real>::value, HALF = is_half_io<IO>::value; // (PCM: a 2-byte sample type on float arithmetic — int16, or HALF)
+    static_assert(!PCM || (CP && (std::is_same<IO, int16_t>::value || HALF) && std::is_same<Real, float>::value), "2-byte samples: int16 / float16 / bfloat16 channel pairs");
     constexpr int ES = (int)sizeof(IO);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     C *cur = reinterpret_cast<C *>(smem_raw);
@@ -816,7 +826,8 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
         Spec::fwd(FFT_STAMP_ARGS cur, PairTabs<Real>::wa(a), [&](int j, int t) -> C {
             if constexpr (PCM) {
                 const unsigned w = __builtin_amdgcn_raw_buffer_load_b32(rs, j * ifb, t * stepb, 0);
-                return C((Real)(int16_t)(w & 0xffffu), (Real)(int16_t)(w >> 16));
+                if constexpr (HALF) return C((Real)__builtin_bit_cast(IO, (uint16_t)(w & 0xffffu)), (Real)__builtin_bit_cast(IO, (uint16_t)(w >> 16)));
+                else return C((Real)(int16_t)(w & 0xffffu), (Real)(int16_t)(w >> 16));
             } else if constexpr (CP) return CpIo<Real>::load(rs, j * ifb, t * stepb);
             else return C(buf_load_real<Real>(rs, j * ifb, t * stepb), buf_load_real<Real>(rs, j * ifb, t * stepb + hop_in * ifb));
         }, last_fwd_store);
@@ -846,7 +857,12 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     Spec::inv(FFT_STAMP_ARGS cur, PairTabs<Real>::wb(a), h_load, [&](int o, int t, C wv) {
         const int n = o + t * (NB / Spec::RB2);
         if (n >= (CP ? vlo : v0) && n < v1) {
-            if constexpr (PCM) {
+            if constexpr (HALF) { // one rounding per half, one 4-byte word out (`v` pinned first, as pcm_stage does)
+                float l = wv.x, r = wv.y;
+                asm("" : "+v"(l));
+                asm("" : "+v"(r));
+                __builtin_amdgcn_raw_buffer_store_b32((unsigned)half_bits<IO>(l) | ((unsigned)half_bits<IO>(r) << 16), ro, (n - v0) * ofb, 0, 0);
+            } else if constexpr (PCM) {
                 const int64_t k = outa + n; // (>= 0: n >= v0); the dither key is the ABSOLUTE index
                 const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, a.out_abs0 + k, k < a.out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, a.out_abs0 + k, k < a.out_frames);
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)l | ((unsigned)r << 16), ro, (n - v0) * ofb, 0, 0);
@@ -871,7 +887,8 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 // path.  build.sh compiles this file three times: -DFFT_PART=0 = everything except the kernels of the schedules listed
 // here (declared extern), -DFFT_PART=1 / =2 = the templates above plus exactly the kernels of one of the two lists, no
 // host code (=3 / =4: the integer-sample kernels of the same lists, =5: the float32-only block sizes of one-round jobs,
-// below).  Without FFT_PART: one piece.
+// below; =6 / =7: the float16 / bfloat16 kernels of the two lists, =8: those of the table's other rows and of the
+// one-round block sizes).  Without FFT_PART: one piece.
 // ---------------------------------------------------------------------------------------------
 #define HIPSOXR_PART1_SPECS(X) X(4096, 2048, 256) X(2048, 4096, 256) X(2048, 1024, 256) X(1024, 2048, 256) X(5376, 1792, 384) X(1792, 5376, 384) X(5376, 3584, 384) X(3584, 5376, 384) X(2688, 896, 384) X(896, 2688, 384) X(2688, 1792, 384) X(1792, 2688, 384) X(5120, 1280, 320) X(1280, 5120, 320) X(5376, 896, 384) X(896, 5376, 384)
 #define HIPSOXR_PART2_SPECS(X) X(7056, 5120, 448) X(5120, 7056, 448) X(4704, 2560, 384) X(2560, 4704, 384) X(5120, 2352, 384) X(2352, 5120, 384) X(7056, 1280, 448) X(1280, 7056, 448) X(5120, 1176, 320) X(1176, 5120, 320) X(3528, 5120, 384) X(5120, 3528, 384) X(4704, 1280, 384) X(1280, 4704, 384) X(3840, 5120, 384) X(5120, 3840, 384)
@@ -889,6 +906,13 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, int16_t>(FftArgs);             \
     HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, double, int32_t>(FftArgs);            \
     HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, true, int16_t>(FftArgs);
+// ... and four more for float16 / bfloat16 samples (HIPSOXR_F16 / HIPSOXR_BF16): units of their own again, FFT_PART=6 / =7,
+// over the same two lists, float arithmetic only
+#define HIPSOXR_INST_HALF(NA, NB, NT)                                                                            \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, _Float16>(FftArgs);            \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, __bf16>(FftArgs);              \
+    HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, true, _Float16>(FftArgs);   \
+    HIPSOXR_EXTERN template __global__ void k_fft_strided2<PairOf<NA, NB, NT>, float, true, __bf16>(FftArgs);
 // ... and ONE for the block sizes that exist for one-round float32 jobs only (48k <-> 44.1k at 14 and 20 periods, see
 // "one-round jobs" below): unit-stride float32 columns, nothing else — a unit of its own, FFT_PART=5, four kernels.
 // Threads: the largest butterfly count of any pass is 294 (2058 = 21*14*7: 98 / 147 / 294; 2240: 140 / 160 / 224) and
@@ -898,6 +922,13 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 #endif
 #define HIPSOXR_PART5_SPECS(X) X(2240, 2058, FFT_ONE_ROUND_NT) X(2058, 2240, FFT_ONE_ROUND_NT) X(3200, 2940, FFT_ONE_ROUND_NT) X(2940, 3200, FFT_ONE_ROUND_NT)
 #define HIPSOXR_INST_F32(NA, NB, NT) HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float>(FftArgs);
+// The rows of the table that are in neither list (their float and integer kernels are instantiated where the table names
+// them, in unit 0): the float16 / bfloat16 forms of those go into unit FFT_PART=8 ...
+#define HIPSOXR_PART8_SPECS(X) X(5120, 4704, 384) X(4704, 5120, 384) X(2560, 2352, 384) X(2352, 2560, 384) X(1280, 1176, 256) X(1176, 1280, 256) X(7056, 2560, 448) X(2560, 7056, 448) X(4410, 1600, 320) X(1600, 4410, 320)
+// ... together with those of the one-round block sizes (a half job takes the row the float32 job takes)
+#define HIPSOXR_INST_F32_HALF(NA, NB, NT)                                                                \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, _Float16>(FftArgs);    \
+    HIPSOXR_EXTERN template __global__ void k_fft_pair2<PairOf<NA, NB, NT>, float, __bf16>(FftArgs);
 #if defined(FFT_PART) && FFT_PART == 0
 #define HIPSOXR_EXTERN extern
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
@@ -905,6 +936,10 @@ HIPSOXR_PART2_SPECS(HIPSOXR_INST)
 HIPSOXR_PART1_SPECS(HIPSOXR_INST_PCM)
 HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
 HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32)
+HIPSOXR_PART1_SPECS(HIPSOXR_INST_HALF)
+HIPSOXR_PART2_SPECS(HIPSOXR_INST_HALF)
+HIPSOXR_PART8_SPECS(HIPSOXR_INST_HALF)
+HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32_HALF)
 #elif defined(FFT_PART) && FFT_PART == 1
 #define HIPSOXR_EXTERN
 HIPSOXR_PART1_SPECS(HIPSOXR_INST)
@@ -920,6 +955,16 @@ HIPSOXR_PART2_SPECS(HIPSOXR_INST_PCM)
 #elif defined(FFT_PART) && FFT_PART == 5
 #define HIPSOXR_EXTERN
 HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32)
+#elif defined(FFT_PART) && FFT_PART == 6
+#define HIPSOXR_EXTERN
+HIPSOXR_PART1_SPECS(HIPSOXR_INST_HALF)
+#elif defined(FFT_PART) && FFT_PART == 7
+#define HIPSOXR_EXTERN
+HIPSOXR_PART2_SPECS(HIPSOXR_INST_HALF)
+#elif defined(FFT_PART) && FFT_PART == 8
+#define HIPSOXR_EXTERN
+HIPSOXR_PART8_SPECS(HIPSOXR_INST_HALF)
+HIPSOXR_PART5_SPECS(HIPSOXR_INST_F32_HALF)
 #endif
 
 #if !defined(FFT_PART) || FFT_PART == 0
@@ -1203,6 +1248,28 @@ static const PairEntry *fft_pairs(int *n)
 #undef HIPSOXR_PAIR
 #undef HIPSOXR_PAIR_F32
 
+// The float16 / bfloat16 forms of a row (HIPSOXR_F16 / HIPSOXR_BF16 jobs; float32 arithmetic): a table of its own, keyed by
+// the row's transform lengths and thread count and written from the instantiation lists — every row that has a `kern2` has
+// both unit-stride forms, every row that has a `kcp` both channel-pair forms (tests/test_half_host.py holds the lists to it).
+struct HalfKernels { int NA, NB; unsigned nt; void (*kern2h)(FftArgs); void (*kern2bf)(FftArgs); void (*kcph)(FftArgs); void (*kcpbf)(FftArgs); };
+#define HIPSOXR_HALF_ROW(NA, NB, NT) \
+    {NA, NB, NT, k_fft_pair2<PairOf<NA, NB, NT>, float, _Float16>, k_fft_pair2<PairOf<NA, NB, NT>, float, __bf16>, \
+     k_fft_strided2<PairOf<NA, NB, NT>, float, true, _Float16>, k_fft_strided2<PairOf<NA, NB, NT>, float, true, __bf16>},
+#define HIPSOXR_HALF_ROW_F32(NA, NB, NT) \
+    {NA, NB, NT, k_fft_pair2<PairOf<NA, NB, NT>, float, _Float16>, k_fft_pair2<PairOf<NA, NB, NT>, float, __bf16>, nullptr, nullptr},
+static const HalfKernels *fft_half_kernels(const PairEntry &e)
+{
+    static const HalfKernels halves[] = {
+        HIPSOXR_PART1_SPECS(HIPSOXR_HALF_ROW) HIPSOXR_PART2_SPECS(HIPSOXR_HALF_ROW) HIPSOXR_PART8_SPECS(HIPSOXR_HALF_ROW)
+        HIPSOXR_PART5_SPECS(HIPSOXR_HALF_ROW_F32)
+    };
+    for (const HalfKernels &h : halves)
+        if (h.NA == e.M * e.k && h.NB == e.L * e.k && h.nt == e.nt) return &h;
+    return nullptr;
+}
+#undef HIPSOXR_HALF_ROW
+#undef HIPSOXR_HALF_ROW_F32
+
 // ---- one-round jobs: block size by per-CU load ------------------------------------------------------------
 // A float32 job of unit-stride columns below the throughput rule's size (a clip of 20 s to a few minutes, a few
 // channels) is ONE round: every workgroup is resident from the start, and the launch ends when the most loaded CU does.
@@ -1255,7 +1322,9 @@ bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &j)
     // what the method neglects is the aliasing of the filter's stop band: only recipes whose stop band
     // is far below the 1e-6 bar qualify (HQ 128 dB, VHQ 177 dB; MQ/LQ at 104 dB do not)
     // (integer samples only by name — HIPSOXR_KERNEL_FFT_PCM: AUTO keeps them on the canonical order, bit for bit)
-    const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32) : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64);
+    // (float16 / bfloat16: wherever the float32 job of the same shape is — they compute in float32)
+    const bool elem_ok = j.kernel == HIPSOXR_KERNEL_FFT_PCM ? (j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32)
+                                                            : (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64 || elem_is_half(j.elem));
     return p.phases == 0 && p.att_db >= 120. && elem_ok && j.in_abs0 == 0 &&
            j.out_k0 == 0 && (uint64_t)j.out_frames <= plan_out_len(p, (uint64_t)j.in_frames);
 }
@@ -1349,7 +1418,8 @@ struct FftJobView {
     // for libsoxr's own VHQ width with HIPSOXR_KERNEL_FFT_F64 (wide32), and int32 samples.  pcm: integer samples
     // (HIPSOXR_KERNEL_FFT_PCM), int16 on float32 and int32 on float64 arithmetic — every size rule is the float job's of
     // that arithmetic width.  kind: the launch log's name of the instance.
-    bool io64, wide32, pcm, pcm32, f64;
+    // half: float16 / bfloat16 samples on float32 arithmetic (bf16: which) — every size rule is the float32 job's.
+    bool io64, wide32, pcm, pcm32, f64, half, bf16;
     const char *kind;
     size_t esz;
 };
@@ -1362,8 +1432,9 @@ static FftJobView fft_job_view(const Plan &p, const hipsoxr_job_t &j, bool windo
     v.cols = (uint64_t)j.n_clips * j.n_channels;
     v.io64 = j.elem == HIPSOXR_F64; v.wide32 = !v.io64 && j.kernel == HIPSOXR_KERNEL_FFT_F64;
     v.pcm = j.elem == HIPSOXR_I16 || j.elem == HIPSOXR_I32; v.pcm32 = j.elem == HIPSOXR_I32;
+    v.half = elem_is_half(j.elem); v.bf16 = j.elem == HIPSOXR_BF16;
     v.f64 = v.io64 || v.wide32 || v.pcm32;
-    v.kind = v.pcm ? (v.pcm32 ? "i32" : "i16") : v.io64 ? "f64" : v.wide32 ? "f32on64" : "f32";
+    v.kind = v.pcm ? (v.pcm32 ? "i32" : "i16") : v.half ? (v.bf16 ? "bf16" : "f16") : v.io64 ? "f64" : v.wide32 ? "f32on64" : "f32";
     v.esz = elem_size(j.elem);
     return v;
 }
@@ -1372,7 +1443,9 @@ static FftJobView fft_job_view(const Plan &p, const hipsoxr_job_t &j, bool windo
 struct FftRow { const PairEntry *use = nullptr; FftGeom g; }; // use == nullptr: no row of the table serves the job
 
 // One-round jobs (see kOneRoundCost): float32 unit-stride columns — exactly the jobs that run `kern2` (v2ok, not f64,
-// not pcm) — as whole signals, where the throughput rule left the large blocks.  Every other element type, layout and the
+// not pcm), and the float16 / bfloat16 jobs that run its half forms: they take the row the float32 job takes, on the
+// float32 cost figures (their own are unmeasured), so that a half job is the float32 job's arithmetic at every size
+// — as whole signals, where the throughput rule left the large blocks.  Every other element type, layout and the
 // stream path keep the size rules' choice `use`; so does this one under HIPSOXR_FFT_LARGE_ONLY / _SMALL_ONLY (they name a
 // block size), and HIPSOXR_FFT_NO_TINY takes k = 8 away.  Ties go to `use`.  HIPSOXR_DEBUG_FFT_K (debug builds): k > 0
 // forces that block size for every such job, whatever its size; k < 0 turns the rule off.
@@ -1384,7 +1457,7 @@ static int fft_one_round_pick(const Plan *p, const hipsoxr_job_t &j, const FftJo
     const bool plain_cols = j.in_frame_stride == 1 && j.out_frame_stride == 1 &&
                             (j.n_channels == 1 || j.in_chan_stride != 1 || j.out_chan_stride != 1); // (=> no XCD map, no channel pairs)
     const int force_k1 = switches().dbg_fft_k;
-    if (!((!use_is_big || force_k1 > 0) && plain_cols && j.elem == HIPSOXR_F32 && !v.wide32 && !v.window && force_k1 >= 0 &&
+    if (!((!use_is_big || force_k1 > 0) && plain_cols && (j.elem == HIPSOXR_F32 || v.half) && !v.wide32 && !v.window && force_k1 >= 0 &&
           ((!switches().fft_large_only && !switches().fft_small_only) || force_k1 > 0)))
         return -1;
     // a candidate's cost; < 0: not a candidate (no figures, no such block, or not co-resident on this device)
@@ -1497,8 +1570,8 @@ static const char *fft_layout(const hipsoxr_job_t &j, const FftJobView &v, const
     // interleaved data with an even channel count: pair channels (one (Real, Real) word per frame)
     const bool cp_layout = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && !sw.fft_no_chpair;
     // ... when a block's byte offsets fit the kernel's 32-bit operands (buffer loads: element alignment is enough)
-    // (int16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
-    const bool cp_pcm_ok = !v.pcm || (!v.pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
+    // (int16 / float16 / bfloat16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
+    const bool cp_pcm_ok = !(v.pcm || v.half) || (!v.pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
                                       ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0);
     const int64_t fstride = std::max(j.in_frame_stride, j.out_frame_stride);
     const bool cp2 = !v.wide32 && cp_pcm_ok && fft_offsets_fit(g, 1, fstride, v.esz);
@@ -1518,11 +1591,11 @@ static const char *fft_layout(const hipsoxr_job_t &j, const FftJobView &v, const
     if (y.chpair && !y.xcd_map) return "internal: channel pairing needs the XCD map"; // (cannot happen: cp_map_ok above)
     y.grid = y.xcd_map ? dim3((unsigned)(items8 * y.units), j.n_clips, 1) : dim3((unsigned)((y.n_blocks + 1) / 2), (unsigned)v.cols, 1);
     // (integer samples are staged as the arithmetic's values, up to 7 elements into the run's first granule)
-    const size_t stage_bytes = v.pcm ? 2 * (size_t)g.hop_out * (v.f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * v.esz + 16;
+    const size_t stage_bytes = (v.pcm || v.half) ? 2 * (size_t)g.hop_out * (v.f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * v.esz + 16;
     y.v2ok = !y.xcd_map && !y.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 && stage_bytes <= y.lds;
     y.cp2ok = y.chpair && y.xcd_map && cp2;
     // ... when the byte offsets of a PAIR of blocks fit the 32-bit operands
-    y.st2ok = !v.wide32 && !v.pcm && !y.chpair && !y.v2ok && fft_offsets_fit(g, 2, fstride, v.esz);
+    y.st2ok = !v.wide32 && !v.pcm && !v.half && !y.chpair && !y.v2ok && fft_offsets_fit(g, 2, fstride, v.esz);
     *out = y;
     return nullptr;
 }
@@ -1596,7 +1669,7 @@ static const char *fft_trace_dump(const FftArgs &, size_t, void *) { return null
 static const char *fft_try_wave(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, const FftLayout &lay, FftArgs a, void *stream, bool *handled)
 {
     FftWaveKernel wk;
-    if (!(lay.v2ok && !v.f64 && !v.pcm && !v.window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk))) return nullptr;
+    if (!(lay.v2ok && !v.f64 && !v.pcm && !v.half && !v.window && a.in_lo <= 0 && !switches().fft_no_wave && fft_wave_pick(p->L, p->M, &wk))) return nullptr;
     // (the job size first, from the kernel's own constants: its geometry — a host DFT of the filter and two
     //  device allocations — is built only for a job that can take it; 48k -> 44.1k never does)
     const int64_t pairs_w = ((j.out_frames + wk.hop - 1) / wk.hop + 1) / 2;
@@ -1616,8 +1689,10 @@ static const char *fft_try_wave(Plan *p, const hipsoxr_job_t &j, const FftJobVie
 static const char *fft_launch_paired(const PairEntry &e, const FftGeom &g, const FftJobView &v, const FftLayout &lay, FftArgs a, void *stream, bool *handled)
 {
     void (*kern)(FftArgs) = nullptr;
-    if (lay.v2ok) kern = v.pcm ? (v.pcm32 ? e.kern2i32 : e.kern2i16) : v.io64 ? e.kern2d : v.wide32 ? e.kern2fd : e.kern2;
-    else kern = v.pcm ? e.kcpi16 : lay.cp2ok ? (v.f64 ? e.kcpd : e.kcp) : (v.f64 ? e.kstd : e.kst); // (pcm: cp2ok — st2ok wants floats)
+    const HalfKernels *hk = v.half ? fft_half_kernels(e) : nullptr;
+    if (v.half && !hk) return "internal: a row of the schedule table has no float16 / bfloat16 kernels"; // (cannot happen: the instantiation lists cover the table)
+    if (lay.v2ok) kern = v.pcm ? (v.pcm32 ? e.kern2i32 : e.kern2i16) : v.half ? (v.bf16 ? hk->kern2bf : hk->kern2h) : v.io64 ? e.kern2d : v.wide32 ? e.kern2fd : e.kern2;
+    else kern = v.pcm ? e.kcpi16 : v.half ? (v.bf16 ? hk->kcpbf : hk->kcph) : lay.cp2ok ? (v.f64 ? e.kcpd : e.kcp) : (v.f64 ? e.kstd : e.kst); // (pcm: cp2ok — st2ok wants floats)
     if (!kern) return "internal: a float32-only block size was chosen for another kind of job"; // (cannot happen: plain_cols of fft_one_round_pick)
     if (const char *err = ensure_dyn_lds((const void *)kern, lay.lds)) return err;
     size_t trace_n = 0;
@@ -1643,13 +1718,15 @@ static const char *fft_launch_row(Plan *p, const hipsoxr_job_t &j, const FftJobV
     if (*handled) return nullptr;
     if (!lay.v2ok && !lay.cp2ok && !lay.st2ok) return nullptr;
     if (j.clip_table && !lay.v2ok) return nullptr; // ragged batches: the unit-stride kernel reads its clip's row; nothing else does
+    // float16 / bfloat16: the fused forms alone (half_rules.h) — what they do not take is the widening pass's, not an error
+    if (v.half && half_fused_form(true, lay.v2ok, lay.cp2ok, j.clip_table != nullptr) == kHalfNone) return nullptr;
     return fft_launch_paired(*row.use, row.g, v, lay, a, stream, handled);
 }
 
 // General path: one block per workgroup — float32 whole signals of any 7-smooth plan, no ragged batches
 static const char *fft_launch_block(Plan *p, const hipsoxr_job_t &j, const FftJobView &v, void *stream, bool *handled)
 {
-    if (v.f64 || v.pcm || j.clip_table || v.window) return nullptr;
+    if (v.f64 || v.pcm || v.half || j.clip_table || v.window) return nullptr;
     FftGeom g;
     if (const char *err = fft_geom_cached(p, 0, 0, &g)) return err;
     if (g.ok) {

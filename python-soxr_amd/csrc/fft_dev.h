@@ -350,6 +350,20 @@ template <> __device__ __forceinline__ int32_t buf_load_real<int32_t>(__amdgpu_b
 {
     return (int32_t)__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, FFT_LOAD_AUX);
 }
+// float16 / bfloat16 samples (HIPSOXR_F16 / HIPSOXR_BF16): int16's width and int16's loads — one element per 2-byte load,
+// any even address, the range check zero-extends — the bits taken as the half type; the caller's (float) widens exactly
+template <> __device__ __forceinline__ _Float16 buf_load_real<_Float16>(__amdgpu_buffer_rsrc_t r, int voff, int soff)
+{
+    return __builtin_bit_cast(_Float16, (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, FFT_LOAD_AUX));
+}
+template <> __device__ __forceinline__ __bf16 buf_load_real<__bf16>(__amdgpu_buffer_rsrc_t r, int voff, int soff)
+{
+    return __builtin_bit_cast(__bf16, (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(r, voff, soff, FFT_LOAD_AUX));
+}
+// ... and the one conversion on the way out: a plain cast — v_cvt_f16_f32 / v_cvt_pk_bf16_f32 on gfx950, round to nearest
+// even, NaN stays NaN, beyond the type's range +-inf — as its bits
+template <typename H> __device__ __forceinline__ uint16_t half_bits(float v) { return __builtin_bit_cast(uint16_t, (H)v); }
+template <typename T> struct is_half_io { static constexpr bool value = std::is_same<T, _Float16>::value || std::is_same<T, __bf16>::value; };
 __device__ __forceinline__ void buf_store_real(float v, __amdgpu_buffer_rsrc_t r, int voff)
 {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, 0, 0);
@@ -376,5 +390,7 @@ template <> struct PairTabs<double> {
 // (element types that are I/O only: the 16-byte granule of the staged output run)
 template <> struct PairTabs<int16_t> { typedef v4u_t V16; };
 template <> struct PairTabs<int32_t> { typedef v4u_t V16; };
+template <> struct PairTabs<_Float16> { typedef v4u_t V16; };
+template <> struct PairTabs<__bf16> { typedef v4u_t V16; };
 
 } // namespace hipsoxr

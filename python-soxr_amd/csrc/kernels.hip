@@ -61,6 +61,7 @@
 #include <vector>
 
 #include "device.h"
+#include "half_rules.h"
 #include "pcm_out.h"
 #include "ragged_rules.h"
 #include "tile_rules.h"
@@ -1622,6 +1623,16 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
     const bool want_pcm = j.kernel == HIPSOXR_KERNEL_FFT_PCM;
     if (want_pcm)
         if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
+    // float16 / bfloat16 samples: device jobs in float32 arithmetic — fused into the frequency-domain engine's paired kernels
+    // where the float32 job of the shape runs them, else a widening pass, the float32 job and a narrowing pass (half.hip)
+    const bool half = elem_is_half(j.elem);
+    if (half) {
+        if (vr || res) return "float16 / bfloat16 samples: device jobs only (streams take float32, float64, int32 and int16)";
+        if (j.kernel == HIPSOXR_KERNEL_FFT_F64)
+            return "HIPSOXR_KERNEL_FFT_F64 serves float32 / float64 jobs (float16 / bfloat16 jobs compute in float32: HIPSOXR_KERNEL_FFT)";
+        if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT)
+            return "HIPSOXR_KERNEL_WAVE_DOT serves float32, float64, int32 and int16 jobs (float16 / bfloat16 jobs are not served by the reference-point kernel)";
+    }
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
     // (the kernel reads its clip's row), else — float clips of an interpolated-phase plan under AUTO with unit frame strides —
     // the two-stage form over the table, else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
@@ -1669,8 +1680,9 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
         }
         // the exact engine: one launch of a kernel's RAGGED form (launch_ragged); what that does not serve — float clips of an
         // interpolated-phase plan under AUTO on other layouts (interleaved channels: the two-stage form's, clip by clip), the
-        // wave-dot kernel — clip by clip
-        {
+        // wave-dot kernel — clip by clip.  float16 / bfloat16 clips the fused launch above did not take: clip by clip too, each
+        // re-entering as a plain half job (the elements between packed clips are never written)
+        if (!half) {
             bool handled = false;
             if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;
             if (handled) return nullptr;
@@ -1688,6 +1700,20 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             if (const char *e = launch_job(p, one, stream)) return e;
         }
         return nullptr;
+    }
+    if (half) {
+        // fused (half_rules.h): the frequency-domain engine by name, or AUTO under the float rule (2^13 outputs in all), on
+        // a whole-signal job of an HQ / VHQ exact-ratio plan — launch_fft then takes it on the row the float32 job takes,
+        // or leaves it (*handled == false: no fused form for the layout or the ratio)
+        const HalfSelector sel = j.kernel == HIPSOXR_KERNEL_FFT ? kHalfSelFft : j.kernel == HIPSOXR_KERNEL_AUTO ? kHalfSelAuto : kHalfSelOther;
+        const int64_t total_out = (int64_t)j.out_frames * j.n_clips * j.n_channels;
+        if (half_try_fused(sel, total_out, switches().no_fft, fft_job_eligible(*p, j), cols)) {
+            if (const char *e = device_bank_ensure(p, 0)) return e;
+            bool handled = false;
+            if (const char *e = launch_fft(p, j, stream, &handled)) return e;
+            if (handled) return nullptr;
+        }
+        return launch_half(p, j, stream, false); // (the float32 job inside refuses what a float32 job is refused)
     }
     // Kernels index (clip, channel) columns through grid.y (<= 65535).  Wider jobs — the Python surface
     // admits 65536 channels like the reference, src/soxr/__init__.py:22 — are folded into several

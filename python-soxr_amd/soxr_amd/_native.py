@@ -52,6 +52,7 @@ lib = C.CDLL(LIB_PATH)
 # datatypes (libsoxr numbering)
 FLOAT32_I, FLOAT64_I, INT32_I, INT16_I, FLOAT32_S, FLOAT64_S, INT32_S, INT16_S = range(8)
 F32, F64, I32, I16 = range(4)
+F16, BF16 = 4, 5  # hipsoxr_elem_t of DEVICE JOBS only: a stream's io type has no such member (4 and 5 are its split float layouts)
 QQ, LQ, MQ, HQ, VHQ = 0, 1, 2, 4, 6
 VR = 32
 NO_DITHER = 8

@@ -145,15 +145,26 @@ _TORCH_ELEM = None
 
 
 def _torch_elem(dtype):
+    """Element type of a device JOB (resample_tensor, PreparedJob, RaggedJob, the adjoint): the four stream types and
+    float16 / bfloat16."""
     global _TORCH_ELEM
     import torch
     if _TORCH_ELEM is None:
         _TORCH_ELEM = {torch.float32: _n.F32, torch.float64: _n.F64, torch.int32: _n.I32,
-                       torch.int16: _n.I16}
+                       torch.int16: _n.I16, torch.float16: _n.F16, torch.bfloat16: _n.BF16}
     try:
         return _TORCH_ELEM[dtype]
     except KeyError:
-        raise TypeError(f"Data type must be one of [float32, float64, int16, int32], not {dtype}")
+        raise TypeError(f"Data type must be one of [float32, float64, int16, int32, float16, bfloat16], not {dtype}")
+
+
+def _torch_stream_elem(dtype):
+    """Element type of a STREAM (TensorStream, TensorStreamGroup): the io types libsoxr's streams have — no half types."""
+    elem = _torch_elem(dtype)
+    if elem in (_n.F16, _n.BF16):
+        raise TypeError("Data type must be one of [float32, float64, int16, int32, float16, bfloat16] for device jobs; "
+                        f"streams take four of them, [float32, float64, int16, int32], not {dtype}")
+    return elem
 
 
 def _as3(t):
@@ -195,7 +206,8 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO
     rates) the gather-form adjoint on the plan's interpolation table, whose coefficients are the very bits the forward
     with kernel=KERNEL_EXACT multiplies by.  There a non-finite gy[k] reaches exactly the frames of its true support.
     Ragged batches: `dist.resample_ragged_adjoint` / `dist.resample_ragged`.  The two-stage form's adjoint, variable
-    rate, streams and integer types are not served."""
+    rate, streams and integer types are not served.  float16 / bfloat16 cotangents: the float32 adjoint on `gy.float()`,
+    rounded once (every selector above; not the ragged entry)."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch
@@ -272,6 +284,11 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     clip_counter = a one-element int64 / uint64 device tensor that counts saturated outputs.  AUTO keeps them on the
     canonical-order engine; kernel=KERNEL_FFT_PCM asks for the frequency-domain engine (int16 in float32, int32 in
     float64 arithmetic, the same output stage: within 1 LSB of the canonical order, not bit-identical to it).
+    float16 / bfloat16 tensors: the result has the input's type and is, bit for bit, the float32 job of the same `kernel`
+    on `x.float()` rounded once to nearest even (`.to(x.dtype)`: NaN, +-inf, overflow to +-inf and float16 subnormals
+    included) — fused into the frequency-domain engine's kernels for unit-stride columns and interleaved channel pairs of the
+    tabled ratios (by name, or AUTO from 2^13 outputs in all), a widening and a narrowing pass around the float32 job
+    otherwise.  KERNEL_FFT_PCM, KERNEL_FFT_F64 and KERNEL_WAVE_DOT refuse them; dither / clip_counter are ignored.
 
     Differentiable: when x.requires_grad (and grad mode is on) the result carries a grad_fn whose backward is the
     transposed operator (`resample_tensor_adjoint`), so gradients — and gradients of gradients — flow through a
@@ -371,7 +388,7 @@ class TensorStream:
         self.engine = engine
         self.channels = int(num_channels)
         self.dtype = torch.float32 if dtype is None else dtype
-        self._elem = _torch_elem(self.dtype)
+        self._elem = _torch_stream_elem(self.dtype)
         self._ratio = float(out_rate) / float(in_rate)
         self._h = _C.c_void_p()
         flags = (_n.VR if vr else 0) | (0 if dither else _n.NO_DITHER) | (_n.STREAM_FFT if engine == "fft" else 0)

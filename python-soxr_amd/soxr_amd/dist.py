@@ -686,6 +686,8 @@ def resample_batch(clips, in_rate, out_rate, quality="VHQ", devices=None, kernel
                 c0 = clips[host[0]]
                 ch = 1 if c0.ndim == 1 else c0.shape[1]
                 tdt = torch.from_numpy(np.empty(0, c0.dtype)).dtype
+                if tdt in (torch.float16, torch.bfloat16):  # (half samples are a DEVICE-tensor type: the host surface stays refused)
+                    raise TypeError(f"Data type must be one of [float32, float64, int16, int32] for host arrays, not {c0.dtype}")
                 key = (d, tdt, ch, int(kernel), int(block_bytes), bool(pinned_results))
                 pipe = _checkout_pipe(key, lambda: _HostPipe(plan, dev_t, tdt, ch, kernel, block_bytes, bool(pinned_results)))
                 pipe.plan = plan
