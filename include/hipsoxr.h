@@ -238,17 +238,26 @@ typedef struct {
      * (~10 us); a device copy supplied by the caller (a prepared job launched many times) is used as it is and must
      * equal the host table — it is not checked.  in_frames / out_frames of the job are then the LARGEST per-clip
      * values.  Whole signals only (in_abs0 == 0, out_k0 == 0).  Unit-stride float columns go out as one launch of
-     * the frequency-domain engine (AUTO: from 2^13 output samples in all, as for equal-length jobs).  Everything else on
+     * the frequency-domain engine (AUTO: from 2^13 output samples in all, as for equal-length jobs).  Interleaved and
+     * strided clips (frame strides other than 1: [frames, channels] tensors, channel slices) are one launch of that
+     * engine BY NAME — HIPSOXR_KERNEL_FFT on float32 / float64 (channel pairs for even channel counts, single strided
+     * columns otherwise; at most 65535 clips per launch of the paired form), HIPSOXR_KERNEL_FFT_PCM on int16 with an even
+     * channel count whose rows' two offsets are even (one aligned 4-byte word per frame and channel pair; the dither key is
+     * the output index within the clip) — while HIPSOXR_KERNEL_AUTO keeps such tables on the exact engine, bit for bit.
+     * Still refused by name: HIPSOXR_KERNEL_FFT_F64 on strided float32 data, int32 channel pairs, int16 with an odd channel
+     * count or at an odd offset, ratios outside the schedule table; float16 / bfloat16 interleaved tables run clip by clip.
+     * Everything else on
      * an exact-bank plan is ONE launch of the exact engine too: int16 / int32 under the default selector, interleaved
-     * or float64 clips, small jobs, HIPSOXR_KERNEL_EXACT and the tile / gather selectors — the kernel reads its clip's
+     * or float64 clips under AUTO, small jobs, HIPSOXR_KERNEL_EXACT and the tile / gather selectors — the kernel reads its clip's
      * row, the grid is the longest clip's (more than 65535 columns: one launch per range of clips).  Each clip has the
      * bits of the clip run alone; out[0, out_frames[c]) of every clip is written and nothing else, not the elements
      * between packed clips either; clip_counter receives the sum over the clips.  An interpolated-phase plan (an
      * arbitrary ratio) is ONE launch in the same way — int16 / int32 under the default selector, every type under
      * HIPSOXR_KERNEL_EXACT / HIPSOXR_KERNEL_GATHER — on the ragged forms of its own kernels, each clip with the bits of
      * the clip run alone.  float32 / float64 clips of such a plan under HIPSOXR_KERNEL_AUTO belong to the two-stage
-     * form (another precision class), and a table with in_frame_stride == out_frame_stride == 1 (mono clips, planar
-     * channels at any channel stride) is a CONSTANT number of launches whatever the number of clips: the table is
+     * form (another precision class), and a table at any positive frame stride (mono clips, planar channels at any
+     * channel stride, interleaved [frames, channels] clips, channel slices) is a CONSTANT number of launches whatever the
+     * number of clips: the table is
      * partitioned by the question asked of each clip alone — a clip of 8192 frames or more on both sides that the form
      * admits runs the two-stage form, every other non-empty clip the exact engine, so engine choice per clip does not
      * depend on the table — into one ragged polyphase launch and one ragged FFT-stage launch over the (clip, channel)
@@ -259,8 +268,9 @@ typedef struct {
      * mono float32 clip alone takes another kernel form of the polyphase stage: other rounding, same class); the short
      * clips ARE bit-equal to the clip alone.  The inner launches read tables the library derives (columns, offsets into the
      * intermediate; one upload per call), so clip_table_dev cannot serve this path and is not read by it.
-     * Served clip by clip from the same call, same results: such float clips with interleaved channels (frame strides
-     * other than 1: the ragged FFT kernels have no strided form), HIPSOXR_KERNEL_WAVE_DOT, and a table with a clip of more
+     * With a frame stride other than 1 both stages run one column per (clip, channel) at the caller's stride on the
+     * caller's side (the intermediate stays library-owned and unit-stride); the results are in the same class.
+     * Served clip by clip from the same call, same results: HIPSOXR_KERNEL_WAVE_DOT, and a table with a clip of more
      * than 2^30 outputs.  HIPSOXR_KERNEL_FFT / _FFT_F64 on a table of an interpolated-phase plan stay refused. */
     const int64_t *clip_table;
     const int64_t *clip_table_dev;

@@ -181,7 +181,7 @@ const char *launch_fft_window(Plan *p, const hipsoxr_job_t &job, void *stream, b
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
-// ... on a clip table (job.clip_table, validated by launch_job; float32 / float64, HIPSOXR_KERNEL_AUTO, unit frame strides):
+// ... on a clip table (job.clip_table, validated by launch_job; float32 / float64, HIPSOXR_KERNEL_AUTO, any positive frame stride):
 // a constant number of launches — per range of columns one ragged polyphase launch and one ragged FFT-stage launch, plus
 // one launch_ragged_short for the clips the two-stage form does not admit.  *handled = false: not a table this path serves,
 // or the FFT stage declined — the caller's clip-by-clip loop computes every clip.

@@ -51,6 +51,7 @@
 #include "fft_dev.h"
 #include "pcm_out.h"
 #include "half_rules.h"
+#include "fft_ragged_rules.h"
 
 namespace hipsoxr {
 
@@ -748,6 +749,11 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_pair2(FftArgs a)
 // item = xcd * ceil(items / 8) + chunk).  Without it each line is fetched and (partially) written once per channel unit: 2.3x / 4x
 // the algorithmic bytes at 8 channels.  (The derived indices need readfirstlane: a run-time integer division goes
 // through the vector ALU, and the compiler then keeps every address in VGPRs.)
+// RAGGED batches (a.clip_tab != nullptr, a wave-uniform run-time test as in k_fft_pair2: no further instances): a workgroup
+// takes its clip's place and lengths from its row of the table instead of clip * a.ics, clip * a.ocs, a.in_frames and
+// a.out_frames; a.in_lo and a.out_lo stay job-wide.  Both descriptors end at the clip's OWN last frame — the hardware range
+// check zero-extends past it and drops the stores behind it — and the dither key is the output index within the clip.
+// The grid is the longest clip's; the work-item map (fft_ragged_rules.h) runs on the clip's own item count.
 // ---------------------------------------------------------------------------------------------
 template <typename Real> struct CpIo;
 template <> struct CpIo<float> {
@@ -792,21 +798,32 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     // XCD-aware ids: x = 8 * slot + xcd, slot = chunk * units + unit;
     // or (a.xcd_map == 0: one column per grid row) items along x, columns along y
     const uint32_t units = CP ? a.n_channels / 2 : a.n_channels;
-    const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
     const bool xm = a.xcd_map != 0;
-    const uint32_t cu = __builtin_amdgcn_readfirstlane(xm ? slot % units : blockIdx.y % units);
     const uint32_t clip = __builtin_amdgcn_readfirstlane(xm ? blockIdx.y : blockIdx.y / units);
+    // ragged batch: this clip's own place and lengths — the row convention of pair2_item: {in offset, END of the column as
+    // an absolute sample index, out offset, out frames}; four scalar loads at a wave-uniform address — and its own item
+    // count (one division per workgroup; the vector ALU does it, so the result goes back to the scalar side)
+    int64_t clip_in = (int64_t)clip * a.ics, clip_out = (int64_t)clip * a.ocs, in_frames = a.in_frames, out_frames = a.out_frames;
+    int64_t items = a.pairs_per_col;
+    if (a.clip_tab) {
+        const int64_t *row = a.clip_tab + 4 * (size_t)clip;
+        clip_in = row[0]; in_frames = row[1]; clip_out = row[2]; out_frames = row[3];
+        items = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)fft_clip_items(out_frames, a.hop_out, CP));
+    }
     // ... and each XCD takes a CONTIGUOUS run of the column's blocks (item = xcd * per_xcd + chunk), so that the input two
     // neighbouring blocks share — 17.7 % of a 4410-frame block at 44.1k -> 16k — meets in ONE L2 instead of being fetched
     // from HBM by two (round 4; with item = 8 * chunk + xcd every XCD saw blocks b, b + 8, b + 16 ...: configs[2] HBM
     // traffic 137.3 MB = 1.19x the algorithmic bytes -> 116.0 MB = 1.005x, launch time unchanged: tools/c2_traffic.sh)
-    const uint32_t per_xcd = (uint32_t)((a.pairs_per_col + 7) / 8);
-    const int64_t bx = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(xm ? xcd * per_xcd + slot / units : blockIdx.x);
-    if (xm && slot / units >= per_xcd) return;
-    if (bx >= a.pairs_per_col) return; // grid.x is padded to a multiple of 8 items per unit
+    // The map itself is fft_ragged_rules.h (the CPU checks it): grid.x is the longest clip's, padded to a multiple of 8
+    // items per unit; an id that is padding, or at or behind this clip's last item, leaves here — before the first
+    // barrier, on the id and the row alone
+    const FftMapItem mi = xm ? fft_xcd_map(blockIdx.x, units, items) : fft_plain_map(blockIdx.x, blockIdx.y, units, items);
+    if (!__builtin_amdgcn_readfirstlane((int)mi.live)) return;
+    const uint32_t cu = __builtin_amdgcn_readfirstlane(mi.unit);
+    const int64_t bx = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane(mi.item);
     const uint32_t ch = CP ? 2 * cu : cu;
     const int32_t hop_in = (int32_t)(a.hop_periods * a.M), hop_out = a.hop_out;
-    const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
+    const IO *xin = (const IO *)a.in + clip_in + (int64_t)ch * a.ichs;
     const int32_t ifb = (int32_t)a.ifs * ES, ofb = (int32_t)a.ofs * ES; // bytes per frame (launcher: 2 N * frame < 2^30)
     auto last_fwd_store = [&](int o, int t, C v) { cur[o + t * (NA / Spec::RA2)] = v; };
     const int32_t v0 = a.v0, v1 = a.v0 + hop_out;
@@ -819,7 +836,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
 
     // ---- forward: z[n] = x_c[n] + i x_{c+1}[n]  (CP)  or  x_a[n] + i x_b[n]  (two blocks), first pass straight from HBM
     if (ina >= a.in_lo) {
-        const int64_t left = (a.in_frames - ina) * (int64_t)ifb; // bytes from the block's first frame to the end of the column
+        const int64_t left = (in_frames - ina) * (int64_t)ifb; // bytes from the block's first frame to the end of the column
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             uniform_ptr((void *)(xin + ina * a.ifs)), 0, __builtin_amdgcn_readfirstlane((int)(left < 0 ? 0 : left > 0x40000000 ? 0x40000000 : left)), 0x00020000);
         const int32_t stepb = nbA * ifb; // one butterfly input further: N/R0 frames
@@ -836,10 +853,10 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
             const int64_t l = ina + j + t * nbA, lb = l + hop_in;
             if constexpr (CP) {
                 C v = C((Real)0, (Real)0);
-                if (l >= a.in_lo && l < a.in_frames) v = C((Real)xin[l * a.ifs], (Real)xin[l * a.ifs + 1]);
+                if (l >= a.in_lo && l < in_frames) v = C((Real)xin[l * a.ifs], (Real)xin[l * a.ifs + 1]);
                 return v;
             } else {
-                return C((l >= a.in_lo && l < a.in_frames) ? xin[l * a.ifs] : (Real)0, (lb >= a.in_lo && lb < a.in_frames) ? xin[lb * a.ifs] : (Real)0);
+                return C((l >= a.in_lo && l < in_frames) ? xin[l * a.ifs] : (Real)0, (lb >= a.in_lo && lb < in_frames) ? xin[lb * a.ifs] : (Real)0);
             }
         }, last_fwd_store);
     }
@@ -847,8 +864,8 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
     FFT_STAMP();
 
     // ---- inverse (see k_fft_pair2), outputs straight to HBM -----------------------------------------
-    IO *ybase = (IO *)a.out + (int64_t)clip * a.ocs + (int64_t)ch * a.ochs + (outa + v0) * a.ofs; // outa + v0 >= 0
-    const int64_t oleft = (a.out_frames - (outa + v0)) * (int64_t)ofb;
+    IO *ybase = (IO *)a.out + clip_out + (int64_t)ch * a.ochs + (outa + v0) * a.ofs; // outa + v0 >= 0
+    const int64_t oleft = (out_frames - (outa + v0)) * (int64_t)ofb;
     const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
         uniform_ptr((void *)ybase), 0, __builtin_amdgcn_readfirstlane((int)(oleft < 0 ? 0 : oleft > 0x40000000 ? 0x40000000 : oleft)), 0x00020000);
     const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((void *)PairTabs<Real>::hr(a)), 0,
@@ -864,7 +881,7 @@ __global__ void __launch_bounds__(Spec::NT) k_fft_strided2(FftArgs a)
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)half_bits<IO>(l) | ((unsigned)half_bits<IO>(r) << 16), ro, (n - v0) * ofb, 0, 0);
             } else if constexpr (PCM) {
                 const int64_t k = outa + n; // (>= 0: n >= v0); the dither key is the ABSOLUTE index
-                const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, a.out_abs0 + k, k < a.out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, a.out_abs0 + k, k < a.out_frames);
+                const uint16_t l = (uint16_t)pcm_stage<IO>(wv.x, a, ch, a.out_abs0 + k, k < out_frames), r = (uint16_t)pcm_stage<IO>(wv.y, a, ch + 1, a.out_abs0 + k, k < out_frames);
                 __builtin_amdgcn_raw_buffer_store_b32((unsigned)l | ((unsigned)r << 16), ro, (n - v0) * ofb, 0, 0);
             } else if constexpr (CP) {
                 CpIo<Real>::store(wv, ro, (n - v0) * ofb); // frame outa + n holds (y_c, y_{c+1})
@@ -1572,13 +1589,15 @@ static const char *fft_layout(const hipsoxr_job_t &j, const FftJobView &v, const
     // ... when a block's byte offsets fit the kernel's 32-bit operands (buffer loads: element alignment is enough)
     // (int16 / float16 / bfloat16: the (l, r) word is ONE 4-byte access — every pair of every frame of every clip must be 4-byte aligned)
     const bool cp_pcm_ok = !(v.pcm || v.half) || (!v.pcm32 && (((uintptr_t)j.in | (uintptr_t)j.out) & 3) == 0 &&
-                                      ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0);
+                                      ((j.in_frame_stride | j.out_frame_stride | (j.n_clips > 1 ? j.in_clip_stride | j.out_clip_stride : 0)) & 1) == 0 &&
+                                      // (a clip table: the clips lie at their rows' offsets — both even, fft_ragged_rules.h)
+                                      (!j.clip_table || fft_table_words_aligned(j.clip_table, j.n_clips)));
     const int64_t fstride = std::max(j.in_frame_stride, j.out_frame_stride);
     const bool cp2 = !v.wide32 && cp_pcm_ok && fft_offsets_fit(g, 1, fstride, v.esz);
     // (channel pairing rides on the XCD-aware work-item map: decided together, so that a job without the
     //  map — HIPSOXR_FFT_NO_XCD_MAP, or too many work items — runs unpaired on the strided kernel instead of failing)
     const int64_t cp_items8 = (y.n_blocks + 7) / 8 * 8;
-    const bool cp_map_ok = j.n_channels > 1 && j.n_clips <= 65535 && cp_items8 * (int64_t)(j.n_channels / 2) <= 2147483647LL && !sw.fft_no_xcd_map;
+    const bool cp_map_ok = j.n_channels > 1 && fft_map_clips_ok(j.n_clips) && cp_items8 * (int64_t)(j.n_channels / 2) <= 2147483647LL && !sw.fft_no_xcd_map;
     y.chpair = (cp_layout && cp_map_ok && cp2) ? 1 : 0;
     y.lds = std::max((size_t)std::max(g.N_in, g.N_out) * (v.f64 ? sizeof(double2) : sizeof(float2)), sw.dbg_fft_lds);
     *out = y;
@@ -1586,10 +1605,10 @@ static const char *fft_layout(const hipsoxr_job_t &j, const FftJobView &v, const
     y.items = y.chpair ? y.n_blocks : (y.n_blocks + 1) / 2;
     const int64_t items8 = (y.items + 7) / 8 * 8;
     y.units = y.chpair ? j.n_channels / 2 : j.n_channels;
-    y.xcd_map = (j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && j.n_clips <= 65535 &&
+    y.xcd_map = (j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1 && fft_map_clips_ok(j.n_clips) &&
                  items8 * y.units <= 2147483647LL && !sw.fft_no_xcd_map) ? 1 : 0;
     if (y.chpair && !y.xcd_map) return "internal: channel pairing needs the XCD map"; // (cannot happen: cp_map_ok above)
-    y.grid = y.xcd_map ? dim3((unsigned)(items8 * y.units), j.n_clips, 1) : dim3((unsigned)((y.n_blocks + 1) / 2), (unsigned)v.cols, 1);
+    y.grid = y.xcd_map ? dim3((unsigned)fft_xcd_grid_x(y.items, y.units), j.n_clips, 1) : dim3((unsigned)((y.n_blocks + 1) / 2), (unsigned)v.cols, 1);
     // (integer samples are staged as the arithmetic's values, up to 7 elements into the run's first granule)
     const size_t stage_bytes = (v.pcm || v.half) ? 2 * (size_t)g.hop_out * (v.f64 ? sizeof(double) : sizeof(float)) + 32 : 2 * (size_t)g.hop_out * v.esz + 16;
     y.v2ok = !y.xcd_map && !y.chpair && j.in_frame_stride == 1 && j.out_frame_stride == 1 && stage_bytes <= y.lds;
@@ -1717,7 +1736,9 @@ static const char *fft_launch_row(Plan *p, const hipsoxr_job_t &j, const FftJobV
     if (const char *err = fft_try_wave(p, j, v, lay, a, stream, handled)) return err;
     if (*handled) return nullptr;
     if (!lay.v2ok && !lay.cp2ok && !lay.st2ok) return nullptr;
-    if (j.clip_table && !lay.v2ok) return nullptr; // ragged batches: the unit-stride kernel reads its clip's row; nothing else does
+    // ragged batches: every paired kernel reads its clip's row; the strided forms by name only (fft_ragged_rules.h: AUTO keeps
+    // interleaved tables of an exact-bank plan on the exact engine, bit for bit)
+    if (j.clip_table && !fft_table_form_served(lay.v2ok, lay.cp2ok, lay.st2ok, j.kernel != HIPSOXR_KERNEL_AUTO)) return nullptr;
     // float16 / bfloat16: the fused forms alone (half_rules.h) — what they do not take is the widening pass's, not an error
     if (v.half && half_fused_form(true, lay.v2ok, lay.cp2ok, j.clip_table != nullptr) == kHalfNone) return nullptr;
     return fft_launch_paired(*row.use, row.g, v, lay, a, stream, handled);

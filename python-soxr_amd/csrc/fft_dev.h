@@ -283,7 +283,7 @@ struct FftArgs {
     int64_t ics, ifs, ichs, ocs, ofs, ochs;
     int64_t in_frames, out_frames;
     int64_t in_lo;           // the column holds samples [in_lo, in_frames) (hipsoxr_job_t::in_abs0: `in` points at sample 0, zero outside).  Ragged batches: job-wide — 0 for the public jobs; the two-stage form's inner tables (twostage.hip) carry pad / 2 or -pad, and a row's second word is then the END of its column as an absolute sample index, in_lo + frames stored, its first word the offset of the first stored sample
-    const int64_t *clip_tab; // ragged batch (hipsoxr_job_t::clip_table_dev): [n_clips][4] = in offset, in frames, out offset, out frames; k_fft_pair2 only
+    const int64_t *clip_tab; // ragged batch (hipsoxr_job_t::clip_table_dev): [n_clips][4] = in offset, in frames, out offset, out frames; k_fft_pair2, k_fft_wave and k_fft_strided2 read their clip's row
     int32_t chpair;          // k_fft_strided2: 1 = pair neighbouring channels of interleaved data instead of blocks
     int64_t pairs_per_col;   // xcd_map: work items (blocks, or pairs of blocks) per channel unit
     int32_t xcd_map;         // interleaved multi-channel data: XCD-aware workgroup ids (see k_fft_strided2)

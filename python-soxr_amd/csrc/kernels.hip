@@ -1634,10 +1634,11 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             return "HIPSOXR_KERNEL_WAVE_DOT serves float32, float64, int32 and int16 jobs (float16 / bfloat16 jobs are not served by the reference-point kernel)";
     }
     // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
-    // (the kernel reads its clip's row), else — float clips of an interpolated-phase plan under AUTO with unit frame strides —
+    // (the kernel reads its clip's row: unit-stride columns under AUTO or by name, interleaved and strided ones by name),
+    // else — float clips of an interpolated-phase plan under AUTO, at any frame stride —
     // the two-stage form over the table, else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
-    // plans alike), else — such float clips with interleaved channels, the wave-dot kernel — clip by clip through the
-    // ordinary path.  Clips are independent and each keeps the engine it has alone: bit-exact engines stay bit-exact.
+    // plans alike), else — the wave-dot kernel, float clips of an interpolated-phase plan the two-stage form handed back —
+    // clip by clip through the ordinary path.  Clips are independent and each keeps the engine it has alone: bit-exact engines stay bit-exact.
     if (j.clip_table) {
         if (vr || res) return "ragged batches: constant-rate device jobs only";
         if (j.in_abs0 != 0 || j.out_k0 != 0) return "ragged batches: whole signals only (in_abs0 == 0, out_k0 == 0)";
@@ -1667,9 +1668,9 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             if (e) return e;
             if (handled) return nullptr;
         }
-        if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (unit-stride float columns of a tabled ratio)";
-        if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (unit-stride int16 / int32 columns of a tabled ratio)";
-        // float clips of an interpolated-phase plan under AUTO with unit frame strides: the two-stage form over the table —
+        if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (served: unit-stride, interleaved and strided float32 / float64 columns of a tabled ratio; not HIPSOXR_KERNEL_FFT_F64 on strided float32 data, not ratios outside the schedule table)";
+        if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (served: unit-stride int16 / int32 columns and interleaved int16 channel pairs at even offsets, of a tabled ratio; not int32 channel pairs, not int16 with an odd channel count, not ratios outside the schedule table)";
+        // float clips of an interpolated-phase plan under AUTO (unit-stride, interleaved or strided columns): the two-stage form over the table —
         // one ragged polyphase launch and one ragged FFT-stage launch per range of columns, one ragged launch of the exact
         // engine for the clips too short for the form (twostage.hip launch_two_stage_ragged; engine choice per clip is the
         // clip's alone)
@@ -1679,7 +1680,7 @@ const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPo
             if (handled) return nullptr;
         }
         // the exact engine: one launch of a kernel's RAGGED form (launch_ragged); what that does not serve — float clips of an
-        // interpolated-phase plan under AUTO on other layouts (interleaved channels: the two-stage form's, clip by clip), the
+        // interpolated-phase plan under AUTO that the two-stage form handed back, the
         // wave-dot kernel — clip by clip.  float16 / bfloat16 clips the fused launch above did not take: clip by clip too, each
         // re-entering as a plain half job (the elements between packed clips are never written)
         if (!half) {

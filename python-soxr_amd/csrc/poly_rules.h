@@ -248,7 +248,7 @@ inline int64_t two_stage_mid_outputs(bool up, int64_t Ls, int64_t Ms, int64_t n,
 }
 
 // ---- a clip table on the two-stage form (twostage.hip launch_two_stage_ragged) ------------------------------------------
-// A float clip table of an interpolated-phase plan with unit frame strides: a constant number of launches whatever the
+// A float clip table of an interpolated-phase plan (unit-stride, interleaved or strided columns): a constant number of launches whatever the
 // number of clips.  The table's rows are {in offset, in frames, out offset, out frames} (elements from in / out).
 //   * partition: a clip is EMPTY (out frames == 0: nothing is launched for it), TWO-STAGE (two_stage_admits says yes for its
 //     own frame counts with its own channels as the column count — the question launch_two_stage asks of the clip alone, so
@@ -297,7 +297,7 @@ struct RaggedPolyPlan {
     uint32_t n_short() const { return (uint32_t)(short_rows.size() / 4); }
     uint32_t n_cols() const { return (uint32_t)col_clip.size(); }
 };
-// rows: the caller's table; in_chs / out_chs: its channel strides (frame strides are 1); fft_T: the FFT stage's taps; budget:
+// rows: the caller's table; in_chs / out_chs: its channel strides (the frame strides are the launcher's: offsets here are of sample 0); fft_T: the FFT stage's taps; budget:
 // kPolyMidBudget (the debug-switch build may lower it)
 inline RaggedPolyPlan ragged_poly_plan(const int64_t *rows, uint32_t n_clips, uint32_t n_channels, int64_t in_chs, int64_t out_chs, size_t width, bool up,
                                        const PolyStage &s, int32_t fft_T, int64_t budget)

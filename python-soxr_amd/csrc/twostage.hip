@@ -686,8 +686,8 @@ struct PolyJob {
     int64_t n_lo, n_src, k_lo, n_out;
     uint32_t n_clips, n_channels;
     const int64_t *sstr, *dstr;
-    // a ragged launch (launch_two_stage_ragged): the device rows of its n_clips COLUMNS (n_channels == 1, clip strides 0, unit
-    // frame strides) — n_src / n_out are then the longest column's
+    // a ragged launch (launch_two_stage_ragged): the device rows of its n_clips COLUMNS (n_channels == 1, clip strides 0, the
+    // caller's frame stride on the caller's side and 1 on the intermediate's) — n_src / n_out are then the longest column's
     const int64_t *rows = nullptr;
 };
 
@@ -914,8 +914,9 @@ const char *launch_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream, bool
 // the clip alone), its place in the packed intermediate, the rows of both stages, the ranges — is poly_rules.h
 // ragged_poly_plan; here: the served layouts, ONE upload of every derived table, and per range one allocation, the two
 // launches in the direction's order and one free, in stream order; the short clips' launch last.
-// Served: float32 / float64, HIPSOXR_KERNEL_AUTO, unit frame strides both sides (mono clips, planar channels at any channel
-// stride) — what the ragged k_fft_pair2 reads.  The caller's clip_table_dev cannot serve: the inner launches read derived
+// Served: float32 / float64, HIPSOXR_KERNEL_AUTO, any positive frame stride on the caller's side (mono clips, planar channels
+// at any channel stride: the ragged k_fft_pair2; interleaved channels, channel slices: the ragged k_fft_strided2, one column
+// per (clip, channel), the intermediate library-owned and unit-stride either way).  The caller's clip_table_dev cannot serve: the inner launches read derived
 // tables (columns, not clips; intermediate offsets), and the short clips a compacted one.
 // *handled = false with no error — a layout not served, a plan without the form, a short clip the ragged exact launch does not
 // take, or the FFT stage declined — and the caller's clip-by-clip loop computes every clip.  (The FFT stage's answer follows
@@ -943,7 +944,7 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *strea
 {
     *handled = false;
     if (!p->phases || !j.clip_table || (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) || j.kernel != HIPSOXR_KERNEL_AUTO) return nullptr;
-    if (j.in_frame_stride != 1 || j.out_frame_stride != 1 || j.in_abs0 != 0 || j.out_k0 != 0 || j.n_channels > kPolyMaxCols) return nullptr;
+    if (j.in_frame_stride < 1 || j.out_frame_stride < 1 || j.in_abs0 != 0 || j.out_k0 != 0 || j.n_channels > kPolyMaxCols) return nullptr;
     {
         std::lock_guard<std::mutex> lk(p->mu);
         if (!p->two)
@@ -978,7 +979,9 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *strea
     const char *err = nullptr;
     bool all = true;
     if (hipMemcpyAsync(tabs, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) err = "ragged batches: table upload failed";
-    const int64_t unit[3] = {0, 1, 0}; // columns: no clip stride, unit frames, one channel
+    // columns: no clip stride, one channel; the intermediate's frames are unit-stride, the caller's lie at the caller's frame
+    // stride (interleaved channels, channel slices): the polyphase kernel multiplies by it, the FFT stage runs its strided form
+    const int64_t unit[3] = {0, 1, 0}, cin[3] = {0, j.in_frame_stride, 0}, cout[3] = {0, j.out_frame_stride, 0};
     for (size_t r = 0; r < rp.ranges.size() && !err && all; ++r) {
         const RaggedPolyRange &g = rp.ranges[r];
         void *mid = nullptr;
@@ -993,11 +996,11 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *strea
         fj.clip_table = rp.fft_rows.data() + 4 * (size_t)g.first; fj.clip_table_dev = fft_dev + 4 * (size_t)g.first;
         fj.in_frames = g.fft_in_longest; fj.out_frames = g.fft_out_longest;
         if (ts.up) { // x --FFT 1:2--> mid --poly--> y
-            fj.in_abs0 = rp.pad / 2; fj.out = mid;
-            pj.src = mid; pj.dst = j.out; pj.n_lo = -rp.pad; pj.k_lo = 0; pj.n_src = 0;
+            fj.in_abs0 = rp.pad / 2; fj.out = mid; fj.out_frame_stride = 1;
+            pj.src = mid; pj.dst = j.out; pj.dstr = cout; pj.n_lo = -rp.pad; pj.k_lo = 0; pj.n_src = 0;
         } else {     // x --poly--> mid --FFT 2:1--> y
-            pj.src = j.in; pj.dst = mid; pj.n_lo = 0; pj.k_lo = -rp.pad; pj.n_src = 0;
-            fj.in = mid; fj.in_abs0 = -rp.pad;
+            pj.src = j.in; pj.sstr = cin; pj.dst = mid; pj.n_lo = 0; pj.k_lo = -rp.pad; pj.n_src = 0;
+            fj.in = mid; fj.in_abs0 = -rp.pad; fj.in_frame_stride = 1;
         }
         bool fft_done = false;
         if (ts.up) {

@@ -119,21 +119,23 @@ class RaggedJob:
     `launch()` = one C call.  `outputs()` returns per-clip views of the packed result.
 
     One call is ONE launch on an exact-bank plan: unit-stride float columns of a tabled ratio go to the frequency-domain
-    engine under KERNEL_AUTO (from 2^13 outputs in all) or by name, as do mono int16 / int32 corpora under KERNEL_FFT_PCM;
-    everything else — int16 / int32 under the default selector, interleaved stereo / multichannel and float64 clips, small
-    jobs, KERNEL_EXACT, the tile and gather selectors — runs the exact engine's ragged kernels (the kernel reads its clip's row of
+    engine under KERNEL_AUTO (from 2^13 outputs in all) or by name, as do mono int16 / int32 corpora under KERNEL_FFT_PCM.
+    Interleaved stereo / multichannel clips — what this class builds for every [frames, channels] clip — are one launch of
+    that engine BY NAME: kernel=KERNEL_FFT on float32 / float64 (2-4x faster than the exact engine's launch on the measured
+    tables, 1e-6 / 2e-9 class), kernel=KERNEL_FFT_PCM on int16 with an even channel count; KERNEL_AUTO keeps them bit-exact:
+    everything else — int16 / int32 under the default selector, interleaved stereo / multichannel and float64 clips under
+    KERNEL_AUTO, small jobs, KERNEL_EXACT, the tile and gather selectors — runs the exact engine's ragged kernels (the kernel reads its clip's row of
     the table; the grid is the longest clip's; more than 65535 clip x channel columns: one launch per range of clips).
     Each clip has the bits of the clip run alone.  Interpolated-phase plans (`plan.phases != 0`, the arbitrary ratios) are
     ONE launch as well — int16 / int32 under the default selector, every type under KERNEL_EXACT / KERNEL_GATHER — on the
     ragged form of k_interp_tile, k_interp_wave or k_interp, chosen from the table.  float32 / float64 clips of such a plan
-    under KERNEL_AUTO belong to the two-stage form (another precision class): MONO clips are a constant number of launches
-    whatever the number of clips — the table is partitioned by the question asked of each clip alone: clips of 8192 frames
+    under KERNEL_AUTO belong to the two-stage form (another precision class): mono and interleaved multichannel clips alike
+    are a constant number of launches whatever the number of clips — the table is partitioned by the question asked of each clip alone: clips of 8192 frames
     or more on both sides run the two-stage form (one ragged polyphase launch + one ragged FFT-stage launch over all of
     them; more than 65535 of them, or more than 1 GiB of intermediate signal, cut that into ranges), every other non-empty
     clip the exact engine (one ragged launch).  Admitted clips are within the two-stage class of the float64 direct form
     (1e-6 float32 / 2e-9 float64 relative RMS), not bit-equal to the clip run alone; the short clips are bit-equal to it.
-    Interleaved multichannel float clips under KERNEL_AUTO (the ragged FFT kernels have no strided form) and
-    KERNEL_WAVE_DOT are served clip by clip inside the same call.
+    KERNEL_WAVE_DOT is served clip by clip inside the same call.
 
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
@@ -142,7 +144,8 @@ class RaggedJob:
         """dither: TPDF dither on int16 output (None = on for int16, as `soxr_amd.resample` and libsoxr do; keyed by
         dither_seed, channel and output index within each clip, so a clip's result does not depend on its neighbours).
         clip_counter: a one-element 64-bit integer device tensor that counts saturated integer outputs.
-        kernel: KERNEL_FFT_PCM serves an int16 / int32 corpus (mono clips) on the frequency-domain engine in one launch.
+        kernel: KERNEL_FFT_PCM serves an int16 / int32 corpus of mono clips, and an int16 corpus of clips with an even channel
+        count, on the frequency-domain engine in one launch; KERNEL_FFT a float32 / float64 corpus at any channel count.
         stream: a torch.cuda.Stream (ordering handled here) or a raw hipStream_t handle (the caller orders it)."""
         import torch
         if not clips:
