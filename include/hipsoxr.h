@@ -224,6 +224,11 @@ typedef struct {
     int64_t in_frames; /* frames present at `in`; the signal is zero outside [in_abs0, +frames)  */
     int64_t out_k0;    /* absolute index of the first output frame to produce                    */
     int64_t out_frames;/* output frames to produce (per clip)                                    */
+    /* Window jobs (in_abs0 / out_k0 != 0) on the exact engine are tested bit for bit — against the oracle at the job's own
+     * position and against the same job moved down by whole periods — with out_k0 up to 2^50 and in_abs0 to match, across
+     * 2^31 and 2^32 on either side (tests/test_gpu_window_positions.py).  hipsoxr_run_device refuses a negative out_k0
+     * ("invalid job extent").  A negative in_abs0 is not refused — in[0] then lies in front of stream index 0, which the
+     * two-stage form uses internally on the frequency-domain engine — but no caller-facing test covers it. */
     uint64_t *clip_counter; /* device counter of saturated integer outputs, or NULL            */
     uint32_t dither;        /* 1: TPDF dither on int16 output                                    */
     uint32_t dither_seed;

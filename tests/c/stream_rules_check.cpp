@@ -221,8 +221,117 @@ static void check_emit_count_vr()
     for (const VrCase &c : cases) run_vr_case(c);
 }
 
+// ---- the constant-rate rules at the counts of a stream that has run for hours or years: n_in_total, k_done and in_base
+// around 2^31, 2^32, 2^40 and 2^50.  A walk from zero is out of reach there, so each rule is held against its DEFINING
+// property, stated in 128-bit integers: the condition of k_avail is monotonic in k, so K is its value iff it holds at
+// K - 1 and fails at K; locate's (n0, p) are the quotient and remainder of k M by L; the stream's length is
+// floor(N L / M + 1/2).
+static bool computable(int64_t L, int64_t M, int32_t T, i128 k, i128 N) { return k >= 0 && k * M / L + T / 2 <= N - 1; }
+static uint64_t k_avail_big(int64_t L, int64_t M, int32_t T, uint64_t N)
+{
+    i128 k = ((i128)N * L) / M; // an estimate: within T/2 L/M + 2 of the answer, which the two loops then walk to
+    while (k > 0 && !computable(L, M, T, k - 1, (i128)N)) --k;
+    while (computable(L, M, T, k, (i128)N)) ++k;
+    return (uint64_t)k;
+}
+static uint64_t out_len_big(int64_t L, int64_t M, uint64_t N) { return (uint64_t)((2 * (i128)N * L + M) / (2 * (i128)M)); }
+
+static const int64_t kBigLM[7][2] = {{160, 147}, {147, 160}, {160, 441}, {2, 3}, {3, 1}, {1, 7}, {4800037, 4410000}};
+static const uint64_t kBigAt[4] = {(uint64_t)1 << 31, (uint64_t)1 << 32, (uint64_t)1 << 40, (uint64_t)1 << 50};
+
+static void check_large_counts()
+{
+    Plan p;
+    const size_t olens[] = {0, 1, 441, (size_t)-1};
+    for (auto &r : kBigLM)
+        for (int32_t T : {2, 30, 736}) {
+            p.L = r[0]; p.M = r[1]; p.T = T;
+            for (uint64_t at : kBigAt)
+                for (int64_t dn = -400; dn <= 400; dn += (dn >= -4 && dn < 4 ? 1 : 99)) {
+                    // ---- k_avail and the stream's length with n_in_total around the power of two ----
+                    const uint64_t N = at + (uint64_t)dn;
+                    const uint64_t avail = k_avail(p, N), total = plan_out_len(p, N);
+                    CHECK(computable(p.L, p.M, T, (i128)avail - 1, (i128)N) && !computable(p.L, p.M, T, (i128)avail, (i128)N),
+                          "k_avail %ld/%ld T=%d N=%lu: %lu is not where the condition ends", (long)p.L, (long)p.M, T, (unsigned long)N, (unsigned long)avail);
+                    CHECK(avail == k_avail_big(p.L, p.M, T, N), "k_avail %ld/%ld T=%d N=%lu: %lu, walked %lu", (long)p.L, (long)p.M, T, (unsigned long)N,
+                          (unsigned long)avail, (unsigned long)k_avail_big(p.L, p.M, T, N));
+                    CHECK(total == out_len_big(p.L, p.M, N), "plan_out_len %ld/%ld N=%lu: %lu, in 128 bits %lu", (long)p.L, (long)p.M, (unsigned long)N,
+                          (unsigned long)total, (unsigned long)out_len_big(p.L, p.M, N));
+                    // ---- emit_count with k_done a few outputs either side of what is due ----
+                    for (int64_t dk : {-100000, -442, -441, -440, -1, 0, 1, 5}) {
+                        for (int ended = 0; ended < 2; ++ended) {
+                            const uint64_t k_end = ended ? out_len_big(p.L, p.M, N) : k_avail_big(p.L, p.M, T, N);
+                            if ((int64_t)k_end + dk < 0) continue;
+                            const uint64_t k_done = k_end + (uint64_t)dk;
+                            const uint64_t due = k_end > k_done ? k_end - k_done : 0;
+                            for (size_t olen : olens)
+                                CHECK(emit_count(p, N, k_done, ended != 0, olen) == (size_t)(due < olen ? due : olen), "emit_count %ld/%ld T=%d N=%lu k_done=%lu ended=%d olen=%zu",
+                                      (long)p.L, (long)p.M, T, (unsigned long)N, (unsigned long)k_done, ended, olen);
+                        }
+                    }
+                }
+            // ---- k_avail with the RESULT around the power of two (ratios far from 1: N is then elsewhere) ----
+            for (uint64_t at : kBigAt) {
+                const uint64_t N0 = (uint64_t)(((i128)at * p.M) / p.L) + (uint64_t)(T / 2);
+                for (uint64_t N = N0 - 3; N <= N0 + 3; ++N) {
+                    const uint64_t avail = k_avail(p, N);
+                    CHECK(computable(p.L, p.M, T, (i128)avail - 1, (i128)N) && !computable(p.L, p.M, T, (i128)avail, (i128)N),
+                          "k_avail %ld/%ld T=%d N=%lu (result near %lu): %lu", (long)p.L, (long)p.M, T, (unsigned long)N, (unsigned long)at, (unsigned long)avail);
+                }
+            }
+            // ---- locate with k around the power of two: k M = L (n0 + T/2 - 1) + p, 0 <= p < L; consecutive outputs ----
+            for (uint64_t at : kBigAt) {
+                int64_t n0_prev = 0, ph_prev = 0;
+                for (int64_t dk = -5; dk <= 5; ++dk) {
+                    const int64_t k = (int64_t)at + dk;
+                    int64_t n0 = 0, ph = 0;
+                    locate(p, k, &n0, &ph);
+                    const i128 q = (i128)n0 + (T / 2 - 1);
+                    CHECK(ph >= 0 && ph < p.L && q * p.L + ph == (i128)k * p.M, "locate %ld/%ld T=%d k=%ld: n0=%ld p=%ld", (long)p.L, (long)p.M, T, (long)k, (long)n0, (long)ph);
+                    if (dk > -5) { // the step from k - 1: the phase moves by M, the window by the carries
+                        const int64_t carry = (ph_prev + p.M) / p.L;
+                        CHECK(ph == (ph_prev + p.M) % p.L && n0 == n0_prev + carry, "locate %ld/%ld k=%ld: no step of M from k - 1", (long)p.L, (long)p.M, (long)k);
+                    }
+                    n0_prev = n0; ph_prev = ph;
+                }
+            }
+        }
+    // ---- ring_keep with the ring's base (and with it first_needed) around the powers of two: a ring that straddles one ----
+    for (uint64_t at : kBigAt)
+        for (int64_t in_base = (int64_t)at - 12; in_base <= (int64_t)at + 2; in_base += 7)
+            for (int64_t in_fill = 0; in_fill <= 20; in_fill += 5)
+                for (int64_t fn = in_base - 3; fn <= in_base + in_fill + 3; ++fn) {
+                    const RingKeep k = ring_keep(fn, in_base, (size_t)in_fill);
+                    const int64_t want = fn < in_base ? in_base : fn > in_base + in_fill ? in_base + in_fill : fn;
+                    CHECK(k.keep_from == want && (int64_t)k.drop == want - in_base && (int64_t)k.keep == in_base + in_fill - want,
+                          "ring_keep first_needed=%ld base=%ld fill=%ld: keep_from %ld drop %zu keep %zu", (long)fn, (long)in_base, (long)in_fill, (long)k.keep_from, k.drop, k.keep);
+                }
+    // ---- the chain the stream walks (engine.cpp first_needed -> ring_keep -> the job's in_abs0): a stream that has emitted
+    // k_done outputs from n_in_total frames keeps the ring from locate(k_done)'s n0 on, and every output still due from the
+    // input so far has its whole window [n0, n0 + T) inside [keep_from, n_in_total) ----
+    for (auto &r : kBigLM) {
+        p.L = r[0]; p.M = r[1]; p.T = 30;
+        for (uint64_t at : kBigAt)
+            for (int64_t back : {1, 441, 4410}) {
+                const uint64_t N = at + 17, k_end = k_avail(p, N);
+                if (k_end < (uint64_t)back) continue;
+                const uint64_t k_done = k_end - (uint64_t)back;
+                int64_t n0 = 0, ph = 0, n0_last = 0;
+                locate(p, (int64_t)k_done, &n0, &ph);
+                locate(p, (int64_t)k_end - 1, &n0_last, &ph);
+                const int64_t in_base = n0 - 100;
+                const RingKeep k = ring_keep(n0, in_base, (size_t)((int64_t)N - in_base));
+                CHECK(k.keep_from == n0 && k.drop == 100 && (int64_t)k.keep == (int64_t)N - n0, "ring_keep in a stream at N=%lu", (unsigned long)N);
+                CHECK(n0_last + p.T <= (int64_t)N && n0_last >= n0, "%ld/%ld N=%lu: the last output due reads [%ld, %ld), the ring holds [%ld, %lu)", (long)p.L, (long)p.M,
+                      (unsigned long)N, (long)n0_last, (long)(n0_last + p.T), (long)n0, (unsigned long)N);
+                CHECK(emit_count(p, N, k_done, false, (size_t)-1) == (size_t)back, "emit_count in a stream at N=%lu", (unsigned long)N);
+            }
+    }
+}
+
 int main()
 {
+    check_large_counts();
     check_k_avail();
     check_ring_keep();
     check_ring_grow();
