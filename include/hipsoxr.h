@@ -282,7 +282,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form; no new field — the element types HIPSOXR_F16 / HIPSOXR_BF16).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form; no new field — the element types HIPSOXR_F16 / HIPSOXR_BF16; no new field — the entries hipsoxr_plan_vr_out_len and hipsoxr_run_device_vr_ragged).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */
@@ -313,6 +313,37 @@ HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint(hipsoxr_plan_t *, const h
  * for n_x[c], integer element types, HIPSOXR_F16 / HIPSOXR_BF16, in_abs0 / out_k0 != 0, variable-rate plans, any other selector.  No clips, no channels
  * or out_frames == 0: success, nothing launched.  Asynchronous on `hip_stream`. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *, const hipsoxr_job_t *job, void *hip_stream);
+
+/* ---- per-clip rates: a ragged batch on a variable-rate plan (speed perturbation in one launch) ---- */
+/* Outputs of `in_len` frames at constant io ratio `io_ratio` on a variable-rate plan (what a variable-rate stream set to that
+ * ratio before its first input emits in all: the k >= 0 with k S + S/2 <= in_len 2^64, S the ratio's truncated Q64.64 step);
+ * 0 on a plan that is not variable-rate, and for a ratio hipsoxr_stream_set_io_ratio would refuse on it.  Host only. */
+HIPSOXR_API uint64_t hipsoxr_plan_vr_out_len(const hipsoxr_plan_t *, uint64_t in_len, double io_ratio);
+/* A ragged batch in which clip c is resampled at io_ratios[c] (input frames per output frame), all clips in ONE launch of the
+ * exact engine's variable-rate kernels (more than 65535 clip x channel columns: one launch per range of clips).  The plan is
+ * hipsoxr_plan_create_vr's: one interpolated-phase table designed for the LARGEST io ratio, in_rate / out_rate; every
+ * smaller ratio is a step on the same table (no filter design and no upload per ratio).  The job is read as a ragged forward
+ * job: clip_table is REQUIRED — n_clips host rows { in offset, n_in, out offset, n_out } in elements from `in` / `out`, the
+ * clip strides are ignored, in_frames / out_frames are the LARGEST per-clip counts, frame and channel strides as usual
+ * (unit-stride columns, interleaved [frames, channels], strided); clip_table_dev as on ragged jobs (NULL: uploaded in stream
+ * order).  io_ratios is a HOST array of n_clips doubles, read before the call returns; io_ratios[c] becomes the clip's step
+ * by the truncation hipsoxr_stream_set_io_ratio applies.
+ * Clip c has, BIT FOR BIT, the frames that a fresh variable-rate stream of this plan — same type, channel count, dither
+ * flag and seed — yields when it is given hipsoxr_stream_set_io_ratio(s, io_ratios[c], 0) before any input, fed the whole
+ * clip and flushed, truncated to n_out[c] <= hipsoxr_plan_vr_out_len(plan, n_in[c], io_ratios[c]).  int16 dither is keyed by
+ * (seed, channel, output index within the clip); clip_counter receives the sum of those streams' counts.  Nothing outside
+ * a clip's [0, n_out[c]) is written, not the elements between packed clips either.
+ * Selectors: HIPSOXR_KERNEL_AUTO, _EXACT and _GATHER all run this one launch (no 1e-6-class form of it exists: AUTO is
+ * bit-exact here for floats too).  float32, float64, int32, int16.
+ * Refused by name, before anything is launched: a plan not made by hipsoxr_plan_create_vr, a NULL clip_table or io_ratios,
+ * a ratio outside (2^-20, 2^20) or above the plan's in_rate / out_rate (by more than the factor 1 + 1e-12 that
+ * hipsoxr_stream_set_io_ratio allows, in its words), a negative offset or count, a row above the job's in_frames /
+ * out_frames, n_out[c] above hipsoxr_plan_vr_out_len, a clip of more than 2^30 outputs, in_abs0 / out_k0 != 0, HIPSOXR_F16 /
+ * HIPSOXR_BF16, any other selector.  Not served: a ratio change inside a clip (streams have slews), gradients, the
+ * frequency-domain engine.  No clips, no channels or out_frames == 0: success, nothing launched.  Asynchronous on
+ * `hip_stream`. */
+HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_vr_ragged(hipsoxr_plan_t *, const hipsoxr_job_t *job,
+                                                         const double *io_ratios /* host, n_clips */, void *hip_stream);
 
 /* ---- stream: the soxr_t counterpart (host pointers, state carried across calls) ----------- */
 HIPSOXR_API hipsoxr_error_t hipsoxr_stream_create(double in_rate, double out_rate,

@@ -189,6 +189,9 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &job, void *str
 // (kernels.hip) the short clips of such a table — job.clip_table / clip_table_dev: the compacted sub-table — in one ragged
 // launch of the exact engine's interpolated kernels, the engine and the bits of each clip alone; *handled as launch_ragged_job's
 const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+// (kernels.hip) hipsoxr_run_device_vr_ragged's launch: job.clip_table validated by the entry, clock = the n_clips steps
+// {hi, lo} of its io ratios (host memory; vr_ragged_rules.h) — one launch of a VR && RAGGED kernel per range of clips
+const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &job, const uint64_t *clock, void *stream);
 // transposed operator of the exact engine (adjoint.hip; hipsoxr_run_device_adjoint): job.in = gy (in_frames of it), job.out = gx
 // (out_frames of it); validates the job itself.  HIPSOXR_KERNEL_ADJOINT: interpolated-phase plans too (k_adj_interp on the
 // forward's own table, device_bank_ensure).  adjoint_release drops the plan's transposed tables (rebuilt on next use).

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "device.h"
+#include "vr_ragged_rules.h"
 
 using namespace hipsoxr;
 
@@ -472,6 +473,44 @@ hipsoxr_error_t hipsoxr_run_device_adjoint_ragged(hipsoxr_plan_t *h, const hipso
 {
     if (!h || !job) return "null argument";
     return launch_adjoint_ragged(&h->p, *job, hip_stream);
+}
+
+uint64_t hipsoxr_plan_vr_out_len(const hipsoxr_plan_t *h, uint64_t in_len, double io_ratio)
+{
+    if (!h || !h->p.vr || vr_ragged_ratio_refusal(io_ratio, h->p.in_rate / h->p.out_rate)) return 0;
+    return vr_const_out_len(in_len, vr_ragged_step(io_ratio));
+}
+
+// Speed perturbation in one launch: clip c of a clip table at its own io ratio.  Everything is refused here, by name and
+// before the device is asked for; the launch is kernels.hip's (launch_vr_ragged).
+hipsoxr_error_t hipsoxr_run_device_vr_ragged(hipsoxr_plan_t *h, const hipsoxr_job_t *job, const double *io_ratios, void *hip_stream)
+{
+    if (!h || !job) return "null argument";
+    const Plan &p = h->p;
+    const hipsoxr_job_t &j = *job;
+    if (j.elem == HIPSOXR_F16 || j.elem == HIPSOXR_BF16)
+        return "variable-rate ragged batch: float16 / bfloat16 clip tables are not served (float32, float64, int32 or int16)";
+    if (j.elem < 0 || j.elem > HIPSOXR_BF16) return "invalid element type";
+    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && j.kernel != HIPSOXR_KERNEL_GATHER)
+        return "variable-rate ragged batch: served by the exact engine alone (HIPSOXR_KERNEL_AUTO, HIPSOXR_KERNEL_EXACT or HIPSOXR_KERNEL_GATHER)";
+    if (!p.vr) return "variable-rate ragged batch: the plan is not a variable-rate plan (hipsoxr_plan_create_vr makes one, for the largest io ratio)";
+    if (!j.clip_table) return "variable-rate ragged batch: the entry needs a clip_table (rows { in offset, in frames, out offset, out frames })";
+    if (!io_ratios) return "variable-rate ragged batch: the entry needs io_ratios (one io ratio per clip)";
+    if (j.in_abs0 != 0 || j.out_k0 != 0) return "variable-rate ragged batch: whole signals only (in_abs0 == 0, out_k0 == 0)";
+    if (j.in_frames < 0 || j.out_frames < 0) return "invalid job extent";
+    const double max_io = p.in_rate / p.out_rate;
+    std::vector<uint64_t> clock((size_t)j.n_clips * kVrClockRow);
+    for (uint32_t c = 0; c < j.n_clips; ++c) {
+        if (const char *e = vr_ragged_ratio_refusal(io_ratios[c], max_io)) return e;
+        const u128 step = vr_ragged_step(io_ratios[c]);
+        if (const char *e = vr_ragged_row_refusal(j.clip_table + kRaggedRow * (size_t)c, j.in_frames, j.out_frames, step)) return e;
+        clock[kVrClockRow * (size_t)c] = (uint64_t)(step >> 64);
+        clock[kVrClockRow * (size_t)c + 1] = (uint64_t)step;
+    }
+    if (j.n_clips == 0 || j.n_channels == 0 || j.out_frames == 0) return nullptr; // nothing to write
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+    if (device_count() <= 0) return kNoDevice;
+    return launch_vr_ragged(&h->p, j, clock.data(), hip_stream);
 }
 
 } // extern "C"

@@ -65,6 +65,7 @@
 #include "pcm_out.h"
 #include "ragged_rules.h"
 #include "tile_rules.h"
+#include "vr_ragged_rules.h"
 
 namespace hipsoxr {
 
@@ -744,6 +745,8 @@ struct GatherLaunch {
     // out_frames, a.ics == a.ocs == 0 (a clip's place is its row's) — and the clip count the log line carries
     const int64_t *rows = nullptr;
     int64_t ragged = -1;
+    // ... of a ragged variable-rate launch (launch_ragged_vr; vr then only says so): the device clock table, a step per clip
+    const uint64_t *clock = nullptr;
     bool whole_job() const { return done == 0 && nf == j.out_frames; }
     // per_wg outputs of one column per workgroup
     dim3 grid(int per_wg) const { return dim3((unsigned)((nf + per_wg - 1) / per_wg), (unsigned)cols, 1); }
@@ -859,10 +862,11 @@ static const char *launch_interp_wave(const Plan &p, const GatherLaunch &c, cons
     if (c.rows) { // the ragged form: the frame axis is the longest clip's (c.nf), no completion words
         InterpWaveArgsR wr;
         (InterpWaveArgs &)wr = wa;
-        wr.rows = c.rows;
+        wr.rows = c.rows; wr.clock = c.clock;
         const dim3 rgrid((unsigned)ragged_span_grid_x(c.nf, 32), (unsigned)c.cols, 1);
+        void (*rk)(InterpWaveArgsR) = c.vr ? k_interp_wave<IO, Real, true, true> : k_interp_wave<IO, Real, false, true>;
         GATHER_LAUNCH_LOG("interp_wave", p, c, rgrid, 256, g.lds, "span_cap=%d", (int)wa.span_cap);
-        hipLaunchKernelGGL((k_interp_wave<IO, Real, false, true>), rgrid, dim3(256), g.lds, c.st, wr);
+        hipLaunchKernelGGL(rk, rgrid, dim3(256), g.lds, c.st, wr);
         HIP_TRY(hipGetLastError());
         return nullptr;
     }
@@ -973,10 +977,11 @@ static const char *launch_interp_tile(const Plan &p, const GatherLaunch &c, cons
     if (c.rows) { // the ragged form (pair modes 0 and 1): the frame axis is the longest clip's (f.nf_t == c.nf)
         InterpTileArgsR tr;
         (InterpTileArgs &)tr = ta;
-        tr.rows = c.rows;
-        void (*rk)(InterpTileArgsR) = f.pair_mode ? k_interp_tile<IO, Real, false, true, false, true> : k_interp_tile<IO, Real, false, false, false, true>;
+        tr.rows = c.rows; tr.clock = c.clock;
+        void (*rk)(InterpTileArgsR) = f.pair_mode ? (c.vr ? k_interp_tile<IO, Real, true, true, false, true> : k_interp_tile<IO, Real, false, true, false, true>)
+                                                  : (c.vr ? k_interp_tile<IO, Real, true, false, false, true> : k_interp_tile<IO, Real, false, false, false, true>);
         if constexpr (sizeof(Real) == 4)
-            if (f.twin) rk = k_interp_tile<IO, Real, false, true, true, true>;
+            if (f.twin) rk = c.vr ? k_interp_tile<IO, Real, true, true, true, true> : k_interp_tile<IO, Real, false, true, true, true>;
         if (const char *e = ensure_dyn_lds((const void *)rk, lds)) return e;
         const dim3 rgrid((unsigned)ragged_span_grid_x(f.nf_t, f.KO), tgrid.y, 1);
         GATHER_LAUNCH_LOG("interp_tile", p, c, rgrid, 1024, lds, "KO=%d pair=%d twin=%d h=%lld nf_t=%lld m2_n=%lld span_cap=%d", (int)ta.KO, f.pair_mode, f.twin ? 1 : 0,
@@ -999,15 +1004,16 @@ static const char *launch_lane(const Plan &p, const GatherLaunch &c, const Inter
 {
     const dim3 block(256), grid = c.a.ch_fast ? dim3((unsigned)((c.nf * (int64_t)c.j.n_channels + 255) / 256), c.j.n_clips, 1) : c.grid(256);
     if (c.rows) { // the ragged form of k_interp (k_gather's: launch_ragged_gather)
-        if (!ia || c.vr) return "ragged batches: no such lane kernel";
+        if (!ia) return "ragged batches: no such lane kernel";
         const int64_t gx = ragged_gather_grid_x(c.nf, c.a.ch_fast ? c.j.n_channels : 1);
         if (gx > kTileMaxGridX) return kTileTooLong;
         InterpArgsR ir;
         (InterpArgs &)ir = *ia;
-        ir.rows = c.rows;
+        ir.rows = c.rows; ir.clock = c.clock;
         const dim3 rgrid((unsigned)gx, grid.y, 1);
         GATHER_LAUNCH_LOG("interp", p, c, rgrid, 256, (size_t)0, "ch_fast=%d", (int)c.a.ch_fast);
-        hipLaunchKernelGGL((k_interp<IO, Real, false, true>), rgrid, block, 0, c.st, ir);
+        if (c.vr) hipLaunchKernelGGL((k_interp<IO, Real, true, true>), rgrid, block, 0, c.st, ir);
+        else hipLaunchKernelGGL((k_interp<IO, Real, false, true>), rgrid, block, 0, c.st, ir);
         HIP_TRY(hipGetLastError());
         return nullptr;
     }
@@ -1452,6 +1458,77 @@ static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_
 const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
 {
     return launch_ragged_job(p, j, (hipStream_t)stream, handled, true);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Ragged variable-rate batches (hipsoxr_run_device_vr_ragged): clip c of a clip table at its own constant step, ONE launch of
+// the VR && RAGGED form of k_interp_tile, k_interp_wave or k_interp.  The decisions and their order are
+// launch_ragged_interp's, with vr = true and the LARGEST step of the clock table (vr_ragged_rules.h) where that one has the
+// plan's M / L: it sizes the span of 32 outputs, KO and span_cap for every clip (a slower clip's spans are shorter).
+// clock / clock_dev: host and device copy of the launch's [n_clips][2] steps.
+// ---------------------------------------------------------------------------------------------
+template <typename IO, typename Real>
+static const char *launch_ragged_vr(Plan *p, const hipsoxr_job_t &j, hipStream_t st, const uint64_t *clock, const uint64_t *clock_dev)
+{
+    const int64_t longest = ragged_longest(j.clip_table, j.n_clips);
+    if (longest == 0) return nullptr; // nothing to write
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (cols > kMaxGridY) return kTileTooManyCols;
+    hipsoxr_job_t jj = j;
+    jj.in_clip_stride = jj.out_clip_stride = 0; // (a clip's place is its row's)
+    static const VrPos per_clip = {0, 0, 0, 0, 0, 0}; // (GatherLaunch::vr says "variable rate": the clocks are the table's)
+    GatherLaunch c{jj, st, &per_clip, nullptr, 0, longest, cols, make_gather_args<IO>(*p, bank_of<Real>(p), jj, 0, longest, 0)};
+    c.rows = j.clip_table_dev; c.ragged = j.n_clips; c.clock = clock_dev;
+    InterpArgs ia;
+    std::memset(&ia, 0, sizeof ia);
+    ia.g = c.a;
+    set_interp_table(ia, *p, bank_of<Real>(p));
+    if ((1 << ia.lgP) != ia.P) return "variable-rate needs a power-of-two phase count";
+    const double step = vr_ragged_max_step(clock, j.n_clips); // input samples per output, at most
+    WaveGeom iw;
+    if (!switches().no_interp_wave && step < 1e6) iw = wave_geom<Real>((int64_t)std::ceil(31. * step), p->T);
+    InterpTileForm tf;
+    if (!switches().no_interp_tile && ragged_tile_considered(j.clip_table, j.n_clips))
+        tf = interp_tile_form<Real>(*p, jj, longest, step, true, iw.ok, j.clip_table);
+    if (tf.KO) return launch_interp_tile<IO, Real>(*p, c, ia, tf);
+    if (iw.ok) return launch_interp_wave<IO, Real>(*p, c, ia, iw);
+    return launch_lane<IO, Real>(*p, c, &ia);
+}
+
+// The whole table (validated by the entry; clock: its n_clips steps, host memory): the clip table as on ragged jobs
+// (clip_table_dev honoured), the clock table uploaded here in stream order and released behind the launches; one launch, or —
+// more columns than gridDim.y holds — one per range of clips, a range offsetting both tables.
+const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &j, const uint64_t *clock, void *stream)
+{
+    hipStream_t st = (hipStream_t)stream;
+    if (ragged_fold_step(j.n_channels) == 0) return "variable-rate ragged batch: more than 65535 channels are not served";
+    if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    const int64_t *rows = nullptr;
+    void *tmp = nullptr, *clk = nullptr;
+    if (const char *e = clip_table_device(j, st, &rows, &tmp)) return e;
+    const size_t bytes = (size_t)j.n_clips * kVrClockRow * sizeof(uint64_t);
+    const char *err = nullptr;
+    if (hipMallocAsync(&clk, bytes, st) != hipSuccess) { clk = nullptr; err = "variable-rate ragged batch: no device memory for the clock table"; }
+    else if (hipMemcpyAsync(clk, clock, bytes, hipMemcpyHostToDevice, st) != hipSuccess) err = "variable-rate ragged batch: clock table upload failed";
+    for (uint32_t r = 0; !err; ++r) {
+        const RaggedRange rg = ragged_fold_range(j.n_clips, j.n_channels, r);
+        if (!rg.count) break;
+        hipsoxr_job_t part = j;
+        part.n_clips = rg.count;
+        part.clip_table = j.clip_table + kRaggedRow * (size_t)rg.first;
+        part.clip_table_dev = rows + kRaggedRow * (size_t)rg.first;
+        const uint64_t *ck = clock + kVrClockRow * (size_t)rg.first, *ck_dev = (const uint64_t *)clk + kVrClockRow * (size_t)rg.first;
+        switch (j.elem) {
+        case HIPSOXR_F32: err = launch_ragged_vr<float, float>(p, part, st, ck, ck_dev); break;
+        case HIPSOXR_F64: err = launch_ragged_vr<double, double>(p, part, st, ck, ck_dev); break;
+        case HIPSOXR_I32: err = launch_ragged_vr<int32_t, double>(p, part, st, ck, ck_dev); break;
+        case HIPSOXR_I16: err = launch_ragged_vr<int16_t, float>(p, part, st, ck, ck_dev); break;
+        default: err = "invalid element type";
+        }
+    }
+    if (clk) (void)hipFreeAsync(clk, st);
+    if (tmp) (void)hipFreeAsync(tmp, st);
+    return err;
 }
 
 bool resident_post(const Plan &p, volatile uint64_t *w, uint32_t seq, int64_t in_abs0, int64_t in_frames, int64_t out_k0, int64_t out_frames,

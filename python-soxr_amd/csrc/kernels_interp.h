@@ -29,12 +29,25 @@ struct InterpArgs {
     uint64_t t_hi, t_lo, s_hi, s_lo, d_hi, d_lo; // VR: T0, S0, D (two's complement), Q64.64
 };
 
-// RAGGED (a clip table on an interpolated-phase plan; constant rate only, so VR has no such form): as k_gather's — the table
-// travels behind the arguments, a column's clip reads its row (in, in_frames, out, out_frames; wave-uniform), the grid is the
-// longest clip's.  Positions are located from the job's own clock (ia: a ragged job starts at output 0 of every clip).
+// RAGGED (a clip table on an interpolated-phase plan): as k_gather's — the table travels behind the arguments, a column's clip
+// reads its row (in, in_frames, out, out_frames; wave-uniform), the grid is the longest clip's.  Positions are located from
+// the job's own clock (ia: a ragged job starts at output 0 of every clip).
+// VR && RAGGED (hipsoxr_run_device_vr_ragged: every clip at its own constant step): a second table behind the arguments, the
+// clip's clock — its Q64.64 step {hi, lo}; T0 = 0, D = 0 — read like its row and put into a local InterpArgs (clip_clock), so
+// that the VR arithmetic below is the variable-rate stream's to the letter.
 struct InterpArgsR : InterpArgs {
-    const int64_t *rows; // [n_clips][4], as GatherArgsR::rows
+    const int64_t *rows;   // [n_clips][4], as GatherArgsR::rows
+    const uint64_t *clock; // VR: [n_clips][2] = step hi, lo (else unused)
 };
+// the clock of one clip: x's table and geometry, t = 0, s = the clip's step, d = 0 (wave-uniform: scalar loads)
+__device__ __forceinline__ const InterpArgs &clip_clock(const InterpArgs &x, const uint64_t *clock, uint32_t clip, InterpArgs &v)
+{
+    const uint64_t *c = clock + 2 * (int64_t)__builtin_amdgcn_readfirstlane(clip);
+    v = x;
+    v.t_hi = v.t_lo = v.d_hi = v.d_lo = 0;
+    v.s_hi = (uint64_t)uniform64((int64_t)c[0]); v.s_lo = (uint64_t)uniform64((int64_t)c[1]);
+    return v;
+}
 template <bool RAGGED> struct InterpArgsOf { typedef InterpArgs type; };
 template <> struct InterpArgsOf<true> { typedef InterpArgsR type; };
 // (clip_view, the view of one clip from its row: kernels.hip, beside k_gather's)
@@ -42,25 +55,28 @@ template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(co
 template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(const InterpArgsR &x, uint32_t clip, GatherArgs &v) { return clip_view<IO>(x.g, x.rows, clip, v); }
 
 template <typename IO, typename Real, bool VR, bool RAGGED = false>
-__global__ void __launch_bounds__(256) k_interp(typename InterpArgsOf<RAGGED>::type ia)
+__global__ void __launch_bounds__(256) k_interp(typename InterpArgsOf<RAGGED>::type ia_)
 {
-    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     typedef typename Vec4<Real>::type V4;
     int64_t idx;
     uint32_t ch, clip;
-    if (ia.g.ch_fast) {
+    if (ia_.g.ch_fast) {
         int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        idx = e / ia.g.n_channels;
-        ch = (uint32_t)(e - idx * ia.g.n_channels);
+        idx = e / ia_.g.n_channels;
+        ch = (uint32_t)(e - idx * ia_.g.n_channels);
         clip = blockIdx.y;
     } else {
         idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-        ch = blockIdx.y % ia.g.n_channels;
-        clip = blockIdx.y / ia.g.n_channels;
+        ch = blockIdx.y % ia_.g.n_channels;
+        clip = blockIdx.y / ia_.g.n_channels;
     }
     [[maybe_unused]] GatherArgs row_view;
-    const GatherArgs &a = clip_args<IO>(ia, clip, row_view);
+    const GatherArgs &a = clip_args<IO>(ia_, clip, row_view);
     if (RAGGED ? ragged_gather_skip(idx, a.out_frames) : idx >= a.out_frames) return;
+    [[maybe_unused]] InterpArgs clock_view;
+    const InterpArgs *iap = &ia_;
+    if constexpr (VR && RAGGED) iap = &clip_clock(ia_, ia_.clock, clip, clock_view);
+    const InterpArgs &ia = *iap;
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
     const int32_t T = a.T, H = T / 2;
     uint64_t iv, xq;
@@ -288,8 +304,10 @@ struct InterpTileArgs {
 
 // RAGGED: one output per lane and channel pairs (both members of a lane lie in the same clip); the halves form splits a
 // column at a point computed from its own length and has none.  A workgroup at or behind its clip's end returns first.
+// VR && RAGGED: the same two modes; KO and span_cap are sized by the largest step of the clock table.
 struct InterpTileArgsR : InterpTileArgs {
     const int64_t *rows;
+    const uint64_t *clock; // VR: as InterpArgsR::clock
 };
 template <bool RAGGED> struct InterpTileArgsOf { typedef InterpTileArgs type; };
 template <> struct InterpTileArgsOf<true> { typedef InterpTileArgsR type; };
@@ -389,9 +407,11 @@ struct InterpWaveArgs {
     uint32_t done_seq;
 };
 // RAGGED: a workgroup's 32 outputs are its column's clip's; a workgroup at or behind that clip's end (every workgroup of an
-// empty clip) returns before anything is located or published.  No completion words.
+// empty clip) returns before anything is located or published.  No completion words.  VR && RAGGED: the span of the 32
+// outputs is the clip's own step's; span_cap is sized by the largest step of the clock table.
 struct InterpWaveArgsR : InterpWaveArgs {
     const int64_t *rows;
+    const uint64_t *clock; // VR: as InterpArgsR::clock
 };
 template <bool RAGGED> struct InterpWaveArgsOf { typedef InterpWaveArgs type; };
 template <> struct InterpWaveArgsOf<true> { typedef InterpWaveArgsR type; };
@@ -401,7 +421,6 @@ template <typename IO> __device__ __forceinline__ const GatherArgs &clip_args(co
 template <typename IO, typename Real, bool VR, bool RAGGED = false>
 __global__ void __launch_bounds__(256) k_interp_wave(typename InterpWaveArgsOf<RAGGED>::type wa)
 {
-    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     typedef typename Vec4<Real>::type V4;
     constexpr int U = 8; // steps (of four taps) requested ahead
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
@@ -419,11 +438,15 @@ __global__ void __launch_bounds__(256) k_interp_wave(typename InterpWaveArgsOf<R
     const GatherArgs &a = clip_args<IO>(wa, clip, row_view);
     if constexpr (RAGGED)
         if (ragged_span_skip(blockIdx.x, 32, a.out_frames)) return; // (workgroup-uniform, before the first barrier; out_frames - 1 below is >= 0)
+    [[maybe_unused]] InterpArgs clock_view;
+    const InterpArgs *icp = &ia;
+    if constexpr (VR && RAGGED) icp = &clip_clock(ia, wa.clock, clip, clock_view);
+    const InterpArgs &ic = *icp; // the clock positions are located from
     const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
 
     const int64_t o = (int64_t)blockIdx.x * 32 + grp * 16 + quad;
     const int64_t oc = o < a.out_frames ? o : a.out_frames - 1; // (quads past the end repeat the last output and store nothing)
-    const InterpPos<Real> pos = interp_locate<Real, VR>(ia, oc);
+    const InterpPos<Real> pos = interp_locate<Real, VR>(ic, oc);
     const Real xx = (Real)pos.xq * (Real)(1. / (double)(1ULL << SH));
     const int64_t loc0 = pos.n0 - a.in_abs0;
     // positions grow with the output index: the first quad of group 0 holds the span's first sample, the last quad of group 1 its last window
@@ -512,7 +535,6 @@ template <typename IO, typename Real, bool VR, bool PAIR, bool TWIN = false, boo
 __global__ void __launch_bounds__(1024) k_interp_tile(typename InterpTileArgsOf<RAGGED>::type ta)
 {
     static_assert(!TWIN || (PAIR && sizeof(Real) == 4), "TWIN: float pairs only");
-    static_assert(!(VR && RAGGED), "a ragged job is constant-rate");
     constexpr int NM = PAIR ? 2 : 1; // members per lane; the staged span is [sample][member]
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const InterpArgs &ia = ta.ia;
@@ -546,13 +568,17 @@ __global__ void __launch_bounds__(1024) k_interp_tile(typename InterpTileArgsOf<
     const int64_t o_base = (int64_t)blockIdx.x * KO;
     if constexpr (RAGGED)
         if (ragged_span_skip(blockIdx.x, KO, a.out_frames)) return; // (workgroup-uniform, before the first barrier: n_here >= 1 below)
+    [[maybe_unused]] InterpArgs clock_view;
+    const InterpArgs *icp = &ia;
+    if constexpr (VR && RAGGED) icp = &clip_clock(ia, ta.clock, clip, clock_view);
+    const InterpArgs &ic = *icp; // the clock positions are located from
     const int32_t n_here = (int32_t)((a.out_frames - o_base) < KO ? (a.out_frames - o_base) : KO);
     const IO *xin = (const IO *)a.in + (int64_t)clip * a.ics + (int64_t)ch * a.ichs;
     IO *yo = (IO *)a.out + (int64_t)clip * a.ocs + (int64_t)ch * a.ochs;
 
     // span of inputs this workgroup needs (positions are monotonic in the output index)
-    const int64_t n_first = interp_locate<Real, VR>(ia, o_base).n0;
-    const int64_t n_end = interp_locate<Real, VR>(ia, o_base + n_here - 1).n0 + T;
+    const int64_t n_first = interp_locate<Real, VR>(ic, o_base).n0;
+    const int64_t n_end = interp_locate<Real, VR>(ic, o_base + n_here - 1).n0 + T;
     const int32_t span = (int32_t)(n_end - n_first);
     // rational mode: position of the workgroup's first output, then cheap local arithmetic
     uint32_t r_base = 0;
@@ -563,7 +589,7 @@ __global__ void __launch_bounds__(1024) k_interp_tile(typename InterpTileArgsOf<
         invL = 1. / (double)a.L;
     }
     auto locate = [&](int i) -> InterpPos<Real> {
-        if (VR) return interp_locate<Real, VR>(ia, o_base + i);
+        if (VR) return interp_locate<Real, VR>(ic, o_base + i);
         return interp_locate_local<Real>(ia, n_first, r_base, invL, i);
     };
 

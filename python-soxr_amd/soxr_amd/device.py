@@ -32,6 +32,7 @@ class Plan:
         self.phases = int(info.interpolated)  # 0: exact bank; P: interpolated-phase plan
         self.precision_bits, self.passband_end = info.precision_bits, info.passband_end
         self.stopband_begin, self.att_db, self.kaiser_beta = info.stopband_begin, info.att_db, info.kaiser_beta
+        self.vr = bool(vr)  # a variable-rate plan: in_rate / out_rate is the largest io ratio (`run_vr_ragged`, dist.resample_varispeed)
 
     def __del__(self, _delete=_n.lib.hipsoxr_plan_delete):  # bound early: module globals may be gone at exit
         h = getattr(self, "_h", None)
@@ -45,6 +46,12 @@ class Plan:
 
     def out_len(self, n_in):
         return int(_n.lib.hipsoxr_plan_out_len(self._h, int(n_in)))
+
+    def vr_out_len(self, n_in, io_ratio):
+        """Frames a variable-rate stream of this plan emits in all for n_in input frames at the constant io ratio `io_ratio`
+        (input frames per output frame; hipsoxr_plan_vr_out_len).  0 on a plan that is not `vr`, and for a ratio the plan
+        does not admit (above in_rate / out_rate, or outside (2^-20, 2^20))."""
+        return int(_n.lib.hipsoxr_plan_vr_out_len(self._h, int(n_in), float(io_ratio)))
 
     def bank(self):
         """float64 bank: phase-major [L][taps], or the cubic table [P][taps][4] of an
@@ -107,6 +114,33 @@ class Plan:
         j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
         j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
         _n.check(_n.lib.hipsoxr_run_device_adjoint_ragged(self._h, _C.byref(j), stream))
+
+    def run_vr_ragged(self, in_ptr, out_ptr, elem, n_channels, table, io_ratios, in_strides, out_strides, stream=None,
+                      kernel=_n.KERNEL_AUTO, table_dev=None, clip_counter=None, dither=False, dither_seed=0):
+        """Raw launch of a ragged batch with a rate per clip (hipsoxr_run_device_vr_ragged) on a `vr` plan: ONE launch for
+        all clips, clip c resampled at io_ratios[c] (input frames per output frame, at most in_rate / out_rate).  table:
+        int64 host array [n_clips, 4] of rows (in offset, n_in, out offset, n_out), offsets in elements from in_ptr /
+        out_ptr, n_out <= vr_out_len(n_in, io_ratios[c]) per clip; table_dev: a device copy of it (pointer), or None =
+        uploaded in stream order.  strides = (frame, channel) in elements.  KERNEL_AUTO, KERNEL_EXACT and KERNEL_GATHER
+        all run the exact engine: each clip has the bits of a variable-rate stream set to its ratio and fed the clip."""
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+        r = np.ascontiguousarray(io_ratios, dtype=np.float64).reshape(-1)
+        n = t.shape[0]
+        if r.shape[0] != n:
+            raise ValueError("one io ratio per clip")
+        if n == 0:  # (an empty array has no address worth passing: the entry refuses NULL tables)
+            t, r = np.zeros((1, 4), np.int64), np.ones(1, np.float64)
+        j = _n.Job()
+        j.in_, j.out, j.elem, j.kernel = in_ptr, out_ptr, elem, kernel
+        j.n_clips, j.n_channels = n, n_channels
+        j.in_frame_stride, j.in_chan_stride = in_strides
+        j.out_frame_stride, j.out_chan_stride = out_strides
+        j.in_abs0, j.out_k0 = 0, 0
+        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
+        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
+        j.clip_counter = clip_counter
+        j.dither, j.dither_seed = int(bool(dither)), int(dither_seed) & 0xFFFFFFFF
+        _n.check(_n.lib.hipsoxr_run_device_vr_ragged(self._h, _C.byref(j), r.ctypes.data, stream))
 
 
 class PreparedJob:

@@ -18,6 +18,9 @@ the GIL released (src/soxr_ext.cpp:222,297; tests/gil_bench.py:22-56).  The MI35
   `resample_ragged_adjoint(plan, gys, in_frames)` the transposed operator over all clips in ONE launch
   (`hipsoxr_run_device_adjoint_ragged`) — what its backward runs.
 
+* a rate per clip (speed perturbation): `resample_varispeed(plan, clips, io_ratios)` / `RaggedJob(..., io_ratios=...)` on a
+  variable-rate plan — every clip at its own ratio in ONE launch (`hipsoxr_run_device_vr_ragged`).
+
 bench.py and the multi-process tests import these from here; nothing below touches `oracle/`.
 """
 import ctypes as _C
@@ -140,8 +143,15 @@ class RaggedJob:
     Stream order: the job's tensors are produced on the caller's current stream; when it launches on another stream
     that stream first waits for the current one (and the result records its use there)."""
 
-    def __init__(self, plan, clips, kernel=_n.KERNEL_AUTO, stream=None, dither=None, dither_seed=0, clip_counter=None):
-        """dither: TPDF dither on int16 output (None = on for int16, as `soxr_amd.resample` and libsoxr do; keyed by
+    def __init__(self, plan, clips, kernel=_n.KERNEL_AUTO, stream=None, dither=None, dither_seed=0, clip_counter=None,
+                 io_ratios=None):
+        """io_ratios: None = every clip at the plan's ratio (everything above).  A sequence of len(clips) floats: clip c is
+        resampled at io_ratios[c] input frames per output frame — the plan must be a variable-rate one (`Plan(..., vr=True)`,
+        in_rate / out_rate the LARGEST ratio), output lengths are `plan.vr_out_len(n, io_ratios[c])`, and `launch()` is one
+        call of hipsoxr_run_device_vr_ragged: ONE launch of the exact engine's variable-rate kernels under KERNEL_AUTO,
+        KERNEL_EXACT and KERNEL_GATHER alike, each clip with the bits of a variable-rate `TensorStream` set to its ratio and
+        fed the clip (see `resample_varispeed`).  Table, in-place clips, stream ordering and `outputs()` are shared.
+        dither: TPDF dither on int16 output (None = on for int16, as `soxr_amd.resample` and libsoxr do; keyed by
         dither_seed, channel and output index within each clip, so a clip's result does not depend on its neighbours).
         clip_counter: a one-element 64-bit integer device tensor that counts saturated integer outputs.
         kernel: KERNEL_FFT_PCM serves an int16 / int32 corpus of mono clips, and an int16 corpus of clips with an even channel
@@ -158,7 +168,16 @@ class RaggedJob:
         es = clips[0].element_size()
         keep = [c if c.is_contiguous() else c.contiguous() for c in clips]  # (a strided clip is the one case that is copied)
         n_in = [int(c.shape[0]) for c in keep]
-        n_out = [plan.out_len(n) for n in n_in]
+        self._ratios = None
+        if io_ratios is None:
+            n_out = [plan.out_len(n) for n in n_in]
+        else:
+            if not getattr(plan, "vr", False):
+                raise ValueError("io_ratios needs a variable-rate plan: Plan(max_in_rate, out_rate, quality, vr=True)")
+            self._ratios = np.ascontiguousarray([float(r) for r in io_ratios], dtype=np.float64)
+            if self._ratios.shape[0] != len(clips):
+                raise ValueError("one io ratio per clip")
+            n_out = [plan.vr_out_len(n, r) for n, r in zip(n_in, self._ratios)]
         ptrs = [c.data_ptr() for c in keep if c.shape[0] > 0]   # (an empty tensor has no storage address)
         self.y = torch.empty((sum(n_out), ch), dtype=keep[0].dtype, device=device)
         base = min(ptrs) if ptrs else self.y.data_ptr()
@@ -192,7 +211,9 @@ class RaggedJob:
         self._any = max(n_out) > 0
 
     def launch(self):
-        if self._any:
+        if self._ratios is not None:  # (an empty job too: the entry is what refuses a ratio the plan does not admit)
+            _n.check(_n.lib.hipsoxr_run_device_vr_ragged(self._plan.handle, self._ref, self._ratios.ctypes.data, self._stream))
+        elif self._any:
             _n.check(_n.lib.hipsoxr_run_device(self._plan.handle, self._ref, self._stream))
 
     def outputs(self):
@@ -202,6 +223,34 @@ class RaggedJob:
             outs.append(v[:, 0] if mono else v)
             pos += n
         return outs
+
+
+def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=None, dither_seed=0, clip_counter=None):
+    """Resample every clip of a batch at a rate of its own, all clips in ONE launch; returns the list of per-clip outputs
+    (views of one packed buffer), clip c with `plan.vr_out_len(len(clips[c]), io_ratios[c])` frames.
+
+    Speed perturbation (Kaldi / ESPnet / NeMo: each clip played `factor` times faster, then relabelled with the original
+    rate): one variable-rate plan for the largest factor serves every factor —
+
+        plan = Plan(max(factors) * rate, rate, quality, vr=True)
+        ys = resample_varispeed(plan, clips, io_ratios=factors)
+
+    — no filter design, no bank upload and no regrouping per factor; the factors may be continuous random numbers.
+    io_ratios[c] is input frames per output frame, at most plan.in_rate / plan.out_rate (a larger one is refused: the
+    filter would alias).  Clips are device tensors of one device, dtype (float32, float64, int32, int16) and channel count,
+    [frames] or [frames, channels], read where they lie.  Each clip has, bit for bit, what a variable-rate
+    `TensorStream(plan.in_rate, plan.out_rate, ..., vr=True)` returns after `set_io_ratio(io_ratios[c], 1.0)` when it is fed
+    the whole clip with last=True: the exact engine under every admitted selector (KERNEL_AUTO, KERNEL_EXACT,
+    KERNEL_GATHER).  dither / dither_seed / clip_counter as for `RaggedJob`.  On the current torch stream, asynchronously.
+    No gradient is served: a clip with requires_grad raises."""
+    import torch
+    if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
+        raise RuntimeError("resample_varispeed: no gradient is served for per-clip rates (the adjoint kernels take constant-rate "
+                           "plans); detach the clips or call it under torch.no_grad()")
+    job = RaggedJob(plan, clips, kernel=kernel, dither=dither, dither_seed=dither_seed, clip_counter=clip_counter,
+                    io_ratios=io_ratios)
+    job.launch()
+    return job.outputs()
 
 
 def _split(packed, lengths, monos):
