@@ -83,6 +83,7 @@
 #include <vector>
 
 #include "device.h"
+#include "job_rules.h"
 
 namespace hipsoxr {
 
@@ -633,7 +634,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
         if (const char *e = launch_adjoint(p, f, stream)) return e;
         if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
         if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-        if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+        if (device_count() <= 0) return kNoDevice;
         return launch_half(p, j, stream, true);
     }
     if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
@@ -648,7 +649,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
         return "adjoint job: in_frames (cotangent frames) exceeds the plan's output length for out_frames";
     if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
     if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-    if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    if (device_count() <= 0) return kNoDevice;
     if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
         if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
         return j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, (hipStream_t)stream) : adj_interp_launch<double>(*p, j, (hipStream_t)stream);
@@ -674,34 +675,28 @@ const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
         return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
     if (!j.clip_table) return "adjoint job: the ragged entry needs a clip_table (equal-length clips: hipsoxr_run_device_adjoint)";
     for (uint32_t c = 0; c < j.n_clips; ++c) {
-        const int64_t *r = j.clip_table + 4 * (size_t)c;
-        if (r[0] < 0 || r[1] < 0 || r[2] < 0 || r[3] < 0) return "adjoint job: ragged: a clip's offset or frame count is negative";
-        if (r[1] > j.in_frames || r[3] > j.out_frames) return "adjoint job: ragged: a clip's frame count is above the job's in_frames / out_frames (the largest per-clip values)";
-        if ((uint64_t)r[1] > plan_out_len(*p, (uint64_t)r[3]))
-            return "adjoint job: ragged: a clip's n_y (cotangent frames) exceeds the plan's output length for its n_x";
+        switch (job_row_check(j.clip_table + kRaggedRow * (size_t)c, j.in_frames, j.out_frames, kJobRowAdjoint, [&](uint64_t n) { return plan_out_len(*p, n); })) {
+        case kJobRowOk: break;
+        case kJobRowNegative: return "adjoint job: ragged: a clip's offset or frame count is negative";
+        case kJobRowAboveJob: return "adjoint job: ragged: a clip's frame count is above the job's in_frames / out_frames (the largest per-clip values)";
+        case kJobRowAbovePlan: return "adjoint job: ragged: a clip's n_y (cotangent frames) exceeds the plan's output length for its n_x";
+        }
     }
     if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
     if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
     if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-    if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    if (device_count() <= 0) return kNoDevice;
     AdjBank *b = nullptr;
     if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
         if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
     } else if (const char *e = adj_ensure(p, &b)) return e;
     // The kernels read the DEVICE copy of the table; without one the host table, validated above, is uploaded in stream
-    // order (launch_job's rule: the buffer lives until the launch behind it has run).  A caller's copy is trusted.
+    // order (clip_table_device: the buffer lives until the launch behind it has run).  A caller's copy is trusted.
     const hipStream_t st = (hipStream_t)stream;
-    const int64_t *rows = j.clip_table_dev;
+    const int64_t *rows = nullptr;
     void *tmp = nullptr;
-    if (!rows) {
-        const size_t bytes = (size_t)j.n_clips * 4 * sizeof(int64_t);
-        if (hipMallocAsync(&tmp, bytes, st) != hipSuccess) return "adjoint job: ragged: no device memory for the clip table";
-        if (hipMemcpyAsync(tmp, j.clip_table, bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
-            (void)hipFreeAsync(tmp, st);
-            return "adjoint job: ragged: clip table upload failed";
-        }
-        rows = (const int64_t *)tmp;
-    }
+    static constexpr ClipTableTexts texts = {"adjoint job: ragged: no device memory for the clip table", "adjoint job: ragged: clip table upload failed"};
+    if (const char *e = clip_table_device(j, stream, &rows, &tmp, texts)) return e;
     const char *e;
     if (p->phases) e = j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, st, rows) : adj_interp_launch<double>(*p, j, st, rows);
     else e = j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, st, rows) : adj_launch<double>(*b, j, st, rows);

@@ -18,8 +18,6 @@ inline size_t elem_size(int elem)
     return elem == HIPSOXR_F32 ? 4 : elem == HIPSOXR_F64 ? 8 : elem == HIPSOXR_I32 ? 4 : 2;
 }
 
-// Enqueue one job (validated by the caller) on `stream`.  vr != nullptr: positions come from *vr
-// instead of the plan's rational ratio (interpolated-phase plans only).
 // Resident form of the small-launch kernel (kernels.hip, k_chain_resident): the mailbox in pinned host memory
 // and what a launch of an instance needs.
 static constexpr unsigned kResidentMaxWgs = 64;
@@ -54,6 +52,8 @@ struct ResidentLaunch {
 // Polling these costs nothing; an event costs a record call, the command processor's signal after the kernel has
 // drained, and the query calls (~4 us per streaming call).
 struct ChainDone { uint32_t *words; uint32_t cap, seq; uint32_t n_wgs = 0; };
+// Enqueue one job (validated by the caller) on `stream`.  vr != nullptr: positions come from *vr
+// instead of the plan's rational ratio (interpolated-phase plans only).
 // res: job.out_frames = the largest message the instance must serve; launches nothing but the resident kernel
 const char *launch_job(Plan *p, const hipsoxr_job_t &job, void *stream, const VrPos *vr = nullptr, ResidentLaunch *res = nullptr,
                        ChainDone *cd = nullptr);
@@ -63,6 +63,8 @@ bool resident_post(const Plan &p, volatile uint64_t *words, uint32_t seq, int64_
 void resident_leave(volatile uint64_t *words, uint32_t epoch);
 
 int device_count();
+// what every entry that needs a device answers without one
+constexpr const char *kNoDevice = "no HIP device available (hipsoxr has no CPU fallback)";
 
 // Dynamic LDS above 64 KB needs hipFuncAttributeMaxDynamicSharedMemorySize raised on the function: a driver call, made
 // once per (function, device) and high-water mark of the sizes asked for — not inside every launch.
@@ -168,7 +170,7 @@ const char *launch_copy(void *dst, const void *src, size_t bytes, void *stream);
 
 // frequency-domain engine (fft.hip): whole-signal float32 / float64 jobs; int16 / int32 jobs that name it
 // (HIPSOXR_KERNEL_FFT_PCM); float16 / bfloat16 jobs where a fused form exists (unit-stride columns, channel pairs: *handled
-// stays false otherwise and launch_job runs half.hip's passes).  ch0: index of the job's channel 0 in the caller's whole
+// stays false otherwise and launch_job_half runs half.hip's passes).  ch0: index of the job's channel 0 in the caller's whole
 // signal (the dither key of jobs folded over channel ranges)
 bool fft_job_eligible(const Plan &p, const hipsoxr_job_t &job);
 const char *launch_fft(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled, uint32_t ch0 = 0);
@@ -181,7 +183,7 @@ const char *launch_fft_window(Plan *p, const hipsoxr_job_t &job, void *stream, b
 void fft_release(const Plan *p);
 // two-stage form for interpolated-phase plans (twostage.hip): FFT stage at 1:2 / 2:1 + a short polyphase stage in LDS
 const char *launch_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
-// ... on a clip table (job.clip_table, validated by launch_job; float32 / float64, HIPSOXR_KERNEL_AUTO, any positive frame stride):
+// ... on a clip table (job.clip_table, validated by launch_job_table; float32 / float64, HIPSOXR_KERNEL_AUTO, any positive frame stride):
 // a constant number of launches — per range of columns one ragged polyphase launch and one ragged FFT-stage launch, plus
 // one launch_ragged_short for the clips the two-stage form does not admit.  *handled = false: not a table this path serves,
 // or the FFT stage declined — the caller's clip-by-clip loop computes every clip.
@@ -189,6 +191,12 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &job, void *str
 // (kernels.hip) the short clips of such a table — job.clip_table / clip_table_dev: the compacted sub-table — in one ragged
 // launch of the exact engine's interpolated kernels, the engine and the bits of each clip alone; *handled as launch_ragged_job's
 const char *launch_ragged_short(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+// (kernels.hip) the device copy of a job's clip table: job.clip_table_dev where the caller gave one (trusted to equal the
+// host table), else the validated host table uploaded in stream order — *tmp is then what the caller releases with
+// hipFreeAsync behind its launches.  texts: the caller's words for the two failures.
+struct ClipTableTexts { const char *no_memory, *upload_failed; };
+constexpr ClipTableTexts kRaggedTableTexts = {"ragged batches: no device memory for the clip table", "ragged batches: clip table upload failed"};
+const char *clip_table_device(const hipsoxr_job_t &job, void *stream, const int64_t **rows, void **tmp, const ClipTableTexts &texts = kRaggedTableTexts);
 // (kernels.hip) hipsoxr_run_device_vr_ragged's launch: job.clip_table validated by the entry, clock = the n_clips steps
 // {hi, lo} of its io ratios (host memory; vr_ragged_rules.h) — one launch of a VR && RAGGED kernel per range of clips
 const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &job, const uint64_t *clock, void *stream);
@@ -200,7 +208,7 @@ const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &job, void *strea
 void adjoint_release(const Plan *p);
 // float16 / bfloat16 jobs that no fused kernel takes (half.hip): one widening pass into stream-ordered float32 temporaries
 // packed in the caller's dimension order, the float32 job of the same selector (adjoint: through launch_adjoint, else
-// launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_job's clip-by-clip loop
+// launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_table_clips, the clip-by-clip loop,
 // re-enters with each clip as a plain job).
 const char *launch_half(Plan *p, const hipsoxr_job_t &job, void *stream, bool adjoint);
 

@@ -200,7 +200,6 @@ static const char *pinned_ensure(void **buf, size_t *cap, size_t bytes)
         if (e_ != hipSuccess) return hipGetErrorString(e_); \
     } while (0)
 
-static const char *kNoDevice = "no HIP device available (hipsoxr has no CPU fallback)";
 
 // ------------------------------------------------------------------------------------------------
 // Plan cache.  soxr.resample designs a filter per call in the reference (soxr_create inside

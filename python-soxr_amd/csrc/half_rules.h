@@ -1,4 +1,4 @@
-// half_rules.h — the two decisions of a float16 / bfloat16 device job (kernels.hip launch_job, fft.hip, half.hip): whether
+// half_rules.h — the two decisions of a float16 / bfloat16 device job (kernels.hip launch_job_half, fft.hip, half.hip): whether
 // the conversion is FUSED into a kernel of the frequency-domain engine, and — where it is not — the float32 temporaries of
 // the widening pass: their strides, their bytes, and the ranges of clips (or channels) a job is cut into so that the
 // temporaries of one range stay within a byte limit.  No HIP, no globals, no switches() (tests/c/half_rules_check.cpp checks
@@ -13,6 +13,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "job_rules.h" // the AUTO threshold and the column limit: the dispatcher's, for every element type
+
 namespace hipsoxr {
 
 // ---- fused or not ---------------------------------------------------------------------------------------------------
@@ -20,17 +22,18 @@ namespace hipsoxr {
 // and the selectors a half job is refused under, which never get here).
 enum HalfSelector { kHalfSelFft, kHalfSelAuto, kHalfSelOther };
 
-// AUTO takes the frequency-domain engine under the float rule — from 2^13 output samples in all — since a half job has no
-// bit-exact legacy to keep; by name always.  total_out: output samples over all clips and channels; no_fft: HIPSOXR_NO_FFT.
-constexpr int64_t kHalfAutoFftMin = (int64_t)1 << 13;
+// AUTO takes the frequency-domain engine under the float rule — job_auto_fft, from kJobAutoFftMin output samples in all —
+// since a half job has no bit-exact legacy to keep; by name always.  total_out: output samples over all clips and channels;
+// no_fft: HIPSOXR_NO_FFT.
+constexpr int64_t kHalfAutoFftMin = kJobAutoFftMin;
 inline bool half_wants_fft(HalfSelector sel, int64_t total_out, bool no_fft)
 {
-    return sel == kHalfSelFft || (sel == kHalfSelAuto && total_out >= kHalfAutoFftMin && !no_fft);
+    return sel == kHalfSelFft || (sel == kHalfSelAuto && job_auto_fft(total_out, no_fft));
 }
 
 // Ask the engine for a fused launch at all?  eligible: fft_job_eligible (whole signal, HQ / VHQ exact-ratio plan);
 // cols: (clip, channel) columns — the paired kernels index them through grid.y.
-constexpr uint64_t kHalfMaxCols = 65535;
+constexpr uint64_t kHalfMaxCols = kJobMaxCols;
 inline bool half_try_fused(HalfSelector sel, int64_t total_out, bool no_fft, bool eligible, uint64_t cols)
 {
     return half_wants_fft(sel, total_out, no_fft) && eligible && cols <= kHalfMaxCols;

@@ -62,6 +62,7 @@
 
 #include "device.h"
 #include "half_rules.h"
+#include "job_rules.h"
 #include "pcm_out.h"
 #include "ragged_rules.h"
 #include "tile_rules.h"
@@ -588,7 +589,7 @@ const char *device_bank_ensure(Plan *p, int prec)
     if (p->device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != p->device)
         return "this plan's device tables live on another device (one plan per device)";
     if (d.ready) return nullptr;
-    if (device_count() <= 0) return "no HIP device available (hipsoxr has no CPU fallback)";
+    if (device_count() <= 0) return kNoDevice;
     if (p->device < 0 && hipGetDevice(&cur) == hipSuccess) p->device = cur; // tables are built on first use, here
     TileGeom g, gm;
     const char *e = prec == 0 ? bank_upload<float>(p, d, &g, &gm) : bank_upload<double>(p, d, &g, &gm);
@@ -1397,21 +1398,55 @@ static const char *launch_ragged(Plan *p, const hipsoxr_job_t &j, hipStream_t st
 
 // The device copy of a ragged job's clip table: the caller's (clip_table_dev, trusted to equal the host table), or — NULL —
 // the host table, already validated, uploaded here in stream order (stream-ordered allocation: the buffer lives until the
-// launches behind it have run).  *tmp: what the caller frees with hipFreeAsync behind its launches.
-static const char *clip_table_device(const hipsoxr_job_t &j, hipStream_t st, const int64_t **rows, void **tmp)
+// launches behind it have run).  *tmp: what the caller frees with hipFreeAsync behind its launches.  texts: the caller's
+// words for the two failures.
+const char *clip_table_device(const hipsoxr_job_t &j, void *stream, const int64_t **rows, void **tmp, const ClipTableTexts &texts)
 {
+    hipStream_t st = (hipStream_t)stream;
     *tmp = nullptr;
     *rows = j.clip_table_dev;
     if (*rows) return nullptr;
-    const size_t bytes = (size_t)j.n_clips * 4 * sizeof(int64_t);
-    if (hipMallocAsync(tmp, bytes, st) != hipSuccess) { *tmp = nullptr; return "ragged batches: no device memory for the clip table"; }
+    const size_t bytes = (size_t)j.n_clips * kRaggedRow * sizeof(int64_t);
+    if (hipMallocAsync(tmp, bytes, st) != hipSuccess) { *tmp = nullptr; return texts.no_memory; }
     if (hipMemcpyAsync(*tmp, j.clip_table, bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
         (void)hipFreeAsync(*tmp, st);
         *tmp = nullptr;
-        return "ragged batches: clip table upload failed";
+        return texts.upload_failed;
     }
     *rows = (const int64_t *)*tmp;
     return nullptr;
+}
+
+// The element type of a job as the kernels' template arguments: f(IO{}, Real{}) with the sample type and the engine's
+// arithmetic type (float for float32 / int16 samples, double for float64 / int32).  invalid: what any other type is answered.
+template <typename F>
+static const char *with_elem(int elem, F f, const char *invalid = "invalid element type")
+{
+    switch (elem) {
+    case HIPSOXR_F32: return f(float{}, float{});
+    case HIPSOXR_F64: return f(double{}, double{});
+    case HIPSOXR_I32: return f(int32_t{}, double{});
+    case HIPSOXR_I16: return f(int16_t{}, float{});
+    }
+    return invalid;
+}
+// ... and selector and element type as the dispatcher's rules see them (job_rules.h)
+static JobSel job_sel(int kernel)
+{
+    JobSel s;
+    s.want_fft = kernel == HIPSOXR_KERNEL_FFT || kernel == HIPSOXR_KERNEL_FFT_F64;
+    s.want_pcm = kernel == HIPSOXR_KERNEL_FFT_PCM;
+    s.is_auto = kernel == HIPSOXR_KERNEL_AUTO;
+    s.exact_family = kernel == HIPSOXR_KERNEL_EXACT || kernel == HIPSOXR_KERNEL_GATHER;
+    s.fft_f64 = kernel == HIPSOXR_KERNEL_FFT_F64;
+    s.wave_dot = kernel == HIPSOXR_KERNEL_WAVE_DOT;
+    return s;
+}
+static JobElem job_elem(int elem)
+{
+    if (elem == HIPSOXR_F32 || elem == HIPSOXR_F64) return kJobElemFloat;
+    if (elem == HIPSOXR_I16 || elem == HIPSOXR_I32) return kJobElemPcm;
+    return elem_is_half(elem) ? kJobElemHalf : kJobElemOther;
 }
 
 // The ragged exact launch of a whole table: one launch, or — more columns than gridDim.y holds — one per range of clips
@@ -1420,11 +1455,9 @@ static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_
 {
     *handled = false;
     if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT || ragged_fold_step(j.n_channels) == 0) return nullptr;
-    // an interpolated-phase plan: float clips under AUTO belong to the two-stage form (another precision class) — all but
-    // the sub-table of clips that form does not admit (two_stage_short: launch_two_stage_ragged's), which are the exact engine's
-    if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage &&
-        !two_stage_short)
-        return nullptr;
+    // a table the two-stage form owns (job_rules.h) — all but the sub-table of clips that form does not admit
+    // (two_stage_short: launch_two_stage_ragged's), which are the exact engine's
+    if (job_two_stage_table(p->phases, job_sel(j.kernel), job_elem(j.elem), switches().no_fft, switches().no_two_stage) && !two_stage_short) return nullptr;
     if (ragged_longest(j.clip_table, j.n_clips) > ((int64_t)1 << 30)) return nullptr; // (launch_gather cuts such a clip into several launches)
     if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
     const int64_t *rows = nullptr;
@@ -1437,16 +1470,10 @@ static const char *launch_ragged_job(Plan *p, const hipsoxr_job_t &j, hipStream_
         if (!rg.count) break;
         hipsoxr_job_t part = j;
         part.n_clips = rg.count;
-        part.clip_table = j.clip_table + 4 * (size_t)rg.first;
-        part.clip_table_dev = rows + 4 * (size_t)rg.first;
+        part.clip_table = j.clip_table + kRaggedRow * (size_t)rg.first;
+        part.clip_table_dev = rows + kRaggedRow * (size_t)rg.first;
         bool h = false;
-        switch (j.elem) {
-        case HIPSOXR_F32: err = launch_ragged<float, float>(p, part, st, &h); break;
-        case HIPSOXR_F64: err = launch_ragged<double, double>(p, part, st, &h); break;
-        case HIPSOXR_I32: err = launch_ragged<int32_t, double>(p, part, st, &h); break;
-        case HIPSOXR_I16: err = launch_ragged<int16_t, float>(p, part, st, &h); break;
-        default: err = "invalid element type";
-        }
+        err = with_elem(j.elem, [&](auto io, auto real) { return launch_ragged<decltype(io), decltype(real)>(p, part, st, &h); });
         if (err) break;
         if (!h) { all = false; break; } // (decided by plan and selector: the same for every range)
     }
@@ -1518,13 +1545,7 @@ const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &j, const uint64_t *cl
         part.clip_table = j.clip_table + kRaggedRow * (size_t)rg.first;
         part.clip_table_dev = rows + kRaggedRow * (size_t)rg.first;
         const uint64_t *ck = clock + kVrClockRow * (size_t)rg.first, *ck_dev = (const uint64_t *)clk + kVrClockRow * (size_t)rg.first;
-        switch (j.elem) {
-        case HIPSOXR_F32: err = launch_ragged_vr<float, float>(p, part, st, ck, ck_dev); break;
-        case HIPSOXR_F64: err = launch_ragged_vr<double, double>(p, part, st, ck, ck_dev); break;
-        case HIPSOXR_I32: err = launch_ragged_vr<int32_t, double>(p, part, st, ck, ck_dev); break;
-        case HIPSOXR_I16: err = launch_ragged_vr<int16_t, float>(p, part, st, ck, ck_dev); break;
-        default: err = "invalid element type";
-        }
+        err = with_elem(j.elem, [&](auto io, auto real) { return launch_ragged_vr<decltype(io), decltype(real)>(p, part, st, ck, ck_dev); });
     }
     if (clk) (void)hipFreeAsync(clk, st);
     if (tmp) (void)hipFreeAsync(tmp, st);
@@ -1626,7 +1647,7 @@ static const char *launch_chain_items_typed(Plan *p, uint32_t nch, bool dither, 
 {
     int64_t max_out = 0;
     for (uint32_t i = 0; i < n_items; ++i) max_out = std::max(max_out, items[i].out_frames);
-    if (max_out >= 4096 || (uint64_t)n_items * nch > 65535 || switches().no_chain) return nullptr;
+    if (max_out >= 4096 || (uint64_t)n_items * nch > kJobMaxCols || switches().no_chain) return nullptr;
     const DeviceBank &d = bank_of<Real>(p);
     const ChainGeom g = chain_geom<Real>(*p, max_out);
     if (!g.ok) return nullptr;
@@ -1669,212 +1690,189 @@ const char *launch_chain_items(Plan *p, int elem, uint32_t n_channels, bool dith
     if (!n_items || !n_channels) return nullptr;
     if (const char *e = device_bank_ensure(p, engine_prec(elem))) return e;
     hipStream_t st = (hipStream_t)stream;
-    switch (elem) {
-    case HIPSOXR_F32: return launch_chain_items_typed<float, float>(p, n_channels, false, items, items_dev, n_items, st, handled);
-    case HIPSOXR_F64: return launch_chain_items_typed<double, double>(p, n_channels, false, items, items_dev, n_items, st, handled);
-    case HIPSOXR_I32: return launch_chain_items_typed<int32_t, double>(p, n_channels, false, items, items_dev, n_items, st, handled);
-    case HIPSOXR_I16: return launch_chain_items_typed<int16_t, float>(p, n_channels, dither, items, items_dev, n_items, st, handled);
-    }
-    return "unknown element type";
+    return with_elem(elem, [&](auto io, auto real) { // (dither: int16 samples alone)
+        using IO = decltype(io);
+        return launch_chain_items_typed<IO, decltype(real)>(p, n_channels, dither && std::is_same<IO, int16_t>::value, items, items_dev, n_items, st, handled);
+    }, "unknown element type");
 }
 
-// HIPSOXR_KERNEL_FFT_PCM is an explicit request for the frequency-domain engine on integer samples: whatever it cannot
-// serve is an error, never a quiet run of the exact engine (whose results differ in the last bit).
-static const char *fft_pcm_refusal(const Plan &p, const hipsoxr_job_t &j, const VrPos *vr, const ResidentLaunch *res)
+// ---------------------------------------------------------------------------------------------
+// The dispatcher of device jobs: launch_job and one function per decision.  What is refused, which engine is offered a job
+// and in which order, what a clip row must satisfy and how wide jobs fold are job_rules.h's; here are the calls.
+// ---------------------------------------------------------------------------------------------
+static const char *job_entry_refusal(const Plan &p, const hipsoxr_job_t &j, bool vr_or_res, bool res)
 {
-    if (vr || res) return "FFT engine: whole-signal device jobs only";
-    if (j.elem != HIPSOXR_I16 && j.elem != HIPSOXR_I32)
-        return "HIPSOXR_KERNEL_FFT_PCM serves int16 / int32 jobs (float jobs have HIPSOXR_KERNEL_FFT / HIPSOXR_KERNEL_FFT_F64)";
-    if (!fft_job_eligible(p, j))
-        return "FFT engine (integer samples) needs a whole-signal job (in_abs0 == 0, out_k0 == 0) on an HQ/VHQ exact-ratio plan";
+    const JobSel s = job_sel(j.kernel);
+    const JobElem el = job_elem(j.elem);
+    if (const char *e = job_resident_refusal(res, (uint64_t)j.n_clips * j.n_channels)) return e;
+    if (const char *e = job_pcm_refusal(s, el, vr_or_res)) return e;
+    if (s.want_pcm && !fft_job_eligible(p, j)) return kJobPcmIneligible;
+    if (const char *e = job_half_refusal(s, el, vr_or_res)) return e;
+    return job_table_refusal(j.clip_table != nullptr, vr_or_res, j.in_abs0, j.out_k0);
+}
+
+// every row of a clip table against the job and the plan; *total_out: the outputs of one channel, over all clips
+static const char *job_table_rows(const Plan &p, const hipsoxr_job_t &j, int64_t *total_out)
+{
+    *total_out = 0;
+    for (uint32_t c = 0; c < j.n_clips; ++c) {
+        const int64_t *r = j.clip_table + kRaggedRow * (size_t)c;
+        if (job_row_check(r, j.in_frames, j.out_frames, kJobRowForward, [&](uint64_t n) { return plan_out_len(p, n); }) != kJobRowOk)
+            return "ragged batches: a clip's offsets or frame counts are negative, exceed the job's, or exceed the plan's output length";
+        *total_out += r[3];
+    }
     return nullptr;
 }
 
-static constexpr int64_t kWideLaneMaxOut = 4095; // outputs per column up to which a wide channel-fast job stays whole (launch_job)
+// a table on the frequency-domain engine: one launch, the kernel reading its clip's row from the device copy of the table
+static const char *launch_table_fft(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+{
+    if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    hipsoxr_job_t jj = j;
+    void *tmp = nullptr;
+    if (const char *e = clip_table_device(j, stream, &jj.clip_table_dev, &tmp)) return e;
+    const char *e = launch_fft(p, jj, stream, handled, t_ch_base);
+    if (tmp) (void)hipFreeAsync(tmp, (hipStream_t)stream);
+    return e;
+}
+
+// a table clip by clip through the ordinary path, each non-empty clip re-entering as a plain job (float16 / bfloat16 clips:
+// as a plain half job — the elements between packed clips are never written)
+static const char *launch_table_clips(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    const size_t es = elem_size(j.elem);
+    for (uint32_t c = 0; c < j.n_clips; ++c) {
+        const int64_t *r = j.clip_table + kRaggedRow * (size_t)c;
+        if (r[3] == 0) continue;
+        hipsoxr_job_t one = j;
+        one.clip_table = one.clip_table_dev = nullptr;
+        one.n_clips = 1;
+        one.in = (const char *)j.in + r[0] * (int64_t)es;
+        one.out = (char *)j.out + r[2] * (int64_t)es;
+        one.in_frames = r[1]; one.out_frames = r[3];
+        if (const char *e = launch_job(p, one, stream)) return e;
+    }
+    return nullptr;
+}
+
+// Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
+// (unit-stride columns under AUTO or by name, interleaved and strided ones by name), else — float clips of an
+// interpolated-phase plan under AUTO, at any frame stride — the two-stage form over the table (one ragged polyphase launch
+// and one ragged FFT-stage launch per range of columns, one ragged launch of the exact engine for the clips too short for
+// the form: twostage.hip launch_two_stage_ragged), else one launch of the exact engine's ragged form (exact-bank and
+// interpolated-phase plans alike), else — the wave-dot kernel, float clips the two-stage form handed back, half clips no
+// fused launch took — clip by clip.  Clips are independent and each keeps the engine it has alone: bit-exact engines stay bit-exact.
+static const char *launch_job_table(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    int64_t total_out = 0;
+    if (const char *e = job_table_rows(*p, j, &total_out)) return e;
+    const JobSel s = job_sel(j.kernel);
+    const Switches &sw = switches();
+    bool handled = false;
+    if (job_try_fft(s, total_out * (int64_t)j.n_channels, sw.no_fft) && (uint64_t)j.n_clips * j.n_channels <= kJobMaxCols && fft_job_eligible(*p, j)) {
+        if (const char *e = launch_table_fft(p, j, stream, &handled)) return e;
+        if (handled) return nullptr;
+    }
+    if (s.want_fft) return "FFT engine unavailable for this ragged job (served: unit-stride, interleaved and strided float32 / float64 columns of a tabled ratio; not HIPSOXR_KERNEL_FFT_F64 on strided float32 data, not ratios outside the schedule table)";
+    if (s.want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (served: unit-stride int16 / int32 columns and interleaved int16 channel pairs at even offsets, of a tabled ratio; not int32 channel pairs, not int16 with an odd channel count, not ratios outside the schedule table)";
+    if (job_two_stage_table(p->phases, s, job_elem(j.elem), sw.no_fft, sw.no_two_stage)) {
+        if (const char *e = launch_two_stage_ragged(p, j, stream, &handled)) return e;
+        if (handled) return nullptr;
+    }
+    if (!elem_is_half(j.elem)) {
+        if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;
+        if (handled) return nullptr;
+    }
+    return launch_table_clips(p, j, stream);
+}
+
+// float16 / bfloat16 samples: device jobs in float32 arithmetic — fused into the frequency-domain engine's paired kernels
+// where the float32 job of the shape runs them (half_rules.h: the engine by name, or AUTO under the float rule, on a
+// whole-signal job of an HQ / VHQ exact-ratio plan — launch_fft then takes it on the row the float32 job takes, or leaves
+// it: no fused form for the layout or the ratio), else a widening pass, the float32 job and a narrowing pass (half.hip)
+static const char *launch_job_half(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    const HalfSelector sel = j.kernel == HIPSOXR_KERNEL_FFT ? kHalfSelFft : j.kernel == HIPSOXR_KERNEL_AUTO ? kHalfSelAuto : kHalfSelOther;
+    const int64_t total_out = (int64_t)j.out_frames * j.n_clips * j.n_channels;
+    if (half_try_fused(sel, total_out, switches().no_fft, fft_job_eligible(*p, j), (uint64_t)j.n_clips * j.n_channels)) {
+        if (const char *e = device_bank_ensure(p, 0)) return e;
+        bool handled = false;
+        if (const char *e = launch_fft(p, j, stream, &handled)) return e;
+        if (handled) return nullptr;
+    }
+    return launch_half(p, j, stream, false); // (the float32 job inside refuses what a float32 job is refused)
+}
+
+// more columns than one launch holds: range by range (job_fold), each re-entering; the dither of a channel stays keyed by
+// its index in the whole signal (t_ch_base)
+static const char *launch_job_folded(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPos *vr)
+{
+    const int64_t es = (int64_t)elem_size(j.elem);
+    const JobFold fold = job_fold(j.n_clips, j.n_channels);
+    const uint32_t saved = t_ch_base;
+    const char *e = nullptr;
+    for (uint64_t r = 0; !e; ++r) {
+        const JobRange g = job_fold_range(fold, r);
+        if (!g.n_clips) break;
+        hipsoxr_job_t part = j;
+        part.n_clips = g.n_clips; part.n_channels = g.n_ch;
+        part.in = (const char *)j.in + ((int64_t)g.clip0 * j.in_clip_stride + (int64_t)g.ch0 * j.in_chan_stride) * es;
+        part.out = (char *)j.out + ((int64_t)g.clip0 * j.out_clip_stride + (int64_t)g.ch0 * j.out_chan_stride) * es;
+        t_ch_base = saved + g.ch0;
+        e = launch_job(p, part, stream, vr);
+    }
+    t_ch_base = saved;
+    return e;
+}
+
+// The 1e-6-class engines in front of the exact one, in job_rules.h's order: the two-stage form, the frequency-domain engine
+// (HIPSOXR_KERNEL_FFT_F64: with float64 arithmetic whatever the I/O type), that engine on integer samples by name.
+// *handled = false and no text: the exact engine's job.
+static const char *launch_job_engines(Plan *p, const hipsoxr_job_t &j, void *stream, bool vr_or_res, bool *handled)
+{
+    const JobSel s = job_sel(j.kernel);
+    const Switches &sw = switches();
+    if (const char *e = job_fft_stream_refusal(s, vr_or_res)) return e;
+    if (!vr_or_res && job_two_stage(p->phases, s, job_elem(j.elem), sw.no_fft, sw.no_two_stage)) {
+        if (const char *e = launch_two_stage(p, j, stream, handled)) return e;
+        if (*handled) return nullptr;
+        if (s.want_fft) return "FFT engine unavailable for this plan (the two-stage form serves HQ / VHQ ratios down to 4:1, whole signals of >= ~5000 frames)";
+    }
+    if (!vr_or_res && (s.want_fft || s.is_auto)) {
+        const bool eligible = fft_job_eligible(*p, j);
+        if (s.want_fft && !eligible)
+            return "FFT engine needs a whole-signal float32 or float64 job (in_abs0 == 0, out_k0 == 0) on an HQ/VHQ exact-ratio plan";
+        if (eligible && job_try_fft(s, (int64_t)j.out_frames * j.n_clips * j.n_channels, sw.no_fft)) {
+            if (const char *e = launch_fft(p, j, stream, handled)) return e;
+            if (*handled) return nullptr;
+            if (s.want_fft) return s.fft_f64 ? "FFT engine (float64 arithmetic) unavailable for this plan or layout (unit-stride columns of a tabled ratio)"
+                                             : "FFT engine unavailable for this plan";
+        }
+    }
+    if (s.want_pcm) { // (eligible: checked on entry)
+        if (const char *e = launch_fft(p, j, stream, handled, t_ch_base)) return e;
+        if (*handled) return nullptr;
+        return "FFT engine (integer samples) unavailable for this plan or layout (unit-stride columns, or int16 interleaved channel pairs, of a tabled ratio)";
+    }
+    return nullptr;
+}
+
 const char *launch_job(Plan *p, const hipsoxr_job_t &j, void *stream, const VrPos *vr, ResidentLaunch *res, ChainDone *cd)
 {
     if (cd) cd->n_wgs = 0;
-    if (j.out_frames <= 0 || j.n_clips == 0 || j.n_channels == 0) return res ? "resident kernel: empty job" : nullptr;
+    if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return job_empty_refusal(res != nullptr);
+    const bool vr_or_res = vr || res;
+    if (const char *e = job_entry_refusal(*p, j, vr_or_res, res != nullptr)) return e;
+    if (j.clip_table) return launch_job_table(p, j, stream);
+    if (elem_is_half(j.elem)) return launch_job_half(p, j, stream);
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
-    if (res && cols > 65535) return "resident kernel: too many columns";
-    const bool want_pcm = j.kernel == HIPSOXR_KERNEL_FFT_PCM;
-    if (want_pcm)
-        if (const char *e = fft_pcm_refusal(*p, j, vr, res)) return e;
-    // float16 / bfloat16 samples: device jobs in float32 arithmetic — fused into the frequency-domain engine's paired kernels
-    // where the float32 job of the shape runs them, else a widening pass, the float32 job and a narrowing pass (half.hip)
-    const bool half = elem_is_half(j.elem);
-    if (half) {
-        if (vr || res) return "float16 / bfloat16 samples: device jobs only (streams take float32, float64, int32 and int16)";
-        if (j.kernel == HIPSOXR_KERNEL_FFT_F64)
-            return "HIPSOXR_KERNEL_FFT_F64 serves float32 / float64 jobs (float16 / bfloat16 jobs compute in float32: HIPSOXR_KERNEL_FFT)";
-        if (j.kernel == HIPSOXR_KERNEL_WAVE_DOT)
-            return "HIPSOXR_KERNEL_WAVE_DOT serves float32, float64, int32 and int16 jobs (float16 / bfloat16 jobs are not served by the reference-point kernel)";
-    }
-    // Ragged batch (hipsoxr_job_t::clip_table): one launch of the frequency-domain engine when it can take the job
-    // (the kernel reads its clip's row: unit-stride columns under AUTO or by name, interleaved and strided ones by name),
-    // else — float clips of an interpolated-phase plan under AUTO, at any frame stride —
-    // the two-stage form over the table, else one launch of the exact engine's ragged form (exact-bank and interpolated-phase
-    // plans alike), else — the wave-dot kernel, float clips of an interpolated-phase plan the two-stage form handed back —
-    // clip by clip through the ordinary path.  Clips are independent and each keeps the engine it has alone: bit-exact engines stay bit-exact.
-    if (j.clip_table) {
-        if (vr || res) return "ragged batches: constant-rate device jobs only";
-        if (j.in_abs0 != 0 || j.out_k0 != 0) return "ragged batches: whole signals only (in_abs0 == 0, out_k0 == 0)";
-        int64_t total_out = 0;
-        for (uint32_t c = 0; c < j.n_clips; ++c) {
-            const int64_t *r = j.clip_table + 4 * (size_t)c;
-            if (r[0] < 0 || r[2] < 0 || r[1] < 0 || r[3] < 0 || r[1] > j.in_frames || r[3] > j.out_frames || (uint64_t)r[3] > plan_out_len(*p, (uint64_t)r[1]))
-                return "ragged batches: a clip's offsets or frame counts are negative, exceed the job's, or exceed the plan's output length";
-            total_out += r[3];
-        }
-        // AUTO takes the 1e-6-class engine under the same rule as for equal-length jobs (>= 2^13 outputs in all): engine
-        // choice — and with it bit-exactness — does not depend on whether a table is present
-        const bool want_fft = j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64 || want_pcm;
-        const bool big = total_out * (int64_t)j.n_channels >= (1 << 13);
-        if ((want_fft || (j.kernel == HIPSOXR_KERNEL_AUTO && big && !switches().no_fft)) &&
-            cols <= 65535 && fft_job_eligible(*p, j)) {
-            if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
-            // The kernel reads the DEVICE copy of the table.  Without one (clip_table_dev == NULL) the host table — the
-            // one validated above — is uploaded here, in stream order (stream-ordered allocation: the buffer lives until
-            // the launch behind it has run).  A caller-supplied device copy is trusted to equal the host table.
-            hipsoxr_job_t jj = j;
-            void *tmp = nullptr;
-            if (const char *e = clip_table_device(j, (hipStream_t)stream, &jj.clip_table_dev, &tmp)) return e;
-            bool handled = false;
-            const char *e = launch_fft(p, jj, stream, &handled, t_ch_base);
-            if (tmp) (void)hipFreeAsync(tmp, (hipStream_t)stream);
-            if (e) return e;
-            if (handled) return nullptr;
-        }
-        if (j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64) return "FFT engine unavailable for this ragged job (served: unit-stride, interleaved and strided float32 / float64 columns of a tabled ratio; not HIPSOXR_KERNEL_FFT_F64 on strided float32 data, not ratios outside the schedule table)";
-        if (want_pcm) return "FFT engine (integer samples) unavailable for this ragged job (served: unit-stride int16 / int32 columns and interleaved int16 channel pairs at even offsets, of a tabled ratio; not int32 channel pairs, not int16 with an odd channel count, not ratios outside the schedule table)";
-        // float clips of an interpolated-phase plan under AUTO (unit-stride, interleaved or strided columns): the two-stage form over the table —
-        // one ragged polyphase launch and one ragged FFT-stage launch per range of columns, one ragged launch of the exact
-        // engine for the clips too short for the form (twostage.hip launch_two_stage_ragged; engine choice per clip is the
-        // clip's alone)
-        if (p->phases && j.kernel == HIPSOXR_KERNEL_AUTO && (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_fft && !switches().no_two_stage) {
-            bool handled = false;
-            if (const char *e = launch_two_stage_ragged(p, j, stream, &handled)) return e;
-            if (handled) return nullptr;
-        }
-        // the exact engine: one launch of a kernel's RAGGED form (launch_ragged); what that does not serve — float clips of an
-        // interpolated-phase plan under AUTO that the two-stage form handed back, the
-        // wave-dot kernel — clip by clip.  float16 / bfloat16 clips the fused launch above did not take: clip by clip too, each
-        // re-entering as a plain half job (the elements between packed clips are never written)
-        if (!half) {
-            bool handled = false;
-            if (const char *e = launch_ragged_job(p, j, (hipStream_t)stream, &handled)) return e;
-            if (handled) return nullptr;
-        }
-        const size_t es = elem_size(j.elem);
-        for (uint32_t c = 0; c < j.n_clips; ++c) {
-            const int64_t *r = j.clip_table + 4 * (size_t)c;
-            if (r[3] == 0) continue;
-            hipsoxr_job_t one = j;
-            one.clip_table = one.clip_table_dev = nullptr;
-            one.n_clips = 1;
-            one.in = (const char *)j.in + r[0] * (int64_t)es;
-            one.out = (char *)j.out + r[2] * (int64_t)es;
-            one.in_frames = r[1]; one.out_frames = r[3];
-            if (const char *e = launch_job(p, one, stream)) return e;
-        }
-        return nullptr;
-    }
-    if (half) {
-        // fused (half_rules.h): the frequency-domain engine by name, or AUTO under the float rule (2^13 outputs in all), on
-        // a whole-signal job of an HQ / VHQ exact-ratio plan — launch_fft then takes it on the row the float32 job takes,
-        // or leaves it (*handled == false: no fused form for the layout or the ratio)
-        const HalfSelector sel = j.kernel == HIPSOXR_KERNEL_FFT ? kHalfSelFft : j.kernel == HIPSOXR_KERNEL_AUTO ? kHalfSelAuto : kHalfSelOther;
-        const int64_t total_out = (int64_t)j.out_frames * j.n_clips * j.n_channels;
-        if (half_try_fused(sel, total_out, switches().no_fft, fft_job_eligible(*p, j), cols)) {
-            if (const char *e = device_bank_ensure(p, 0)) return e;
-            bool handled = false;
-            if (const char *e = launch_fft(p, j, stream, &handled)) return e;
-            if (handled) return nullptr;
-        }
-        return launch_half(p, j, stream, false); // (the float32 job inside refuses what a float32 job is refused)
-    }
-    // Kernels index (clip, channel) columns through grid.y (<= 65535).  Wider jobs — the Python surface
-    // admits 65536 channels like the reference, src/soxr/__init__.py:22 — are folded into several
-    // launches over channel (or clip) ranges; columns are independent, so the result is the same.
-    // Not folded: a short constant-rate job of an interpolated-phase plan on channel-fast data.  launch_gather serves it whole
-    // with lane-per-output k_interp — consecutive lanes on consecutive channels of one frame, every load coalesced, the clips
-    // in grid.y — where the fold would run k_chain twice over columns a frame apart in memory (kWideLaneMaxOut: measured).
-    const bool wide_lane = cols > 65535 && p->phases && !vr && !res && j.n_clips <= 65535 && j.in_chan_stride == 1 &&
-                           j.out_frames <= kWideLaneMaxOut && (int64_t)j.out_frames * j.n_channels < ((int64_t)1 << 31) &&
-                           (j.kernel == HIPSOXR_KERNEL_AUTO || j.kernel == HIPSOXR_KERNEL_EXACT || j.kernel == HIPSOXR_KERNEL_GATHER);
-    if (cols > 65535 && !wide_lane) {
-        const size_t es = elem_size(j.elem);
-        hipsoxr_job_t part = j;
-        if (j.n_channels == 1 || j.n_clips > 65535) { // one clip range at a time (clips and channels both wide: the channels are folded below it)
-            for (uint32_t c0 = 0; c0 < j.n_clips; c0 += 65535) {
-                part = j;
-                part.n_clips = std::min<uint32_t>(65535, j.n_clips - c0);
-                part.in = (const char *)j.in + (int64_t)c0 * j.in_clip_stride * (int64_t)es;
-                part.out = (char *)j.out + (int64_t)c0 * j.out_clip_stride * (int64_t)es;
-                if (const char *e = launch_job(p, part, stream, vr)) return e;
-            }
-            return nullptr;
-        }
-        const uint32_t step = 65535 / j.n_clips;
-        for (uint32_t h0 = 0; h0 < j.n_channels; h0 += step) {
-            part = j;
-            part.n_channels = std::min<uint32_t>(step, j.n_channels - h0);
-            part.in = (const char *)j.in + (int64_t)h0 * j.in_chan_stride * (int64_t)es;
-            part.out = (char *)j.out + (int64_t)h0 * j.out_chan_stride * (int64_t)es;
-            const uint32_t saved = t_ch_base;
-            t_ch_base = saved + h0;
-            const char *e = launch_job(p, part, stream, vr);
-            t_ch_base = saved;
-            if (e) return e;
-        }
-        return nullptr;
-    }
-    const int prec = engine_prec(j.elem);
-    if (const char *e = device_bank_ensure(p, prec)) return e;
-    // Frequency-domain engine: explicit request, or AUTO for large whole-signal float32 jobs.
-    // It is NOT bit-identical to the canonical order (about 2e-7 relative RMS), so it is never chosen
-    // for HIPSOXR_KERNEL_EXACT — which is what the stream / one-shot host entry points pass.
-    // HIPSOXR_KERNEL_FFT_F64: the same engine with float64 arithmetic whatever the I/O type (float32 jobs at the width
-    // libsoxr's VHQ recipe computes in; float64 jobs run it anyway).
-    const bool want_fft = j.kernel == HIPSOXR_KERNEL_FFT || j.kernel == HIPSOXR_KERNEL_FFT_F64;
-    if (want_fft && (vr || res)) return "FFT engine: whole-signal device jobs only";
-    // Ratios without an exact bank (interpolated-phase plans): the two-stage form — FFT engine at 1:2 / 2:1 plus a short
-    // polyphase stage — for whole-signal float jobs (1e-6 class, like the FFT engine itself; twostage.hip)
-    if (!vr && !res && p->phases && (want_fft || (j.kernel == HIPSOXR_KERNEL_AUTO && !switches().no_fft)) &&
-        (j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64) && !switches().no_two_stage) {
-        bool handled = false;
-        if (const char *e = launch_two_stage(p, j, stream, &handled)) return e;
-        if (handled) return nullptr;
-        if (want_fft) return "FFT engine unavailable for this plan (the two-stage form serves HQ / VHQ ratios down to 4:1, whole signals of >= ~5000 frames)";
-    }
-    if (!vr && !res && (want_fft || j.kernel == HIPSOXR_KERNEL_AUTO)) {
-        const bool no_fft = switches().no_fft;
-        const bool eligible = fft_job_eligible(*p, j);
-        const bool big = (int64_t)j.out_frames * j.n_clips * j.n_channels >= (1 << 13); // even one block pair beats the tiled exact kernels (7 vs 10 us)
-        if (want_fft && !eligible)
-            return "FFT engine needs a whole-signal float32 or float64 job (in_abs0 == 0, out_k0 == 0) on an HQ/VHQ exact-ratio plan";
-        if (eligible && (want_fft || (big && !no_fft))) {
-            bool handled = false;
-            if (const char *e = launch_fft(p, j, stream, &handled)) return e;
-            if (handled) return nullptr;
-            if (want_fft) return j.kernel == HIPSOXR_KERNEL_FFT_F64 ? "FFT engine (float64 arithmetic) unavailable for this plan or layout (unit-stride columns of a tabled ratio)"
-                                                                     : "FFT engine unavailable for this plan";
-        }
-    }
-    if (want_pcm) { // (eligible: checked on entry)
-        bool handled = false;
-        if (const char *e = launch_fft(p, j, stream, &handled, t_ch_base)) return e;
-        if (handled) return nullptr;
-        return "FFT engine (integer samples) unavailable for this plan or layout (unit-stride columns, or int16 interleaved channel pairs, of a tabled ratio)";
-    }
-    hipStream_t st = (hipStream_t)stream;
-    switch (j.elem) {
-    case HIPSOXR_F32: return launch_typed<float, float>(p, j, st, vr, res, cd);
-    case HIPSOXR_F64: return launch_typed<double, double>(p, j, st, vr, res, cd);
-    case HIPSOXR_I32: return launch_typed<int32_t, double>(p, j, st, vr, res, cd);
-    case HIPSOXR_I16: return launch_typed<int16_t, float>(p, j, st, vr, res, cd);
-    }
-    return "invalid element type";
+    if (cols > kJobMaxCols && !job_wide_lane(cols, p->phases != 0, vr_or_res, j.n_clips, j.in_chan_stride, j.out_frames, j.n_channels, job_sel(j.kernel)))
+        return launch_job_folded(p, j, stream, vr);
+    if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    bool handled = false;
+    if (const char *e = launch_job_engines(p, j, stream, vr_or_res, &handled)) return e;
+    if (handled) return nullptr;
+    return with_elem(j.elem, [&](auto io, auto real) { return launch_typed<decltype(io), decltype(real)>(p, j, (hipStream_t)stream, vr, res, cd); });
 }
 
 } // namespace hipsoxr

@@ -6,6 +6,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "job_rules.h" // kRaggedRow (a clip table's row), kJobMaxCols
+
 // (the skip tests are what the kernels themselves call: under a device compiler they are device functions too)
 #if defined(__HIPCC__)
 #define HIPSOXR_RULE __host__ __device__ inline
@@ -15,9 +17,7 @@
 
 namespace hipsoxr {
 
-// A clip table's rows are {in offset, in frames, out offset, out frames}.
-constexpr int kRaggedRow = 4;
-constexpr uint32_t kMaxGridY = 65535;
+constexpr uint32_t kMaxGridY = kJobMaxCols;
 
 // the longest clip of rows [0, n): what sizes the grid's frame axis and chooses the kernel family
 inline int64_t ragged_longest(const int64_t *rows, uint32_t n)

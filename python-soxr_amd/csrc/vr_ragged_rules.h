@@ -54,9 +54,10 @@ inline const char *vr_ragged_ratio_refusal(double io_ratio, double max_io)
 // What is refused of one row {in offset, in frames, out offset, out frames} at its clip's step, or nullptr
 inline const char *vr_ragged_row_refusal(const int64_t *row, int64_t job_in_frames, int64_t job_out_frames, u128 step)
 {
-    if (row[0] < 0 || row[1] < 0 || row[2] < 0 || row[3] < 0) return "variable-rate ragged batch: a clip's offset or frame count is negative";
-    if (row[1] > job_in_frames || row[3] > job_out_frames)
-        return "variable-rate ragged batch: a clip's frame counts exceed the job's in_frames / out_frames (the largest per-clip counts)";
+    // (sign and bounds: job_rules.h's, as on every clip table; the length rule is the clip's own step's)
+    const JobRowFault f = job_row_bounds(row, job_in_frames, job_out_frames);
+    if (f == kJobRowNegative) return "variable-rate ragged batch: a clip's offset or frame count is negative";
+    if (f == kJobRowAboveJob) return "variable-rate ragged batch: a clip's frame counts exceed the job's in_frames / out_frames (the largest per-clip counts)";
     if ((uint64_t)row[3] > vr_const_out_len((uint64_t)row[1], step))
         return "variable-rate ragged batch: a clip's out_frames exceed hipsoxr_plan_vr_out_len of its in_frames at its io ratio";
     if (row[3] > kVrRaggedMaxOut) return "variable-rate ragged batch: a clip of more than 2^30 outputs is not served";
