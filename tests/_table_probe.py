@@ -10,7 +10,11 @@ line, "TABLE_PROBE {...}": per case whether it held, what failed, and the larges
 A ROW is (L, M, k, small) of a HIPSOXR_PAIR / HIPSOXR_PAIR_F32 line; an INSTANCE is (form, kind), one kernel pointer of
 PairEntry: form pair2 (unit-stride columns, two blocks per transform), strided2_cp (interleaved channel pairs, one block of
 two channels per transform), strided2_st (strided columns, two blocks per transform); kind f32, f64, f32on64 (float32
-samples on float64 arithmetic, HIPSOXR_KERNEL_FFT_F64), i16, i32 (HIPSOXR_KERNEL_FFT_PCM)."""
+samples on float64 arithmetic, HIPSOXR_KERNEL_FFT_F64), i16, i32 (HIPSOXR_KERNEL_FFT_PCM).
+
+The float16 / bfloat16 forms of a row (fft_half_kernels: HIPSOXR_HALF_ROW / HIPSOXR_HALF_ROW_F32 over the instantiation
+lists) are HALF_INSTANCES, kinds f16 and bf16: parsed by parse_half, planned by case_plan(..., half=...), run by
+`_table_probe.py half:<child name>` for tests/test_gpu_fft_table_half.py — a module and children of their own."""
 import json
 import os
 import re
@@ -26,7 +30,13 @@ FLOOR_JSON = os.path.join(HERE, "golden", "fft_table_floor.json")
 # PairEntry's kernel pointers, in the struct's order (fft_launch_paired picks a field by layout, element type and selector)
 INSTANCES = (("pair2", "f32"), ("pair2", "f64"), ("pair2", "f32on64"), ("strided2_cp", "f32"), ("strided2_cp", "f64"),
              ("strided2_st", "f32"), ("strided2_st", "f64"), ("pair2", "i16"), ("pair2", "i32"), ("strided2_cp", "i16"))
+# HalfKernels' kernel pointers, in the struct's order (fft_launch_paired: by layout and element type)
+HALF_INSTANCES = (("pair2", "f16"), ("pair2", "bf16"), ("strided2_cp", "f16"), ("strided2_cp", "bf16"))
 WIDE_KINDS = ("f64", "f32on64", "i32")          # float64 arithmetic (`f64` of FftJobView)
+# float32 unit-stride columns and their half forms: the jobs of fft_one_round_pick (`j.elem == HIPSOXR_F32 || v.half`)
+F32_UNIT = (("pair2", "f32"), ("pair2", "f16"), ("pair2", "bf16"))
+FLOAT_TWIN = {("pair2", "f16"): ("pair2", "f32"), ("pair2", "bf16"): ("pair2", "f32"),
+              ("strided2_cp", "f16"): ("strided2_cp", "f32"), ("strided2_cp", "bf16"): ("strided2_cp", "f32")}
 QUALITIES = ("VHQ", "HQ")
 FFT, FFT_F64, FFT_PCM = 5, 8, 9                 # hipsoxr_kernel_t
 
@@ -118,6 +128,58 @@ def instances_of(row, macros):
     return [i for i in macros[row["macro"]] if i is not None]
 
 
+def _half_instance_of(expr):
+    """A HalfKernels initialiser -> (form, kind), or None for nullptr."""
+    if expr == "nullptr":
+        return None
+    kinds = {"_Float16": "f16", "__bf16": "bf16"}
+    m = re.fullmatch(r"k_fft_pair2<PairOf<NA, NB, NT>, float, (_Float16|__bf16)>", expr)
+    if m:
+        return ("pair2", kinds[m.group(1)])
+    m = re.fullmatch(r"k_fft_strided2<PairOf<NA, NB, NT>, float, true, (_Float16|__bf16)>", expr)
+    assert m, expr
+    return ("strided2_cp", kinds[m.group(1)])
+
+
+def parse_half(text=None):
+    """The float16 / bfloat16 table of fft_half_kernels -> dict macros: name -> the (form, kind) or None of the four
+    pointers of HIPSOXR_HALF_ROW / HIPSOXR_HALF_ROW_F32, as the #define writes them; entries: dicts NA, NB, nt, macro, list —
+    the HIPSOXR_PART*_SPECS lists that `halves[]` expands, in its order; nt_one_round: FFT_ONE_ROUND_NT."""
+    if text is None:
+        with open(FFT_SRC) as f:
+            text = f.read()
+    macros = {}
+    for name in ("HIPSOXR_HALF_ROW", "HIPSOXR_HALF_ROW_F32"):
+        parts = _split_top(_macro_body(text, name))
+        assert parts[:3] == ["NA", "NB", "NT"] and len(parts) == 3 + len(HALF_INSTANCES), parts
+        macros[name] = [_half_instance_of(e) for e in parts[3:]]
+    nt_one_round = int(re.search(r"#define FFT_ONE_ROUND_NT (\d+)", text).group(1))
+    m = re.search(r"static const HalfKernels halves\[\] = \{(.*?)\n    \};", text, re.S)
+    assert m, "fft_half_kernels: the table was not found"
+    body = re.sub(r"//[^\n]*", "", m.group(1))
+    pat = re.compile(r"(HIPSOXR_PART\d+_SPECS)\((HIPSOXR_HALF_ROW(?:_F32)?)\)")
+    assert not pat.sub("", body).strip(), "fft_half_kernels holds an entry that is not a list of specs: " + body.strip()[:200]
+    entries = []
+    for lst, macro in pat.findall(body):
+        line = re.search(r"#define " + lst + r"\(X\)([^\n]*)\n", text)
+        assert line, lst
+        specs = re.findall(r"X\(([^()]*)\)", line.group(1))
+        assert specs and not re.sub(r"X\([^()]*\)", "", line.group(1)).strip(), lst
+        for s in specs:
+            na, nb, nt = (t.strip() for t in s.split(","))
+            entries.append(dict(NA=int(na), NB=int(nb), nt=nt_one_round if nt == "FFT_ONE_ROUND_NT" else int(nt), macro=macro, list=lst))
+    return dict(macros=macros, entries=entries, nt_one_round=nt_one_round)
+
+
+def half_instances_of(row, half):
+    """The half instances fft_half_kernels finds for a row: the first entry with the row's (M k, L k, threads)."""
+    nt = half["nt_one_round"] if row["nt"] is None else row["nt"]
+    for e in half["entries"]:
+        if (e["NA"], e["NB"], e["nt"]) == (row["M"] * row["k"], row["L"] * row["k"], nt):
+            return [i for i in half["macros"][e["macro"]] if i is not None]
+    return []
+
+
 def rates_of(L, M):
     """A rate pair of the ratio out / in = L / M."""
     g = max(1, 48000 // max(L, M))
@@ -204,9 +266,11 @@ UNREACHABLE = {(row, inst): "float64 arithmetic never stays on the full-size row
                for row in _FULL_SIZE_ROWS_OF_RATIOS_WITH_A_HALF_SIZE_ROW for inst in INSTANCES if inst[1] in WIDE_KINDS}
 
 
-def case_plan(rows, macros, taps_of):
+def case_plan(rows, macros, taps_of, half=None):
     """taps_of(L, M, quality) -> taps per phase.  -> (cases, status): cases = dicts child, row, form, kind, quality, hop;
-    status[(row key, instance, quality)] = "case" | "inadmissible" | "unreachable"."""
+    status[(row key, instance, quality)] = "case" | "inadmissible" | "unreachable".  half (parse_half): the plan of the
+    float16 / bfloat16 instances instead — a half job takes the row the float32 job of its shape takes, on float32
+    arithmetic, under the same switches and in children of the same names."""
     envs = children(rows)
     cases, status = [], {}
     for r in rows:
@@ -214,14 +278,14 @@ def case_plan(rows, macros, taps_of):
         for q in QUALITIES:
             T = taps_of(r["L"], r["M"], q)
             hop = hop_out(r["L"], r["M"], T, r["k"])
-            for inst in instances_of(r, macros):
+            for inst in (instances_of(r, macros) if half is None else half_instances_of(r, half)):
                 key = (row_key(r), inst, q)
                 if not hop or pick_row(ratio, T, {}, False, False, macros) is None:
                     status[key] = "inadmissible"     # (fft_geometry: g.ok == false for the row, or for the ratio's full-size row)
                     continue
                 status[key] = "unreachable"
                 for name, env in envs.items():
-                    if pick_row(ratio, T, env, inst[1] in WIDE_KINDS, inst == ("pair2", "f32"), macros) is r:
+                    if pick_row(ratio, T, env, inst[1] in WIDE_KINDS, inst in F32_UNIT, macros) is r:
                         status[key] = "case"
                         cases.append(dict(child=name, row=row_key(r), form=inst[0], kind=inst[1], quality=q, hop=hop))
                         break
@@ -236,6 +300,16 @@ def case_id(c):
 # jobs of a case: output lengths around the seams of its work items, layouts of its form, inputs
 LAYOUTS = {"pair2": ("col", "batch3"), "strided2_cp": ("pair", "pair4x2"), "strided2_st": ("odd3", "slice")}
 SHAPES = {"col": (1, 1), "batch3": (3, 1), "pair": (1, 2), "pair4x2": (2, 4), "odd3": (1, 3), "slice": (1, 1)}   # clips, channels
+
+
+def shortest_in(out_len, t, L, M):
+    """The shortest input with at least t outputs."""
+    n = max(1, t * M // L)
+    while out_len(n) < t:
+        n += 1
+    while n > 1 and out_len(n - 1) >= t:
+        n -= 1
+    return n
 
 
 def out_lengths(c, out_len):
@@ -254,11 +328,7 @@ def out_lengths(c, out_len):
             got.append((out_len(n_in), n_in))
 
     for s in seams:
-        n = max(1, s * M // L)
-        while out_len(n) < s:
-            n += 1
-        while n > 1 and out_len(n - 1) >= s:
-            n -= 1                      # the shortest input with at least s outputs
+        n = shortest_in(out_len, s, L, M)
         if out_len(n) == s:
             add(n - 1)                  # ... the last length before the seam's end,
             add(n)                      # on it,
@@ -270,12 +340,7 @@ def out_lengths(c, out_len):
             add(n - 1)
             add(n)
     for t in (3 * h + 5, 7 * h + r):
-        n = max(1, t * M // L)
-        while out_len(n) < t:
-            n += 1
-        while n > 1 and out_len(n - 1) >= t:
-            n -= 1
-        add(n)
+        add(shortest_in(out_len, t, L, M))
     return got
 
 
@@ -531,5 +596,233 @@ def _run_child(name):
     print("TABLE_PROBE " + json.dumps(results))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# the child process of the float16 / bfloat16 instances (tests/test_gpu_fft_table_half.py)
+# pair2: col_odd = the input is base[1:] (2-byte aligned only), the output starts at element PAD + 1; col_o6 = aligned
+# input, output at PAD + 6 (4-byte aligned, inside a 16-byte granule) — hop_out is even, so with a granule-aligned output
+# the store loop would never meet an odd shift.  strided2_cp: pair_o1f = input and output one frame in (4-byte, not 8-byte
+# aligned: still one aligned word per frame, still fused).
+HALF_LAYOUTS = {"pair2": ("col", "batch3", "col_odd", "col_o6"), "strided2_cp": ("pair", "pair4x2", "pair_o1f")}
+HALF_SHAPES = dict(SHAPES, col_odd=(1, 1), col_o6=(1, 1), pair_o1f=(1, 2))
+HALF_OFFSETS = {"col_odd": (1, PAD + 1, 8), "col_o6": (0, PAD + 6, 8), "pair_o1f": (1, PAD + 1, 2)}   # frames: input, output, longer buffer
+HALF_FORMAT = {"f16": (10, -14), "bf16": (7, -126)}     # stored significand bits, exponent of the smallest normal
+SUBNORMAL_SCALE = 2.0 ** -12                            # float16, column 2 of batch3: RMS 2^-14, the smallest normal
+
+
+def half_ulp(y, kind):
+    """Half the spacing of the half type at |y| (float64): subnormal spacing below the smallest normal."""
+    bits, emin = HALF_FORMAT[kind]
+    e = np.floor(np.log2(np.maximum(np.abs(y), 2.0 ** emin)))
+    return 0.5 * 2.0 ** (e - bits)
+
+
+def half_bar(ref, kind):
+    """Pointwise bar of a half result against the float64 direct form: the float32 engine's own (4e-5 x RMS,
+    tests/test_gpu_fft.py) plus the one rounding, at the largest magnitude the float32 value can have."""
+    s = 4e-5 * rms(ref)
+    return s + half_ulp(np.abs(ref) + s, kind)
+
+
+def _run_half_child(name):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "python-soxr_amd"))
+    import ctypes as C
+    import torch
+    torch.cuda.init()
+    torch.zeros(1, device="cuda").cpu()
+    from soxr_amd import _native as nat, device as dev
+    from oracle import oracle as o
+    o.lib()
+    log = LogTail(os.environ["HIPSOXR_DEBUG_LAUNCH_LOG"])
+    rows, macros = parse_table()
+    half = parse_half()
+    plans = {}
+
+    def plan_of(L, M, q):
+        if (L, M, q) not in plans:
+            plans[(L, M, q)] = dev.Plan(*rates_of(L, M), q)
+            assert (plans[(L, M, q)].L, plans[(L, M, q)].M) == (L, M)
+        return plans[(L, M, q)]
+
+    cases, _ = case_plan(rows, macros, lambda L, M, q: plan_of(L, M, q).taps, half=half)
+    results = {}
+    tdt = {"f16": torch.float16, "bf16": torch.bfloat16}
+
+    def bits(t):
+        return t.contiguous().view(torch.int16)
+
+    def buffers(layout, cols, n_out):
+        """cols: the columns as host tensors of the half type, clip-major.  -> the base tensor of the input (host), the
+        frame its view starts at, the shape of the padded output buffer, the index of the result inside it."""
+        clips, ch = HALF_SHAPES[layout]
+        x = torch.stack(cols).reshape(clips, ch, -1).permute(0, 2, 1).contiguous()   # [clips, frames, channels]
+        i_off, o_off, more = HALF_OFFSETS.get(layout, (0, PAD, 0))
+        idx = (slice(o_off, o_off + n_out),)
+        if ch == 1 and clips == 1:
+            base, shape = x[0, :, 0], (n_out + 2 * PAD + more,)
+        elif clips == 1:
+            base, shape = x[0], (n_out + 2 * PAD + more, ch)
+        else:
+            base, shape, idx = x, (clips, n_out + 2 * PAD, ch), (slice(None),) + idx
+        if i_off:
+            base = torch.cat([torch.zeros_like(base[:i_off]), base])
+        return base.contiguous(), i_off, shape, idx
+
+    def launch(plan, xt, buf, idx):
+        """One job into the padded buffer -> (result as [columns, frames] host tensor, sentinels intact, log lines)."""
+        buf.fill_(SENT)
+        log.take()
+        dev.resample_tensor(plan, xt, out=buf[idx], kernel=FFT)
+        torch.cuda.synchronize()
+        lines = log.take()
+        b = buf.cpu()
+        y = b[idx]
+        outside = b.clone()
+        outside[idx] = SENT
+        y3 = y[None, :, None] if y.ndim == 1 else (y[None] if y.ndim == 2 else y)
+        return y3.permute(0, 2, 1).reshape(-1, y3.shape[1]).contiguous(), bool((outside == SENT).all()), lines
+
+    def raw_ragged(plan, dtype, x, out, table):
+        j = nat.Job()
+        j.in_, j.out, j.elem, j.kernel = x.data_ptr(), out.data_ptr(), dev._torch_elem(dtype), FFT
+        j.n_clips, j.n_channels = table.shape[0], 1
+        j.in_frame_stride, j.in_chan_stride, j.out_frame_stride, j.out_chan_stride = 1, 1, 1, 1
+        j.in_frames, j.out_frames = int(table[:, 1].max()), int(table[:, 3].max())
+        j.clip_table = table.ctypes.data
+        nat.check(nat.lib.hipsoxr_run_device(plan.handle, C.byref(j), torch.cuda.current_stream().cuda_stream))
+
+    for c in cases:
+        if c["child"] != name:
+            continue
+        cid = case_id(c)
+        print("TABLE_CASE", cid, flush=True)
+        L, M, k, small = c["row"]
+        q, kind, form = c["quality"], c["kind"], c["form"]
+        dt = tdt[kind]
+        plan = plan_of(L, M, q)
+        fails, figs, jobs = [], {}, 0
+        want = dict(form=form, L=str(L), M=str(M), k=str(k), small=str(small), kind=kind, hop_out=str(c["hop"]), window="0")
+
+        def check_line(lines, want, tag):
+            if len(lines) != 1:
+                fails.append(f"{tag}: {len(lines)} launch log lines: {lines}")
+                return
+            bad = {f: (lines[0].get(f), v) for f, v in want.items() if lines[0].get(f) != v}
+            if bad:
+                fails.append(f"{tag}: served by {lines[0]} — (got, wanted) {bad}")
+
+        def signal(n_in, col, scale=1.0):
+            """The master Gaussian (x scale, a power of two), rounded to the half type: a host tensor."""
+            return torch.from_numpy(master(L, M, n_in, col) * scale).to(dt)
+
+        def identity(yh, yf, tag):
+            """half result == float32 twin rounded once, bit for bit"""
+            diff = (bits(yh) != bits(yf.to(dt))).reshape(-1)
+            if bool(diff.any()):
+                at = int(diff.nonzero()[0])
+                fails.append(f"{tag}: {int(diff.sum())} of {diff.numel()} elements differ from the float32 twin rounded once, the first at {at}")
+
+        def oracle_bar(yh, xh, key, n_out, tag, subnormal=False):
+            """every point of a column against the float64 direct form on the widened input"""
+            ref = oracle_ref(o, L, M, q, xh.double().numpy(), key + (kind,))
+            if ref.shape != (n_out,):
+                fails.append(f"{tag}: oracle length {ref.shape}")
+                return
+            if subnormal:
+                n_sub = int(np.count_nonzero((np.abs(ref) > 0) & (np.abs(ref) < 2.0 ** -14)))
+                if not n_sub > n_out / 10:
+                    fails.append(f"{tag}: the subnormal column is vacuous: {n_sub} of {n_out} reference outputs in (0, 2^-14)")
+            share = float((np.abs(yh.double().numpy() - ref) / half_bar(ref, kind)).max())
+            figs["oracle"] = max(figs.get("oracle", 0.0), share)
+            if not share <= 1.0:
+                fails.append(f"{tag}: |y - ref| reaches {share:.4g} of 4e-5 x RMS + half an ulp")
+
+        for n_out, n_in in out_lengths(c, plan.out_len):
+            for layout in HALF_LAYOUTS[form]:
+                tag = f"n_out={n_out} {layout}"
+                jobs += 1
+                ncols = HALF_SHAPES[layout][0] * HALF_SHAPES[layout][1]
+                sub = {2} if (kind == "f16" and layout == "batch3") else set()
+                cols = [signal(n_in, col, SUBNORMAL_SCALE if col in sub else 1.0) for col in range(ncols)]
+                try:
+                    base, i_off, shape, idx = buffers(layout, cols, n_out)
+                    xh = base.cuda()
+                    xf = xh.float()
+                    bufh, buff = torch.empty(shape, dtype=dt, device="cuda"), torch.empty(shape, dtype=torch.float32, device="cuda")
+                    yh, intact, lines = launch(plan, xh[i_off:], bufh, idx)
+                    if layout == HALF_LAYOUTS[form][0]:
+                        yh2, intact2, _ = launch(plan, xh[i_off:], bufh, idx)
+                        if not torch.equal(bits(yh), bits(yh2)):
+                            fails.append(f"{tag}: two runs of the job differ")
+                        intact = intact and intact2
+                    yf, intactf, flines = launch(plan, xf[i_off:], buff, idx)
+                except RuntimeError as e:
+                    fails.append(f"{tag}: {e}; launch log: {log.take()}")
+                    continue
+                check_line(lines, want, tag)
+                check_line(flines, dict(want, kind="f32"), tag + " (float32 twin)")
+                if tuple(yh.shape) != (ncols, n_out) or yf.shape != yh.shape:
+                    fails.append(f"{tag}: result shape {tuple(yh.shape)}, twin {tuple(yf.shape)}")
+                    continue
+                if not (intact and intactf):
+                    fails.append(f"{tag}: a sentinel beside the result was overwritten")
+                identity(yh, yf, tag)
+                for col in range(ncols):
+                    oracle_bar(yh[col], cols[col], (n_in, "2s" if col in sub else col), n_out, f"{tag} column {col}", col in sub)
+
+        if form == "pair2":
+            # one ragged job (a clip table): the 3 hop + 5 input, one frame short of the two-item seam, 1 frame and none,
+            # packed at odd element offsets, guard elements between the outputs
+            tag = "ragged"
+            jobs += 1
+            h = c["hop"]
+            frames = [shortest_in(plan.out_len, 3 * h + 5, L, M), shortest_in(plan.out_len, 2 * h, L, M) - 1, 1, 0]
+            n_outs = [plan.out_len(n) for n in frames]
+            in_off, out_off, pos_i, pos_o = [], [], 1, PAD + 1
+            for n, m in zip(frames, n_outs):
+                in_off.append(pos_i)
+                out_off.append(pos_o)
+                pos_i += n + (1 if (pos_i + n) % 2 == 0 else 2)           # the next clip starts at an odd element again
+                pos_o += m + (PAD + 1 if (pos_o + m + PAD + 1) % 2 else PAD)
+            assert all(v % 2 for v in in_off + out_off)
+            table = np.ascontiguousarray(np.stack([in_off, frames, out_off, n_outs], axis=1), dtype=np.int64)
+            clips = [signal(n, 0) for n in frames]
+            x = torch.zeros(pos_i + PAD, dtype=dt)
+            for a, n, s in zip(in_off, frames, clips):
+                x[a:a + n] = s
+            try:
+                xh = x.cuda()
+                outh = torch.full((pos_o + PAD,), float(SENT), dtype=dt, device="cuda")
+                outf = torch.full((pos_o + PAD,), float(SENT), dtype=torch.float32, device="cuda")
+                log.take()
+                raw_ragged(plan, dt, xh, outh, table)
+                torch.cuda.synchronize()
+                lines = log.take()
+                raw_ragged(plan, torch.float32, xh.float(), outf, table)
+                torch.cuda.synchronize()
+                flines = log.take()
+                check_line(lines, dict(want, ragged="4"), tag)
+                check_line(flines, dict(want, kind="f32", ragged="4"), tag + " (float32 twin)")
+                yh, yf = outh.cpu(), outf.cpu()
+                identity(yh, yf, tag)                                      # (77 is exact in all three types: the guards compare too)
+                guard = torch.ones(yh.shape[0], dtype=torch.bool)
+                for a, m in zip(out_off, n_outs):
+                    guard[a:a + m] = False
+                if not bool((yh[guard] == SENT).all() and (yf[guard] == SENT).all()):
+                    fails.append(f"{tag}: guard elements between packed clips were written")
+                for i, (a, m, n) in enumerate(zip(out_off, n_outs, frames)):
+                    if m:
+                        oracle_bar(yh[a:a + m], clips[i], (n, 0), m, f"{tag} clip {i}")
+            except RuntimeError as e:
+                fails.append(f"{tag}: {e}; launch log: {log.take()}")
+
+        results[cid] = dict(ok=not fails, jobs=jobs, fails=fails[:6], n_fails=len(fails), share_of_bar={k_: round(v, 4) for k_, v in figs.items()})
+        print("TABLE_RESULT", cid, json.dumps(results[cid]), flush=True)
+    print("TABLE_PROBE " + json.dumps(results))
+
+
 if __name__ == "__main__":
-    _run_child(sys.argv[1])
+    if sys.argv[1].startswith("half:"):
+        _run_half_child(sys.argv[1][len("half:"):])
+    else:
+        _run_child(sys.argv[1])

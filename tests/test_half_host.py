@@ -81,7 +81,8 @@ def test_element_types_above_bf16_stay_invalid():
 def test_every_table_row_has_its_half_kernels():
     """A half job takes the row the float32 job takes, so every row of fft_pairs needs float16 / bfloat16 instances: the
     half table (fft_half_kernels) is written from the instantiation lists, keyed by (N_in, N_out, threads) — every row of the
-    schedule table is in exactly one of them, and each list is compiled in a unit of its own."""
+    schedule table is in exactly one of them, and each list is compiled in a unit of its own.  (Names only: the kernels
+    themselves are run, instance by instance, by tests/test_gpu_fft_table_half.py; its case plan is held by tests/test_fft_table.py.)"""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import _table_probe as tp
