@@ -207,6 +207,111 @@ __device__ __forceinline__ void fft_pass_ct(const C *W, Load load, Store store, 
     }
 }
 
+// own += s * other in place for n consecutive floats of v, `other` = the neighbouring lane's (lane ^ 1) value through DPP.
+// By hand: before register allocation the product is a three-address v_fma_f32, which has no DPP encoding on gfx950, so
+// the compiler leaves __builtin_amdgcn_update_dpp as a v_mov_b32_dpp in front of every v_fmac (two instructions per
+// real).  One block, so that ONE s_nop covers the two wait states a DPP read needs behind the vector instruction that
+// wrote its source (the hazard recogniser does not look into inline assembly); no instruction of the block reads what
+// another one wrote.
+#define FFT_PAIR_X(n) "v_fmac_f32_dpp %" #n ", %" #n ", %[s] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+__device__ __forceinline__ void pair_exchange(float2 (&u)[7], float s)
+{
+    asm volatile("s_nop 1\n\t" FFT_PAIR_X(0) FFT_PAIR_X(1) FFT_PAIR_X(2) FFT_PAIR_X(3) FFT_PAIR_X(4) FFT_PAIR_X(5) FFT_PAIR_X(6)
+                 FFT_PAIR_X(7) FFT_PAIR_X(8) FFT_PAIR_X(9) FFT_PAIR_X(10) FFT_PAIR_X(11) FFT_PAIR_X(12) FFT_PAIR_X(13)
+                 : "+v"(u[0].x), "+v"(u[0].y), "+v"(u[1].x), "+v"(u[1].y), "+v"(u[2].x), "+v"(u[2].y), "+v"(u[3].x), "+v"(u[3].y),
+                   "+v"(u[4].x), "+v"(u[4].y), "+v"(u[5].x), "+v"(u[5].y), "+v"(u[6].x), "+v"(u[6].y)
+                 : [s] "v"(s));
+}
+__device__ __forceinline__ void pair_exchange(float2 (&u)[8], float s)
+{
+    asm volatile("s_nop 1\n\t" FFT_PAIR_X(0) FFT_PAIR_X(1) FFT_PAIR_X(2) FFT_PAIR_X(3) FFT_PAIR_X(4) FFT_PAIR_X(5) FFT_PAIR_X(6)
+                 FFT_PAIR_X(7) FFT_PAIR_X(8) FFT_PAIR_X(9) FFT_PAIR_X(10) FFT_PAIR_X(11) FFT_PAIR_X(12) FFT_PAIR_X(13) FFT_PAIR_X(14) FFT_PAIR_X(15)
+                 : "+v"(u[0].x), "+v"(u[0].y), "+v"(u[1].x), "+v"(u[1].y), "+v"(u[2].x), "+v"(u[2].y), "+v"(u[3].x), "+v"(u[3].y),
+                   "+v"(u[4].x), "+v"(u[4].y), "+v"(u[5].x), "+v"(u[5].y), "+v"(u[6].x), "+v"(u[6].y), "+v"(u[7].x), "+v"(u[7].y)
+                 : [s] "v"(s));
+}
+#undef FFT_PAIR_X
+
+// Lane-pair form of a radix-14 pass (one-round float32 kernels, where a pass of N/14 butterflies leaves two of five waves
+// idle at the barrier): lanes 2j and 2j + 1 share butterfly j.  14 = 2 x 7 by the Good-Thomas maps of dft_pfa<2, 7>, the
+// two dimensions taken in the other order: lane a (= tid & 1) holds the residue class n1 = a — inputs
+// t = (7a + 2i) mod 14, i < 7 — twiddles them, runs dft_r<7>, and the 2-point stage is one v_fmac_f32 per real whose
+// multiplicand comes from the neighbour through DPP (quad_perm [1,0,3,2]): no LDS trip, no barrier.  Lane a keeps
+// output k1 = a: X[(7a + 8i) mod 14] = y0[i] + (-1)^a y1[i].  Lane 1 carries -y1 (its twiddles are read half a turn
+// further on in W), so both lanes compute own + s * other with s = -1 / +1: one instruction stream.
+// Everything that depends on t is base + immediate: t = 2i + 7a (i <= 3) or 2i - 7a (i >= 4), so a lane has two input
+// bases (n_lo, n_hi); output m = 8i mod 14 + 7a (i even) or - 7a (i odd), two output bases (all kept non-negative).  `load_at(n)` / `store_at(n, v)`
+// take element indices of the pass input / output.
+// Twiddles w^(t k): three table entries per lane — g = w^2, b_lo = w^(7a), b_hi = w^(8 - 7a), each rounded once — and
+// w^t = b_lo g^i (i <= 3) or b_hi g^(i - 4): seven products instead of twelve, error factor <= 1 + 3 (see fft_pass_ct: <= 5).
+template <int N, int Ns, int SIGN, int NT, bool SYNC_BEFORE_STORE, typename C, typename LoadAt, typename StoreAt>
+__device__ __forceinline__ void fft_pass_pair14(const C *W, LoadAt load_at, StoreAt store_at, const int tid)
+{
+    constexpr int R = 14, nb = N / R, wstep = N / (Ns * R);
+    static_assert(sizeof(C) == 8 && N % 2 == 0 && Ns > 1 && 2 * nb <= NT, "lane-pair radix-14 pass: float32, a twiddled pass, one half-butterfly per thread");
+    const int j = tid >> 1, a = tid & 1;
+    const bool live = 2 * nb == NT || j < nb; // (2 nb is even: both lanes of a pair are in or out)
+    const int k = j % Ns;
+    C u[7], g, b_lo, b_hi;
+    if (live) {
+        const int kw = k * wstep, half = a * (N / 2);
+        g = W[2 * kw];
+        b_lo = W[7 * a * kw + half];       // 1 or -w^7
+        b_hi = W[(8 - 7 * a) * kw + half]; // w^8 or -w
+        const int n_lo = j + 7 * a * nb, n_hi = j + (8 - 7 * a) * nb; // inputs 0 / 7 and 8 / 1: non-negative bases
+#pragma unroll
+        for (int i = 0; i < 7; ++i) u[i] = i <= 3 ? load_at(n_lo + 2 * i * nb) : load_at(n_hi + (2 * i - 8) * nb);
+    }
+    if (SYNC_BEFORE_STORE) __syncthreads(); // in place: every input of the pass is in registers
+    if (live) {
+        const C g2 = cmul(g, g), g3 = cmul(g2, g);
+        u[0] = cmul(u[0], b_lo); u[1] = cmul(u[1], cmul(b_lo, g)); u[2] = cmul(u[2], cmul(b_lo, g2)); u[3] = cmul(u[3], cmul(b_lo, g3));
+        u[4] = cmul(u[4], b_hi); u[5] = cmul(u[5], cmul(b_hi, g)); u[6] = cmul(u[6], cmul(b_hi, g2));
+        dft_r<7, SIGN>(u);
+        const float s = a ? 1.f : -1.f;
+        pair_exchange(u, s);
+        const int o = (j - k) * R + k, o_ev = o + 7 * a * Ns, o_od = o + (8 - 7 * a) * Ns; // outputs 0 / 7 and 8 / 1
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            if (i % 2 == 0) store_at(o_ev + ((8 * i) % R) * Ns, u[i]);
+            else store_at(o_od + ((8 * i) % R - 8) * Ns, u[i]);
+        }
+    }
+}
+
+// Lane-pair form of a radix-16 FIRST pass (Ns = 1: no external twiddles; its N/16 butterflies fill little more than two of
+// five waves): 16 = 2 x 8 by decimation in time.  Lane a of the pair of butterfly j loads inputs t = 2i + a, i < 8 —
+// `load(j + a N/16, 2i)`: half the loads per lane — runs dft_r<8>, multiplies by the internal factors (lane 0: 1; lane 1:
+// -w16^q, per-lane constants), and X[q + 8a] = own + s * other as in fft_pass_pair14.  `store(j, a, q, v)` takes output q + 8a.
+template <int N, int SIGN, int NT, bool SYNC_BEFORE_STORE, typename C, typename Load, typename Store>
+__device__ __forceinline__ void fft_pass_pair16(Load load, Store store, const int tid)
+{
+    constexpr int nb = N / 16;
+    constexpr double PI2 = 6.283185307179586476925286766559;
+    static_assert(sizeof(C) == 8 && 2 * nb <= NT, "lane-pair radix-16 pass: float32, one half-butterfly per thread");
+    const int j = tid >> 1, a = tid & 1;
+    const bool live = 2 * nb == NT || j < nb;
+    C u[8];
+    if (live) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) u[i] = load(j + a * nb, 2 * i);
+    }
+    if (SYNC_BEFORE_STORE) __syncthreads();
+    if (live) {
+        dft_r<8, SIGN>(u);
+        const float s = a ? 1.f : -1.f;
+        u[0] = C(-s * u[0].x, -s * u[0].y);
+#pragma unroll
+        for (int q = 1; q < 8; ++q) {
+            const float wr = -(float)__builtin_cos(PI2 * q / 16), wi = -(float)(SIGN * __builtin_sin(PI2 * q / 16));
+            u[q] = cmul(u[q], C(a ? wr : 1.f, a ? wi : 0.f));
+        }
+        pair_exchange(u, s);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) store(j, a, q, u[q]);
+    }
+}
+
 // Three-pass transform: first pass input from `first_load`, last pass output to `last_store`, in place in between.
 // LDS bank conflicts: pass loads are contiguous across lanes (conflict-free); pass stores run in groups of Ns consecutive
 // elements, so only the FIRST pass (Ns = 1: lane stride = R0 elements) can conflict.  An odd-ish R0 (5, 21: stride 40 /
@@ -229,7 +334,9 @@ __device__ __forceinline__ void fft_pass_ct(const C *W, Load load, Store store, 
 // tw (PassTabs): the twiddled passes named by TABS (bit 0: pass 2, bit 1: pass 3) read their factors from the
 // transform's per-pass tables — pass 2's [t][k] block of (R1 - 1) R0 entries, then pass 3's of (R2 - 1) R0 R1 (host side:
 // pass_tables, which lays out both whatever TABS says) — instead of forming them from W.
-template <int N, int SIGN, int NT, int R0, int R1, int R2, bool SWZ, bool LASTSYNC, int TABS = 3, typename C, typename Load, typename Store, typename StoreAlt, typename Tw = NoTabs>
+// SPLIT: the passes that run in the lane-pair form (bit 0: a radix-16 pass 1, fft_pass_pair16; bit 1: a radix-14 pass 2,
+// fft_pass_pair14).
+template <int N, int SIGN, int NT, int R0, int R1, int R2, bool SWZ, bool LASTSYNC, int TABS = 3, int SPLIT = 0, typename C, typename Load, typename Store, typename StoreAlt, typename Tw = NoTabs>
 __device__ __forceinline__ void fft_ct3(FFT_STAMP_DECL C *buf, const C *W, Load first_load, Store last_store, bool first_in_lds, StoreAlt last_store_alt,
                                         bool use_alt, const int tid, Tw tw = Tw())
 {
@@ -250,12 +357,24 @@ __device__ __forceinline__ void fft_ct3(FFT_STAMP_DECL C *buf, const C *W, Load 
         else buf[o + t] = v;
     };
     // pass 0 (Ns = 1): when its input is not in LDS nothing has to be protected before storing
-    if (first_in_lds) fft_pass_ct<N, 1, R0, SIGN, NT, true>(W, first_load, swz_store, tid);
+    if constexpr ((SPLIT & 1) != 0) {
+        static_assert(R0 == 16 && SWZ, "lane-pair pass 1: radix 16 into the swizzled layout");
+        // swz_store's element 16 j + ((q + 8 a) ^ (j & 15)): the lane's byte offset XOR 64 a, then XOR a constant per output
+        auto pair_store = [&](int j, int a, int q, C v) {
+            *reinterpret_cast<C *>(reinterpret_cast<char *>(buf) + (((unsigned)((16 * j | (j & 15)) * (int)sizeof(C)) ^ (unsigned)(a * 8 * (int)sizeof(C))) ^ (unsigned)(q * (int)sizeof(C)))) = v;
+        };
+        if (first_in_lds) fft_pass_pair16<N, SIGN, NT, true, C>(first_load, pair_store, tid);
+        else fft_pass_pair16<N, SIGN, NT, false, C>(first_load, pair_store, tid);
+    } else if (first_in_lds) fft_pass_ct<N, 1, R0, SIGN, NT, true>(W, first_load, swz_store, tid);
     else fft_pass_ct<N, 1, R0, SIGN, NT, false>(W, first_load, swz_store, tid);
     FFT_STAMP();
     __syncthreads();
     FFT_STAMP();
-    if constexpr (TABS & 1) fft_pass_ct<N, R0, R1, SIGN, NT, true, 0>(W, swz_load, lds_store1, tid, tw);
+    if constexpr ((SPLIT & 2) != 0) {
+        static_assert(R1 == 14 && !(TABS & 1), "lane-pair pass 2: radix 14, powers formed in registers");
+        fft_pass_pair14<N, R0, SIGN, NT, true>(W, [&](int n) -> C { if constexpr (SWZ) return buf[n ^ ((n >> 4) & 15)]; else return buf[n]; },
+                                               [&](int n, C v) { buf[n] = v; }, tid); // (lds_store1's layout: element o + t * R0)
+    } else if constexpr (TABS & 1) fft_pass_ct<N, R0, R1, SIGN, NT, true, 0>(W, swz_load, lds_store1, tid, tw);
     else fft_pass_ct<N, R0, R1, SIGN, NT, true>(W, swz_load, lds_store1, tid);
     FFT_STAMP();
     __syncthreads();
@@ -391,19 +510,38 @@ __global__ void __launch_bounds__(256, 2) k_fft_block(FftArgs a)
 // TABS_: which twiddled passes of both transforms take their factors from per-pass tables (FftArgs::TWA / TWB, float32;
 // the one-round kernels; bits as FFT_ONE_ROUND_TABS).  fwd / inv_staged then get the transform's PassTabs; everything
 // else leaves the argument out.
+// Which passes of the one-round float32 kernels run in the lane-pair form (fft_pass_pair16 / fft_pass_pair14): bit 0 / 1 =
+// forward pass 1 / 2, bit 2 / 3 = inverse pass 1 / 2.  What a kernel HAS: 2240 x 2058 a radix-16 forward pass 1 from HBM
+// and both radix-14 passes 2 (11); 2058 x 2240 both passes 2 (10) — its radix-16 pass is the inverse's first, whose loader
+// decides the side of the spectrum per compile-time input: not built.  The kernels of 20 periods keep the plain passes:
+// 2940 / 14 = 210 butterflies are 420 halves, two rounds of the 320 threads — no shorter than one round of whole
+// butterflies — and 3200 = 16 * 20 * 10 has no radix-14 pass.
+// What a kernel KEEPS is what was measured to gain (k = 14 forced, 60 s mono, us per launch, three alternated runs each,
+// spread <= 0.03: profiles/NOTES_one_round_split.md):
+//   2240 x 2058  parent 9.86; forward pass 1 alone 10.60, forward pass 2 alone 10.70, inverse pass 2 alone 9.56, all 10.62
+//   2058 x 2240  parent 9.70; forward pass 2 alone 9.79, inverse pass 2 alone 9.56, both 9.45
+// The forward passes of 2240 read and write LDS rows a multiple of 256 bytes apart from the two lanes of a pair (two-way
+// bank conflicts on every access); why the conflict-free radix-16 pass loses as much is not understood.
+// -DFFT_ONE_ROUND_SPLIT=mask (A/B builds): that mask in both kernels instead, cut down to what each has.
+#ifdef FFT_ONE_ROUND_SPLIT
+constexpr int pair_split(int NA, int NB) { return (NA == 2240 && NB == 2058 ? 11 : NA == 2058 && NB == 2240 ? 10 : 0) & (FFT_ONE_ROUND_SPLIT); }
+#else
+constexpr int pair_split(int NA, int NB) { return NA == 2240 && NB == 2058 ? 8 : NA == 2058 && NB == 2240 ? 10 : 0; }
+#endif
 template <int NA_, int NB_, int NT_, int A0, int A1, int A2, bool ASWZ, int B0, int B1, int B2, bool BSWZ, int TABS_ = 0>
 struct PairSpec {
     static constexpr int NA = NA_, NB = NB_, NT = NT_;
     static constexpr int RA0 = A0, RA2 = A2, RB0 = B0, RB2 = B2;
     static constexpr int TABS = TABS_; // bit 0: pass 2, bit 1: pass 3
+    static constexpr int SPLIT = pair_split(NA_, NB_); // lane-pair passes (float32 one-round kernels): bits 0-1 forward pass 1, 2; bits 2-3 inverse pass 1, 2
     static constexpr int TWA_N = (A1 - 1) * A0 + (A2 - 1) * A0 * A1, TWB_N = (B1 - 1) * B0 + (B2 - 1) * B0 * B1; // entries of the per-pass tables
-    template <typename C, typename Ld, typename St, typename Tw = NoTabs> static __device__ __forceinline__ void fwd(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x, Tw tw = Tw())
-    { fft_ct3<NA, -1, NT, A0, A1, A2, ASWZ, false, TABS>(FFT_STAMP_ARGS b, W, ld, st, false, st, false, tid, tw); }
+    template <int SPLIT2 = 0, typename C, typename Ld, typename St, typename Tw = NoTabs> static __device__ __forceinline__ void fwd(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x, Tw tw = Tw())
+    { fft_ct3<NA, -1, NT, A0, A1, A2, ASWZ, false, TABS, SPLIT2>(FFT_STAMP_ARGS b, W, ld, st, false, st, false, tid, tw); }
     template <typename C, typename Ld, typename St> static __device__ __forceinline__ void inv(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, int tid = (int)threadIdx.x)
     { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, false>(FFT_STAMP_ARGS b, W, ld, st, true, st, false, tid); }
     // last pass stores into LDS in another layout (output staging): all its inputs must be in registers first
-    template <typename C, typename Ld, typename St, typename StAlt, typename Tw = NoTabs> static __device__ __forceinline__ void inv_staged(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, StAlt st_alt, bool use_alt, Tw tw = Tw())
-    { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, true, TABS>(FFT_STAMP_ARGS b, W, ld, st, true, st_alt, use_alt, (int)threadIdx.x, tw); }
+    template <int SPLIT2 = 0, typename C, typename Ld, typename St, typename StAlt, typename Tw = NoTabs> static __device__ __forceinline__ void inv_staged(FFT_STAMP_DECL C *b, const C *W, Ld ld, St st, StAlt st_alt, bool use_alt, Tw tw = Tw())
+    { fft_ct3<NB, +1, NT, B0, B1, B2, BSWZ, true, TABS, SPLIT2>(FFT_STAMP_ARGS b, W, ld, st, true, st_alt, use_alt, (int)threadIdx.x, tw); }
 };
 // Three-pass schedule of each transform length in use (first radix 21: conflict-free as it is; first radix 16:
 // swizzled layout between pass 1 and 2).  4410 = 21*14*15 is the order the product runs (configs[2] 47 us, against
@@ -539,6 +677,9 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     // float16 / bfloat16 samples (HALF; float arithmetic): the same staging — the kernel is the float32 kernel up to the
     // store loop, which rounds each staged value once to the half type: no dither, no clip count
     constexpr bool PCM = std::is_integral<IO>::value, HALF = is_half_io<IO>::value, CONV = PCM || HALF;
+    // lane-pair passes (the one-round block sizes: float arithmetic only) — their float16 / bfloat16 forms take them too:
+    // a half job is the float32 job's arithmetic up to the store loop (tests/test_gpu_fft_table_half.py holds them to it)
+    constexpr int SPLIT = std::is_same<Real, float>::value ? Spec::SPLIT : 0;
     static_assert(!HALF || std::is_same<Real, float>::value, "float16 / bfloat16 samples: float32 arithmetic");
     typedef typename std::conditional<CONV, Real, IO>::type ST;
     ST *stage = reinterpret_cast<ST *>(smem_raw);
@@ -575,11 +716,11 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
         const int64_t left = (in_frames - ina) * ES; // bytes from the first block's first sample to the end of the column
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             uniform_ptr((void *)(xin + ina)), 0, __builtin_amdgcn_readfirstlane((int)(left < 0 ? 0 : left > 0x40000000 ? 0x40000000 : left)), 0x00020000);
-        Spec::fwd(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C { // (the butterfly's own offset: one VGPR for all t)
+        Spec::template fwd<SPLIT & 3>(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C { // (the butterfly's own offset: one VGPR for all t)
             return C((Real)buf_load_real<IO>(rs, j * ES, t * nbA * ES), (Real)buf_load_real<IO>(rs, j * ES, (t * nbA + hop_in) * ES));
         }, last_fwd_store, (int)threadIdx.x, twa);
     } else { // the first item of a column reaches before its start: explicit zero-extension
-        Spec::fwd(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C {
+        Spec::template fwd<SPLIT & 3>(FFT_STAMP_ARGS buf, PairTabs<Real>::wa(a), [&](int j, int t) -> C {
             const int64_t la = ina + j + t * nbA, lb = la + hop_in;
             return C((la >= a.in_lo && la < in_frames) ? (Real)xin[la] : (Real)0, (lb >= a.in_lo && lb < in_frames) ? (Real)xin[lb] : (Real)0);
         }, last_fwd_store, (int)threadIdx.x, twa);
@@ -602,7 +743,7 @@ __device__ __forceinline__ void pair2_item(const FftArgs &a, unsigned char *smem
     // the kept run begins inside the first stride of outputs and ends inside the last one (`typical`, wave-uniform):
     // then only outputs t = 0 and t = RB2 - 1 compare per lane, the others are stored as they are.
     const bool typical = v0 >= 0 && v0 <= NsL && v1 >= NB - NsL && v1 <= NB;
-    Spec::inv_staged(FFT_STAMP_ARGS buf, PairTabs<Real>::wb(a), h_load,
+    Spec::template inv_staged<(SPLIT >> 2) & 3>(FFT_STAMP_ARGS buf, PairTabs<Real>::wb(a), h_load,
         [&](int o, int t, C w) { // typical geometry
             ST *const sa = stage + (o - v0 + sh) + t * NsL, *const sb = sa + hop_out;
             if (t == 0) { if (o >= v0) { *sa = (ST)w.x; *sb = (ST)w.y; } }
@@ -1296,11 +1437,12 @@ static const HalfKernels *fft_half_kernels(const PairEntry &e)
 // workgroup that shares the CU adds.  Microseconds, least-squares fits per k over the mono and 2-column clips of 10 .. 90 s
 // below the throughput rule's size, k forced (tools/one_round_sweep.py; rows and fit: profiles/NOTES_one_round.md §3,
 // profiles/one_round_forced_k.json).
+// The k = 14 rows: refitted to the kernels with lane-pair passes (the same rows, one visit: profiles/NOTES_one_round_split.md §4).
 // More candidate block sizes of a ratio are more rows here and more entries in fft_pairs — no code.
 struct OneRoundCost { int64_t L, M; int k; float chain_us, queue_us; };
 static const OneRoundCost kOneRoundCost[] = {
-    {147, 160, 8, 6.29f, 0.79f}, {147, 160, 14, 7.70f, 1.26f}, {147, 160, 16, 8.01f, 1.24f}, {147, 160, 20, 8.72f, 1.57f}, {147, 160, 32, 9.72f, 2.85f}, // 48k -> 44.1k
-    {160, 147, 8, 6.81f, 0.89f}, {160, 147, 14, 7.63f, 1.19f}, {160, 147, 16, 8.02f, 1.29f}, {160, 147, 20, 8.56f, 1.48f}, {160, 147, 32, 9.93f, 2.63f}, // 44.1k -> 48k
+    {147, 160, 8, 6.29f, 0.79f}, {147, 160, 14, 7.65f, 1.06f}, {147, 160, 16, 8.01f, 1.24f}, {147, 160, 20, 8.72f, 1.57f}, {147, 160, 32, 9.72f, 2.85f}, // 48k -> 44.1k
+    {160, 147, 8, 6.81f, 0.89f}, {160, 147, 14, 7.21f, 1.20f}, {160, 147, 16, 8.02f, 1.29f}, {160, 147, 20, 8.56f, 1.48f}, {160, 147, 32, 9.93f, 2.63f}, // 44.1k -> 48k
 };
 // A candidate must beat the size rules' choice by more than this: the run-to-run spread of one row of that sweep (a tie
 // goes to the choice the thresholds make, so that nothing changes where nothing is gained)
