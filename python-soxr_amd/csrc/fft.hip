@@ -65,8 +65,8 @@ namespace hipsoxr {
 // One Stockham pass of a length-N transform with a run-time schedule (k_fft_block), IN PLACE in a single LDS buffer:
 // every thread reads the inputs of its butterflies into registers, the workgroup synchronises, then results are written
 // to their autosort positions.  Radix R, Ns = product of earlier radices, NB = max butterflies per thread.
-// W = table exp(SIGN*2*pi*i*m/N), m = 0..N-1 (L1/L2 resident); only the t = 1 twiddle of a butterfly is loaded, its
-// powers are formed in registers.
+// W = table exp(SIGN*2*pi*i*m/N), m = 0..N-1 (L1/L2 resident); the t = 1 twiddle of a butterfly is loaded — from radix 5
+// the t = 4 one as well — and the other powers are formed in registers.
 template <int R, int SIGN, int NB>
 __device__ __forceinline__ void fft_pass(cf *buf, int N, int Ns, const cf *W)
 {
@@ -83,12 +83,23 @@ __device__ __forceinline__ void fft_pass(cf *buf, int N, int Ns, const cf *W)
 #pragma unroll
             for (int t = 0; t < R; ++t) u[i][t] = buf[j + t * nb];
             if (Ns > 1) {
-                const cf w1 = W[k * wstep];
-                cf w = w1;
+                // w^t from w and, for the radices with t >= 4, a second entry w^4: w^(4a+b) = (w^4)^a w^b — t rounded
+                // products of ONE entry carry t times its phase error, which at the peak of an impulse (crest factor 70)
+                // is 4.6e-5 of the column's RMS with radix 16; with the second entry the factor is a + b <= 6
+                // (profiles/NOTES_fft_block.md; fft_pass_ct does the same from radix 10)
+                cf pw[4], w4 = make_float2(1.f, 0.f), base = w4;
+                pw[1] = W[k * wstep];
+                if (R >= 5) w4 = W[4 * k * wstep]; // 4 k wstep < 4 N / R < N
 #pragma unroll
                 for (int t = 1; t < R; ++t) {
-                    u[i][t] = cmul(u[i][t], w);
-                    if (t + 1 < R) w = cmul(w, w1);
+                    const int a4 = t / 4, b4 = t % 4;
+                    if (a4 == 0) {
+                        if (t > 1) pw[t] = cmul(pw[t - 1], pw[1]);
+                        u[i][t] = cmul(u[i][t], pw[t]);
+                    } else {
+                        if (b4 == 0) base = a4 == 1 ? w4 : cmul(base, w4);
+                        u[i][t] = cmul(u[i][t], b4 == 0 ? base : cmul(base, pw[b4]));
+                    }
                 }
             }
             dft_r<R, SIGN>(u[i]);
@@ -1288,6 +1299,10 @@ static const char *fft_build(const Plan &p, FftGeom *out, bool small, int force_
     if (pass_tables(g.N_in, -1, &twa) && pass_tables(g.N_out, +1, &twb)) { // (behind everything else: 16-byte aligned or not, the loads are 8 bytes)
         g.twa = tab.size(); g.twb = g.twa + twa.size();
         tab.resize(g.twb + twb.size());
+    } else {
+        // one length alone has a table schedule (k_fft_block at N_in = 3200, say, beside any N_out but 2940): no per-pass
+        // tables — `twa`, filled by the first call, must not reach the copy below, which would lay it over WA and WB at g.twa = 0
+        twa.clear(); twb.clear();
     }
     float2 *Hs = tab.data() + at.Hs;
     float *Hr = reinterpret_cast<float *>(tab.data() + at.Hr);
