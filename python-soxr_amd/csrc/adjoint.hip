@@ -82,6 +82,7 @@
 #include <mutex>
 #include <vector>
 
+#include "adjoint_rules.h" // kAdjRS, floor_div, ceil_div; the tables, the launch forms, the refusals
 #include "device.h"
 #include "job_rules.h"
 
@@ -92,9 +93,6 @@ namespace hipsoxr {
         hipError_t e_ = (expr);                             \
         if (e_ != hipSuccess) return hipGetErrorString(e_); \
     } while (0)
-
-static constexpr int kAdjRS = 16;        // phases per wave tile of k_adj_tile
-static constexpr int kAdjMinPeriods = 4; // k_adj_tile from this many (replicated) periods of input up
 
 struct AdjArgs {
     const void *gy;
@@ -123,9 +121,6 @@ struct AdjRaggedArgs : AdjArgs {
 };
 template <bool RAGGED> struct AdjArgsOf { typedef AdjArgs type; };
 template <> struct AdjArgsOf<true> { typedef AdjRaggedArgs type; };
-
-__host__ __device__ static inline int64_t floor_div(int64_t a, int64_t b) { int64_t q = a / b; return (a % b != 0 && a < 0) ? q - 1 : q; } // b > 0
-__host__ __device__ static inline int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
 
 __device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_r(double a, double b, double c) { return __builtin_fma(a, b, c); }
@@ -167,8 +162,8 @@ __global__ void __launch_bounds__(256) k_adj_gather(typename AdjArgsOf<RAGGED>::
 // ---------------------------------------------------------------------------------------------
 // k_adj_tile
 // ---------------------------------------------------------------------------------------------
-// Geometry (host-built, adj_build): "period" is the replicated period, Mc = c M inputs <- Lc = c L cotangent samples, c such
-// that Mc >= 16 and Lc >= 64.  Workgroup x takes periods [x pb, x pb + pb); its slab holds gy frames
+// Geometry (host-built, adjoint_rules.h adj_tables): "period" is the replicated period, Mc = c M inputs <- Lc = c L
+// cotangent samples, c such that Mc >= 16 and Lc >= 64.  Workgroup x takes periods [x pb, x pb + pb); its slab holds gy frames
 // [x pb Lc + dmin, + x_count) of cg channels, frame n of it at LDS element (n + pad (n / Lc)) cg + channel: rows of
 // Lc + pad frames — an odd count, so that the lanes of a wave (stride one row) fall on different banks.  Phase tile st
 // (phases s = 16 st .. 16 st + 15) reads slab frames e0[st] + ii (ii < I) of its lane's period, coefficient tab[st][ii][s].
@@ -375,15 +370,13 @@ __global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<
 // ---------------------------------------------------------------------------------------------
 // host: transposed bank, cache, launch
 // ---------------------------------------------------------------------------------------------
-struct AdjBank {
+struct AdjBank : AdjGeom { // (tile: the period fits LDS, tab and e0 exist)
     const Plan *plan = nullptr;
     int device = -1;
-    int64_t L = 1, M = 1, Lc = 1, Mc = 1;
-    int32_t Tt = 0, dmin = 0;
-    void *ct[2] = {nullptr, nullptr}; // [Tt][M], 0 = f32, 1 = f64
-    int32_t *d_lo = nullptr;          // [M]
-    bool tile = false;                // the period fits LDS: tables of k_adj_tile
-    int32_t n_st = 0, I = 0, wmax = 0, pad = 0;
+    int64_t L = 1, M = 1;
+    int32_t Tt = 0, dmin = 0, I = 0;
+    void *ct[2] = {nullptr, nullptr};  // [Tt][M], 0 = f32, 1 = f64
+    int32_t *d_lo = nullptr;           // [M]
     void *tab[2] = {nullptr, nullptr}; // [n_st][I][16]
     int32_t *e0 = nullptr;             // [n_st]
 };
@@ -422,65 +415,20 @@ static const char *adj_upload(void **dst, const std::vector<double> &src)
     return nullptr;
 }
 
+// adj_tables' tables on the device: the transposed bank with d_lo, then — where the plan has them — the tile tables with e0
 static const char *adj_build(const Plan &p, AdjBank *b)
 {
-    const int64_t L = p.L, M = p.M, H = p.T / 2;
-    const int32_t T = p.T;
-    b->L = L; b->M = M;
-    auto d_lo = [&](int64_t s) { return ceil_div((s - H) * L, M); };
-    auto d_hi = [&](int64_t s) { return ceil_div((s + H) * L, M) - 1; };
-    // coefficient of gy[q L + d] in gx[q M + s]: c[(d M) mod L][s + T/2 - 1 - floor(d M / L)], 0 outside the phase's terms
-    auto coef = [&](int64_t s, int64_t d) -> double {
-        if (d < d_lo(s) || d > d_hi(s)) return 0.0;
-        const int64_t nfl = floor_div(d * M, L), ph = d * M - nfl * L, j = s + H - 1 - nfl;
-        return (j >= 0 && j < T) ? p.bank[(size_t)(ph * T + j)] : 0.0;
-    };
-    int64_t Tt = 0;
-    std::vector<int32_t> lo((size_t)M);
-    for (int64_t s = 0; s < M; ++s) {
-        lo[(size_t)s] = (int32_t)d_lo(s);
-        Tt = std::max(Tt, d_hi(s) - d_lo(s) + 1);
+    const AdjTables t = adj_tables(p.L, p.M, p.T, p.bank.data());
+    const struct { const std::vector<double> &coef; const std::vector<int32_t> &first; void **d_coef; int32_t **d_first; } sets[2] = {
+        {t.ct, t.lo, b->ct, &b->d_lo}, {t.tab, t.e0, b->tab, &b->e0}};
+    for (int k = 0; k < (t.tile ? 2 : 1); ++k) {
+        if (const char *e = adj_upload<float>(&sets[k].d_coef[0], sets[k].coef)) return e;
+        if (const char *e = adj_upload<double>(&sets[k].d_coef[1], sets[k].coef)) return e;
+        HIP_TRY(hipMalloc((void **)sets[k].d_first, sets[k].first.size() * sizeof(int32_t)));
+        HIP_TRY(hipMemcpy(*sets[k].d_first, sets[k].first.data(), sets[k].first.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     }
-    b->Tt = (int32_t)Tt;
-    b->dmin = lo[0]; // d_lo is non-decreasing in s
-    {
-        std::vector<double> ct((size_t)(Tt * M));
-        for (int64_t s = 0; s < M; ++s)
-            for (int64_t i = 0; i < Tt; ++i) ct[(size_t)(i * M + s)] = coef(s, lo[(size_t)s] + i);
-        if (const char *e = adj_upload<float>(&b->ct[0], ct)) return e;
-        if (const char *e = adj_upload<double>(&b->ct[1], ct)) return e;
-        HIP_TRY(hipMalloc((void **)&b->d_lo, (size_t)M * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(b->d_lo, lo.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    // k_adj_tile: the period replicated until a wave tile (16 phases) and a slab row (64 frames) are filled
-    const int64_t c = std::max((kAdjRS + M - 1) / M, (64 + L - 1) / L);
-    b->Lc = c * L; b->Mc = c * M;
-    b->pad = (b->Lc & 1) ? 0 : 1;
-    if (b->Lc > 8192 || b->Mc > 65536) return nullptr; // (16 periods of float32 would not fit LDS: k_adj_gather serves the plan)
-    const int32_t n_st = (int32_t)((b->Mc + kAdjRS - 1) / kAdjRS);
-    int64_t I = 0;
-    for (int32_t st = 0; st < n_st; ++st) {
-        const int64_t s0 = (int64_t)st * kAdjRS, s1 = std::min<int64_t>(s0 + kAdjRS, b->Mc) - 1;
-        I = std::max(I, d_hi(s1) - d_lo(s0) + 1);
-    }
-    I = (I + 3) / 4 * 4;
-    std::vector<int32_t> e0((size_t)n_st);
-    std::vector<double> tab((size_t)n_st * (size_t)I * kAdjRS, 0.0);
-    int64_t wmax = 0;
-    for (int32_t st = 0; st < n_st; ++st) {
-        const int64_t s0 = (int64_t)st * kAdjRS, first = d_lo(s0);
-        e0[(size_t)st] = (int32_t)(first - b->dmin);
-        wmax = std::max(wmax, first - b->dmin + I);
-        for (int64_t ii = 0; ii < I; ++ii)
-            for (int rr = 0; rr < kAdjRS; ++rr)
-                if (s0 + rr < b->Mc) tab[((size_t)st * (size_t)I + (size_t)ii) * kAdjRS + rr] = coef(s0 + rr, first + ii);
-    }
-    b->n_st = n_st; b->I = (int32_t)I; b->wmax = (int32_t)wmax;
-    if (const char *e = adj_upload<float>(&b->tab[0], tab)) return e;
-    if (const char *e = adj_upload<double>(&b->tab[1], tab)) return e;
-    HIP_TRY(hipMalloc((void **)&b->e0, (size_t)n_st * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(b->e0, e0.data(), (size_t)n_st * sizeof(int32_t), hipMemcpyHostToDevice));
-    b->tile = true;
+    static_cast<AdjGeom &>(*b) = t;
+    b->L = p.L; b->M = p.M; b->Tt = t.Tt; b->dmin = t.dmin; b->I = t.I;
     return nullptr;
 }
 
@@ -518,13 +466,45 @@ static void adj_launch_log(const char *kernel, size_t width, const AdjBank &b, i
     fputc('\n', f);
     fclose(f);
 }
-
-// rows: the device copy of a ragged job's clip table, or NULL (equal-length clips).  A ragged job's in_frames / out_frames
-// are its largest clip's: the form is chosen by, and the grid's frame axis sized by, the LONGEST clip.
+// ... and k_adj_interp's line
 template <typename Real>
-static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows = nullptr)
+static void adj_interp_log(const Plan &p, bool per_lane, dim3 grid, const AdjInterpRaggedArgs &a, uint32_t n_clips)
 {
-    const int prec = sizeof(Real) == 4 ? 0 : 1;
+    FILE *f = fopen(switches().dbg_launch_log, "a");
+    if (!f) return;
+    fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u", sizeof(Real),
+            (long long)p.L, (long long)p.M, p.T, p.phases, kAdjIW, kAdjIC, sizeof(AdjRec<Real>) * kAdjIC, per_lane ? "lane" : "union",
+            grid.x, grid.y, grid.z, (unsigned)kAdjIW);
+    if (a.rows) fprintf(f, " ragged=%u", n_clips);
+    fputc('\n', f);
+    fclose(f);
+}
+
+// The launches proper, one call site per kernel: the RAGGED instantiation takes the whole argument block, the equal-length
+// one the block it always took — the AdjArgs / AdjInterpArgs part.
+template <typename Real, bool RAGGED>
+static const char *adj_run_tile(const AdjRaggedArgs &a, dim3 grid, unsigned nt, size_t lds, hipStream_t st)
+{
+    if (const char *e = ensure_dyn_lds((const void *)k_adj_tile<Real, RAGGED>, lds)) return e;
+    hipLaunchKernelGGL((k_adj_tile<Real, RAGGED>), grid, dim3(nt), lds, st, static_cast<const typename AdjArgsOf<RAGGED>::type &>(a));
+    return nullptr;
+}
+template <typename Real, bool RAGGED>
+static void adj_run_gather(const AdjRaggedArgs &a, dim3 grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_adj_gather<Real, RAGGED>), grid, dim3(kAdjGatherLanes), 0, st, static_cast<const typename AdjArgsOf<RAGGED>::type &>(a));
+}
+template <typename Real, bool UNION, bool RAGGED>
+static void adj_run_interp(const AdjInterpRaggedArgs &a, dim3 grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((k_adj_interp<Real, UNION, RAGGED>), grid, dim3(kAdjIW), 0, st, static_cast<const typename AdjInterpArgsOf<RAGGED>::type &>(a));
+}
+
+// The argument block of the exact-bank kernels, all but what the tile form decides.  rows: the device copy of a ragged job's
+// clip table, or NULL (equal-length clips).  A ragged job's in_frames / out_frames are its largest clip's: the form is
+// chosen by, and the grid's frame axis sized by, the LONGEST clip.
+static AdjRaggedArgs adj_args(const AdjBank &b, int prec, const hipsoxr_job_t &j, const int64_t *rows)
+{
     AdjRaggedArgs a{}; // (the equal-length kernels take its AdjArgs part)
     a.gy = j.in; a.gx = j.out;
     a.ct = b.ct[prec]; a.d_lo = b.d_lo; a.tab = b.tab[prec]; a.e0 = b.e0;
@@ -535,128 +515,124 @@ static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStrea
     a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
     a.n_y = j.in_frames; a.n_x = j.out_frames;
     a.rows = rows;
-    const bool inter = j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1; // frames of interleaved channels
-    a.inter = inter ? 1 : 0;
+    a.inter = (j.n_channels > 1 && j.in_chan_stride == 1 && j.out_chan_stride == 1) ? 1 : 0; // frames of interleaved channels
+    return a;
+}
 
-    if (b.tile && j.out_frames >= kAdjMinPeriods * b.Mc) {
-        // lanes per workgroup slab: 64 (32, 16 where LDS demands); two workgroups per CU where that is possible
-        size_t lds = 0;
-        int lanes = 0;
-        for (size_t limit : {(size_t)80 * 1024, (size_t)160 * 1024}) {
-            for (int ln : {64, 32, 16}) {
-                const int32_t cg = inter ? (int32_t)std::min<uint32_t>(j.n_channels, (uint32_t)ln) : 1, pb = ln / cg;
-                const int64_t xc = (int64_t)(pb - 1) * b.Lc + b.wmax, rows = (xc + b.Lc - 1) / b.Lc;
-                const size_t need = (size_t)(rows * (b.Lc + b.pad)) * (size_t)cg * sizeof(Real);
-                if (need <= limit) { lanes = ln; lds = need; a.cg = cg; a.pb = pb; a.x_count = (int32_t)xc; break; }
-            }
-            if (lanes) break;
-        }
-        const int64_t n_per = (j.out_frames + b.Mc - 1) / b.Mc;
-        const int64_t gx = lanes ? (n_per + a.pb - 1) / a.pb : 0;
-        if (lanes && gx <= 2147483647LL) {
-            a.cg_shift = -1;
-            for (int sh = 0; sh < 7; ++sh)
-                if ((1 << sh) == a.cg) a.cg_shift = sh;
-            a.n_groups = (j.n_channels + (uint32_t)a.cg - 1) / (uint32_t)a.cg;
-            const uint64_t cols = (uint64_t)j.n_clips * a.n_groups;
-            const uint32_t gy = (uint32_t)std::min<uint64_t>(cols, 65535);
-            // few workgroups: spread a slab's phase tiles over z workgroups until the chip has ~4 per CU
-            const int64_t wgs = gx * (int64_t)gy;
-            int z = (int)std::min<int64_t>(b.n_st, std::max<int64_t>(1, 1024 / wgs));
-            int nw = std::min(16, (b.n_st + z - 1) / z);
-            z = std::min(z, (b.n_st + nw - 1) / nw);
-            a.n_waves = nw;
-            if (const char *e = ensure_dyn_lds(rows ? (const void *)k_adj_tile<Real, true> : (const void *)k_adj_tile<Real, false>, lds)) return e;
-            if (rows) hipLaunchKernelGGL((k_adj_tile<Real, true>), dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, a);
-            else hipLaunchKernelGGL((k_adj_tile<Real, false>), dim3((uint32_t)gx, gy, (uint32_t)z), dim3((uint32_t)nw * 64), lds, st, (AdjArgs)a);
-            HIP_TRY(hipGetLastError());
-            if (switches().dbg_launch_log) adj_launch_log("adj_tile", sizeof(Real), b, lanes, lds, a, dim3((uint32_t)gx, gy, (uint32_t)z), (unsigned)nw * 64);
-            return nullptr;
-        }
-    }
-    const int64_t per_clip = j.out_frames * (int64_t)j.n_channels;
-    const int64_t gx = (per_clip + 255) / 256;
-    if (gx > 2147483647LL) return "adjoint job: too long for one launch";
-    if (rows) hipLaunchKernelGGL((k_adj_gather<Real, true>), dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((k_adj_gather<Real, false>), dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535)), dim3(256), 0, st, (AdjArgs)a);
+template <typename Real>
+static const char *adj_launch_tile(const AdjBank &b, const AdjTileForm &f, AdjRaggedArgs a, hipStream_t st)
+{
+    a.cg_shift = f.cg_shift; a.n_groups = f.n_groups; a.n_waves = f.n_waves;
+    const dim3 grid((uint32_t)f.gx, f.gy, (uint32_t)f.gz);
+    const unsigned nt = (unsigned)f.n_waves * 64;
+    if (const char *e = a.rows ? adj_run_tile<Real, true>(a, grid, nt, f.lds, st) : adj_run_tile<Real, false>(a, grid, nt, f.lds, st)) return e;
     HIP_TRY(hipGetLastError());
-    if (switches().dbg_launch_log) adj_launch_log("adj_gather", sizeof(Real), b, 0, 0, a, dim3((uint32_t)gx, std::min<uint32_t>(j.n_clips, 65535), 1), 256);
+    if (switches().dbg_launch_log) adj_launch_log("adj_tile", sizeof(Real), b, f.lanes, f.lds, a, grid, nt);
     return nullptr;
+}
+
+template <typename Real>
+static const char *adj_launch_gather(const AdjBank &b, const hipsoxr_job_t &j, const AdjRaggedArgs &a, hipStream_t st)
+{
+    const AdjGrid g = adj_gather_grid(j.out_frames, j.n_clips, j.n_channels);
+    if (!g.ok) return kAdjTooLong;
+    const dim3 grid(g.gx, g.gy);
+    if (a.rows) adj_run_gather<Real, true>(a, grid, st);
+    else adj_run_gather<Real, false>(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) adj_launch_log("adj_gather", sizeof(Real), b, 0, 0, a, grid, kAdjGatherLanes);
+    return nullptr;
+}
+
+// The exact-bank launch: the arguments, the form (adjoint_rules.h), the form's kernel.
+template <typename Real>
+static const char *adj_launch(const AdjBank &b, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows)
+{
+    AdjRaggedArgs a = adj_args(b, sizeof(Real) == 4 ? 0 : 1, j, rows);
+    const AdjTileForm f = adj_tile_form(b, sizeof(Real), j.out_frames, j.n_clips, j.n_channels, a.inter != 0);
+    a.cg = f.cg; a.pb = f.pb; a.x_count = f.x_count;
+    return f.ok ? adj_launch_tile<Real>(b, f, a, st) : adj_launch_gather<Real>(b, j, a, st);
 }
 
 // k_adj_interp on the plan's own interpolation table (uploaded by device_bank_ensure, as for the forward).
 template <typename Real>
-static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows = nullptr)
+static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows)
 {
-    const int prec = sizeof(Real) == 4 ? 0 : 1;
     AdjInterpRaggedArgs a{};
-    a.gy = j.in; a.gx = j.out; a.tab = p.dev[prec].interp_tab;
+    a.gy = j.in; a.gx = j.out; a.tab = p.dev[sizeof(Real) == 4 ? 0 : 1].interp_tab;
     a.L = p.L; a.M = p.M; a.T = p.T; a.P = p.phases;
     a.n_cols = (uint64_t)j.n_clips * j.n_channels; a.n_channels = j.n_channels;
     a.ics = j.in_clip_stride; a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride;
     a.ocs = j.out_clip_stride; a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
     a.n_y = j.in_frames; a.n_x = j.out_frames;
     a.rows = rows;
-    // positions are 64-bit products, as in the forward: (frame + T/2) L and k M
-    const __int128 lim = (__int128)1 << 62;
-    if ((__int128)(j.out_frames + p.T) * p.L >= lim || (__int128)j.in_frames * p.M >= lim) return "adjoint job: too long for one launch";
-    const int64_t gx = (j.out_frames + kAdjIW - 1) / kAdjIW;
-    if (gx > 2147483647LL) return "adjoint job: too long for one launch";
-    const dim3 grid((uint32_t)gx, (uint32_t)std::min<uint64_t>(a.n_cols, 65535));
+    const AdjGrid g = adj_interp_grid(p.L, p.M, p.T, j.in_frames, j.out_frames, a.n_cols, kAdjIW);
+    if (!g.ok) return kAdjTooLong;
+    const dim3 grid(g.gx, g.gy);
     const bool per_lane = switches().adj_interp_per_lane;
-    if (rows) {
-        if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false, true>), grid, dim3(kAdjIW), 0, st, a);
-        else hipLaunchKernelGGL((k_adj_interp<Real, true, true>), grid, dim3(kAdjIW), 0, st, a);
-    } else if (per_lane) hipLaunchKernelGGL((k_adj_interp<Real, false, false>), grid, dim3(kAdjIW), 0, st, (AdjInterpArgs)a);
-    else hipLaunchKernelGGL((k_adj_interp<Real, true, false>), grid, dim3(kAdjIW), 0, st, (AdjInterpArgs)a);
+    if (rows) per_lane ? adj_run_interp<Real, false, true>(a, grid, st) : adj_run_interp<Real, true, true>(a, grid, st);
+    else per_lane ? adj_run_interp<Real, false, false>(a, grid, st) : adj_run_interp<Real, true, false>(a, grid, st);
     HIP_TRY(hipGetLastError());
-    if (switches().dbg_launch_log)
-        if (FILE *f = fopen(switches().dbg_launch_log, "a")) {
-            fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u", sizeof(Real),
-                    (long long)p.L, (long long)p.M, p.T, p.phases, kAdjIW, kAdjIC, sizeof(AdjRec<Real>) * kAdjIC, per_lane ? "lane" : "union",
-                    grid.x, grid.y, grid.z, (unsigned)kAdjIW);
-            if (rows) fprintf(f, " ragged=%u", j.n_clips);
-            fputc('\n', f);
-            fclose(f);
-        }
+    if (switches().dbg_launch_log) adj_interp_log<Real>(p, per_lane, grid, a, j.n_clips);
     return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host: the two entries
+// ---------------------------------------------------------------------------------------------
+template <typename F> static const char *with_real(int elem, F f) { return elem == HIPSOXR_F32 ? f(float{}) : f(double{}); }
+
+static AdjAsk adj_ask(const Plan &p, const hipsoxr_job_t &j)
+{
+    AdjAsk q;
+    q.half = elem_is_half(j.elem);
+    q.real = j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64;
+    q.by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT; // every constant-rate plan: k_adj_interp where there is no exact bank
+    q.auto_or_exact = j.kernel == HIPSOXR_KERNEL_AUTO || j.kernel == HIPSOXR_KERNEL_EXACT;
+    q.vr = p.vr; q.phases = p.phases != 0;
+    q.window = j.in_abs0 != 0 || j.out_k0 != 0;
+    q.table = j.clip_table != nullptr;
+    return q;
+}
+// ... what both entries ask last, of a job that is not empty
+static const char *adj_device_refusal(const hipsoxr_job_t &j)
+{
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+    return device_count() <= 0 ? kNoDevice : nullptr;
+}
+
+// The tables the job's kernel reads: the forward's interpolation table in the element's width (a fresh plan has none yet),
+// or the transposed bank (*b).
+static const char *adj_tables_ensure(Plan *p, const hipsoxr_job_t &j, AdjBank **b)
+{
+    return p->phases ? device_bank_ensure(p, engine_prec(j.elem)) : adj_ensure(p, b);
+}
+static const char *adj_run(const Plan &p, const AdjBank *b, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows)
+{
+    if (p.phases) return with_real(j.elem, [&](auto r) { return adj_interp_launch<decltype(r)>(p, j, st, rows); });
+    return with_real(j.elem, [&](auto r) { return adj_launch<decltype(r)>(*b, j, st, rows); });
 }
 
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
-    const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT; // every constant-rate plan: k_adj_interp where there is no exact bank
     if (elem_is_half(j.elem)) {
         // float16 / bfloat16: the float32 adjoint on the widened cotangent, rounded once (half.hip) — under every selector
         // this entry serves for float32.  The refusals by name and the empty job first, asked of the float32 job without clips.
         hipsoxr_job_t f = j;
         f.elem = HIPSOXR_F32; f.n_clips = 0;
         if (const char *e = launch_adjoint(p, f, stream)) return e;
-        if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
-        if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-        if (device_count() <= 0) return kNoDevice;
+        if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
+        if (const char *e = adj_device_refusal(j)) return e;
         return launch_half(p, j, stream, true);
     }
-    if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
-    if (by_name && p->vr) return "adjoint job: variable-rate plans are not served (HIPSOXR_KERNEL_ADJOINT takes constant-rate plans)";
-    if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans and the two-stage form are not served)";
-    if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
-    if (j.clip_table) return "adjoint job: ragged batches (clip_table) are served by hipsoxr_run_device_adjoint_ragged, not by this entry";
-    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && !by_name)
-        return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
-    if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
-    if ((uint64_t)j.in_frames > plan_out_len(*p, (uint64_t)j.out_frames))
-        return "adjoint job: in_frames (cotangent frames) exceeds the plan's output length for out_frames";
-    if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
-    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-    if (device_count() <= 0) return kNoDevice;
-    if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
-        if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
-        return j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, (hipStream_t)stream) : adj_interp_launch<double>(*p, j, (hipStream_t)stream);
-    }
+    if (const char *e = adj_entry_refusal(kAdjEqual, adj_ask(*p, j))) return e;
+    if (const char *e = adj_extent_refusal(kAdjEqual, j.in_frames, j.out_frames, [&](uint64_t n) { return plan_out_len(*p, n); })) return e;
+    if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
+    if (const char *e = adj_device_refusal(j)) return e;
     AdjBank *b = nullptr;
-    if (const char *e = adj_ensure(p, &b)) return e;
-    return j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, (hipStream_t)stream) : adj_launch<double>(*b, j, (hipStream_t)stream);
+    if (const char *e = adj_tables_ensure(p, j, &b)) return e;
+    return adj_run(*p, b, j, (hipStream_t)stream, nullptr);
 }
 
 // hipsoxr_run_device_adjoint_ragged: all clips of a clip table in ONE launch of the kernel's RAGGED form.  The refusals are
@@ -664,32 +640,15 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 // loops wrap.
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
-    const bool by_name = j.kernel == HIPSOXR_KERNEL_ADJOINT;
-    if (elem_is_half(j.elem))
-        return "adjoint job: ragged: float16 / bfloat16 clip tables are not served (float32 or float64; half cotangents clip by clip through hipsoxr_run_device_adjoint)";
-    if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64) return "adjoint job: float32 or float64 elements only (integer types have no gradient)";
-    if (p->vr) return "adjoint job: variable-rate plans are not served (ragged batches take constant-rate plans)";
-    if (p->phases && !by_name) return "adjoint job: needs an exact-bank plan (interpolated-phase plans are served by name, HIPSOXR_KERNEL_ADJOINT)";
-    if (j.in_abs0 != 0 || j.out_k0 != 0) return "adjoint job: whole signals only (in_abs0 == 0, out_k0 == 0)";
-    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_EXACT && !by_name)
-        return "adjoint job: the kernel selector must be AUTO or EXACT (the adjoint is the exact engine's; the frequency-domain engine has none)";
-    if (!j.clip_table) return "adjoint job: the ragged entry needs a clip_table (equal-length clips: hipsoxr_run_device_adjoint)";
-    for (uint32_t c = 0; c < j.n_clips; ++c) {
-        switch (job_row_check(j.clip_table + kRaggedRow * (size_t)c, j.in_frames, j.out_frames, kJobRowAdjoint, [&](uint64_t n) { return plan_out_len(*p, n); })) {
-        case kJobRowOk: break;
-        case kJobRowNegative: return "adjoint job: ragged: a clip's offset or frame count is negative";
-        case kJobRowAboveJob: return "adjoint job: ragged: a clip's frame count is above the job's in_frames / out_frames (the largest per-clip values)";
-        case kJobRowAbovePlan: return "adjoint job: ragged: a clip's n_y (cotangent frames) exceeds the plan's output length for its n_x";
-        }
-    }
-    if (j.in_frames < 0 || j.out_frames < 0) return "adjoint job: invalid job extent";
-    if (j.out_frames == 0 || j.n_clips == 0 || j.n_channels == 0) return nullptr;
-    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
-    if (device_count() <= 0) return kNoDevice;
+    const auto out_len = [&](uint64_t n) { return plan_out_len(*p, n); };
+    if (const char *e = adj_entry_refusal(kAdjRagged, adj_ask(*p, j))) return e;
+    for (uint32_t c = 0; c < j.n_clips; ++c)
+        if (const char *e = adj_row_refusal(job_row_check(j.clip_table + kRaggedRow * (size_t)c, j.in_frames, j.out_frames, kJobRowAdjoint, out_len))) return e;
+    if (const char *e = adj_extent_refusal(kAdjRagged, j.in_frames, j.out_frames, out_len)) return e;
+    if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
+    if (const char *e = adj_device_refusal(j)) return e;
     AdjBank *b = nullptr;
-    if (p->phases) { // the forward's table in the element's width; a fresh plan has none yet
-        if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
-    } else if (const char *e = adj_ensure(p, &b)) return e;
+    if (const char *e = adj_tables_ensure(p, j, &b)) return e;
     // The kernels read the DEVICE copy of the table; without one the host table, validated above, is uploaded in stream
     // order (clip_table_device: the buffer lives until the launch behind it has run).  A caller's copy is trusted.
     const hipStream_t st = (hipStream_t)stream;
@@ -697,9 +656,7 @@ const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
     void *tmp = nullptr;
     static constexpr ClipTableTexts texts = {"adjoint job: ragged: no device memory for the clip table", "adjoint job: ragged: clip table upload failed"};
     if (const char *e = clip_table_device(j, stream, &rows, &tmp, texts)) return e;
-    const char *e;
-    if (p->phases) e = j.elem == HIPSOXR_F32 ? adj_interp_launch<float>(*p, j, st, rows) : adj_interp_launch<double>(*p, j, st, rows);
-    else e = j.elem == HIPSOXR_F32 ? adj_launch<float>(*b, j, st, rows) : adj_launch<double>(*b, j, st, rows);
+    const char *e = adj_run(*p, b, j, st, rows);
     if (tmp) (void)hipFreeAsync(tmp, st);
     return e;
 }

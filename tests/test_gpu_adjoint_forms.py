@@ -1,9 +1,11 @@
 """GPU: every launch form of the transposed operator (csrc/adjoint.hip, adj_launch) against a float64 reference.
 
-adj_launch decides: lane-per-element kernel or period-tiled kernel; 64, 32 or 16 lanes per slab; the 80 KB or the 160 KB
-LDS limit; channel groups (by shift or by division); z workgroups per slab against n_waves waves per workgroup; and the
-gridDim.y wrap at 65535 columns.  The debug-switch build writes one line per launch (HIPSOXR_DEBUG_LAUNCH_LOG), so a case
-here names the property its launch must show and the test reads it from the log — adj_launch is not restated.  All jobs
+adj_launch asks csrc/adjoint_rules.h (adj_tile_form, adj_gather_grid), which decides: lane-per-element kernel or period-tiled
+kernel; 64, 32 or 16 lanes per slab; the 80 KB or the 160 KB LDS limit; channel groups (by shift or by division); z
+workgroups per slab against n_waves waves per workgroup; and the gridDim.y wrap at 65535 columns.  The debug-switch build
+writes one line per launch (HIPSOXR_DEBUG_LAUNCH_LOG, adj_launch_log), so a case here names the property its launch must
+show and the test reads it from the log — the rule is not restated (tests/c/adjoint_rules_check.cpp holds the same table
+against the rule on the CPU).  All jobs
 run in ONE child process (tests/_adjoint_probe.py) into guarded, NaN-filled buffers; everything is compared here.
 
 Per case: the launch form; 8 guard elements either side of every column untouched and every payload element written;
