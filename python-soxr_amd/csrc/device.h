@@ -133,6 +133,9 @@ struct Switches {
     const char *dbg_launch_log = nullptr; // HIPSOXR_DEBUG_LAUNCH_LOG  path of a text file: launch_fft_impl (fft.hip) appends one line per call — form, table row, instance kind, launch shape (written by the launcher of the form that took the job, or "none" by the dispatcher); adj_launch (adjoint.hip) one line per launch — kernel, element width, lanes, LDS bytes, channel group, launch shape (a ragged launch appends ragged=<n_clips>); launch_tile and launch_ragged (kernels.hip, tile_launch_log) one line per tile launch of the exact engine — kernel tile | tile_mfma | tile_mfma_p | tile_mfma64_p (a ragged launch also: gather), element width, io type, L M Lc Mc, pb, n_rt, nw (waves that compute), split (workgroups per slab), halves, xz, LDS bytes, launch shape; a ragged launch appends ragged=<n_clips> (equal-length launches of launch_gather's family: below); adj_interp_launch: kernel, element width, L M T P, tile frames, chunk size, LDS bytes, walk, launch shape; launch_poly (twostage.hip) one line per polyphase launch of the two-stage form — kernel poly | poly2, element width, taps, MQ, il (channel pairs), split, R, lane multiplier and its conflict cost, LDS bytes, channel group, columns, tiles, launch shape, outputs of member 1 and member 2 (a launch over a clip table's columns appends ragged=<columns>, tiles and n_out then being the longest column's — as does the FFT line of a launch over a table); launch_gather (kernels.hip) one line per launch — kernel gather_wave | chain | chain_resident | interp_wave | interp_tile | interp | gather, element width, io type, vr, L M T P, done nf cols, k0 in_abs0 (the launch's first output and the absolute index of input frame 0), launch shape, LDS bytes, then the form's own fields (chain: NO span_cap mode; wave forms: span_cap; tile: KO pair twin h nf_t m2_n span_cap; lane per output: ch_fast)
 };
 const Switches &switches();
+// (engine.cpp) what the debug-switch build exports as hipsoxr_debug_stream_seek — no header declares it, the product does not
+// export it: a fresh stream's counters set to (in_frames, out_frames), for tests of the stream kernels at large positions
+const char *debug_stream_seek(hipsoxr_stream_t *s, uint64_t in_frames, uint64_t out_frames);
 
 // One independent stream's part of a many-streams launch (kernels.hip k_chain_multi; engine.cpp
 // hipsoxr_streams_process_device): the small-launch kernel's job description per stream, plus the chunk this call appends

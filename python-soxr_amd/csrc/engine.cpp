@@ -54,6 +54,7 @@ struct hipsoxr_stream {
     unsigned long flags = 0;
     bool ended = false;
     uint64_t n_in_total = 0, k_done = 0;
+    uint64_t n_in_origin = 0, k_origin = 0; // where the signal starts: 0, but for debug_stream_seek (the debug-switch build)
     // device staging of pending input: frames [in_base, in_base + in_fill)
     void *d_in = nullptr, *d_in_alt = nullptr;
     size_t in_cap = 0, alt_cap = 0; // frames
@@ -518,6 +519,8 @@ hipsoxr_error_t hipsoxr_run_device_vr_ragged(hipsoxr_plan_t *h, const hipsoxr_jo
 // stream internals
 // ------------------------------------------------------------------------------------------------
 static inline size_t esz(const hipsoxr_stream *s) { return elem_size(s->elem); }
+// no input yet: the first chunk decides where the ring lives
+static inline bool stream_unfed(const hipsoxr_stream *s) { return s->n_in_total == s->n_in_origin; }
 
 // Absolute index of the first input sample the next output (k_done) needs.
 static int64_t first_needed(const hipsoxr_stream *s)
@@ -537,8 +540,7 @@ static int64_t first_needed(const hipsoxr_stream *s)
         // reach discarded outputs — every kept output >= k_done has its whole support [n0, ...) in the ring — but the
         // rounding of a block depends on all of its input, and a result must not depend on when the ring was compacted
         // (a pooled ring, clear(), another element size).
-        const int64_t blk0 = ((int64_t)(s->k_done / (uint64_t)p.L) - s->fft_lead) * p.M;
-        return std::min(n0, blk0);
+        return std::min(n0, fft_block_origin(p, s->k_done, s->fft_lead));
     }
     return n0;
 }
@@ -670,7 +672,7 @@ static const char *device_ring_reserve(hipsoxr_stream *s, size_t ilen)
 static const char *stream_append(hipsoxr_stream *s, const void *in, size_t ilen, void **h_buf, size_t *h_bytes)
 {
     const size_t bytes_in = ilen * s->ch * esz(s);
-    if (!s->split && !s->ring_on_host && s->n_in_total == 0 && bytes_in <= kHostRingChunk && !switches().no_host_ring) {
+    if (!s->split && !s->ring_on_host && stream_unfed(s) && bytes_in <= kHostRingChunk && !switches().no_host_ring) {
         // first chunk of a stream, and a small one: ring in pinned host memory.  A DEVICE ring inherited from the
         // pool (the stream before this one fed large chunks) is given up for it: keeping it cost every later
         // small-chunk stream of the process the host ring and with it the resident kernel — 441-frame calls 23 us
@@ -757,6 +759,9 @@ static const char *resident_emit(hipsoxr_stream *s, const hipsoxr_job_t &j, bool
     hipsoxr_stream::Resident &r = s->res;
     *served = false;
     if (r.failed >= 2) return nullptr;
+    // A message the mailbox cannot carry (stream_rules.h resident_msg: positions from 2^48 on) goes the ordinary path before
+    // anything is launched for it: resident_post would refuse it only after an instance had been started for nothing, call after call
+    if (!resident_msg(s->plan->p, j.in_abs0, j.in_frames, j.out_k0, j.out_frames, vp != nullptr).fits) { resident_stop(s); return nullptr; }
     if (!r.box) {
         if (hipHostMalloc((void **)&r.box, sizeof(ResidentBox), hipHostMallocDefault) != hipSuccess) { r.box = nullptr; r.failed = 2; return nullptr; }
         std::memset(r.box, 0, sizeof(ResidentBox));
@@ -1024,7 +1029,7 @@ static const char *stream_process_deferred(hipsoxr_stream *s, const void *in, si
         if (s->ended) return "Input after last input";
         const int b = (int)(s->calls & 1);
         const size_t bytes = ilen * frame;
-        if (s->ring_on_host || ((!s->split || !s->d_in) && s->n_in_total == 0 && bytes <= kHostRingChunk && !switches().no_host_ring)) {
+        if (s->ring_on_host || ((!s->split || !s->d_in) && stream_unfed(s) && bytes <= kHostRingChunk && !switches().no_host_ring)) {
             if (const char *e = stream_append(s, in, ilen, &s->h_in, &s->h_in_bytes)) return e; // host ring: a memcpy, nothing in flight to protect
         } else if (bytes <= kPinnedMax && (!s->ev_src[b] || hipEventSynchronize(s->ev_src[b]) == hipSuccess) &&
                    !pinned_ensure(&s->h_src[b], &s->h_src_bytes[b], bytes)) {
@@ -1532,7 +1537,7 @@ hipsoxr_error_t hipsoxr_stream_process(hipsoxr_stream_t *s, const void *in, size
         // (its per-channel planes are woven / unwoven at this boundary: a few hundred frames per call); a large one keeps
         // the planar device ring, where every channel moves with one copy
         s->adapt_decided = true;
-        if (s->n_in_total == 0 && ilen * s->ch * esz(s) <= kHostRingChunk && !switches().no_host_ring) {
+        if (stream_unfed(s) && ilen * s->ch * esz(s) <= kHostRingChunk && !switches().no_host_ring) {
             s->adapt = true; s->split = false;
             s->defer = (s->flags & HIPSOXR_DEFER) && !(s->flags & HIPSOXR_VR);
             s->resident = ((s->flags & HIPSOXR_RESIDENT) || switches().resident) && !s->defer;
@@ -1620,7 +1625,7 @@ hipsoxr_error_t hipsoxr_stream_clear(hipsoxr_stream_t *s)
     resident_stop(s);
     s->res.mirror_of = nullptr; // (the ring starts over at frame 0: nothing in the device mirror is current)
     if (s->st) (void)hipStreamSynchronize(s->st);
-    s->ended = false; s->n_in_total = 0; s->k_done = 0; s->in_base = 0; s->in_fill = 0;
+    s->ended = false; s->n_in_total = 0; s->n_in_origin = 0; s->k_origin = 0; s->k_done = 0; s->in_base = 0; s->in_fill = 0;
     s->pend_n = s->pend_off = 0;
     if (s->vr.on) { // fresh signal at the ratio last requested
         s->vr.k_s = 0; s->vr.t_s = 0; s->vr.s0 = s->vr.s1; s->vr.delta = 0; s->vr.n_slew = 0;
@@ -1636,12 +1641,18 @@ double hipsoxr_stream_delay(hipsoxr_stream_t *s)
 {
     if (!s) return 0.;
     const Plan &p = s->plan->p;
+    // stream_rules.h delay_constant / delay_vr: the difference of two counts that grow with the stream's age, formed so that
+    // the age costs no accuracy.  Counted from the signal's start (a seeked stream of the debug-switch build: from its seek —
+    // the value of the fresh stream, as the frames are; what the rule does at counts of 2^31 to 2^50 is held on the CPU,
+    // tests/c/stream_rules_check.cpp, profiles/NOTES_stream_positions.md)
     double d;
-    if (s->vr.on) { // input not yet passed by the output clock, in output samples at the current step
-        const double two64 = 18446744073709551616.;
-        d = ((double)s->n_in_total - (double)s->vr.pos(s->k_done) / two64) / ((double)s->vr.step(s->k_done) / two64);
+    if (s->vr.on) {
+        VrState v = s->vr; // the clock seen from the origin: positions less n_in_origin, outputs less k_origin
+        v.t_s -= (i128)((u128)s->n_in_origin << 64); v.k_s -= s->k_origin;
+        d = delay_vr(v, s->n_in_total - s->n_in_origin, s->k_done - s->k_origin);
     } else {
-        d = (double)s->n_in_total * (double)p.L / (double)p.M - (double)(s->k_done - (uint64_t)(s->pend_n - s->pend_off));
+        const uint64_t handed = s->k_done - (uint64_t)(s->pend_n - s->pend_off);
+        d = delay_constant(p, s->n_in_total - s->n_in_origin, handed - s->k_origin);
     }
     return d > 0. ? d : 0.;
 }
@@ -1702,3 +1713,35 @@ hipsoxr_error_t hipsoxr_oneshot(double in_rate, double out_rate, unsigned num_ch
 }
 
 } // extern "C"
+
+namespace hipsoxr {
+// hipsoxr_debug_stream_seek (exported by the debug-switch build alone, kernels.hip; tests/test_gpu_stream_positions.py): a
+// fresh stream's counters moved to (in_frames, out_frames), as if the signal began there — a time translation.  Every later
+// call then carries the positions of a stream that old: a constant-rate stream moved by whole periods emits the same
+// counts at the same phases, reads zeros in front of in_frames where the fresh one reads them in front of 0, and cuts the
+// same frequency-domain blocks relative to its ring (tests/c/stream_rules_check.cpp: the translation property).
+const char *debug_stream_seek(hipsoxr_stream *s, uint64_t in_frames, uint64_t out_frames)
+{
+    if (!s) return "null argument";
+    if (s->ended) return "debug seek: only a fresh or just-cleared stream can be moved (this one has ended)";
+    if (s->n_in_total != 0 || s->k_done != 0 || s->in_base != 0 || s->in_fill != 0)
+        return "debug seek: only a fresh or just-cleared stream can be moved (its counters are not at zero: fed, or seeked before)";
+    if (s->pend_n != s->pend_off) return "debug seek: a deferred result is pending";
+    if (s->res.running) return "debug seek: a resident instance is running";
+    if ((in_frames | out_frames) >> 62) return "debug seek: position out of range (below 2^62)";
+    if (!s->vr.on) {
+        const Plan &p = s->plan->p;
+        if ((u128)in_frames * (u128)p.L != (u128)out_frames * (u128)p.M)
+            return "debug seek: a constant-rate stream moves by whole periods only (in_frames L == out_frames M)";
+    }
+    s->n_in_total = s->n_in_origin = in_frames;
+    s->in_base = (int64_t)in_frames; s->in_fill = 0;
+    s->k_done = s->k_origin = out_frames;
+    s->res.mirror_of = nullptr; // (as clear(): nothing in a resident mirror of the ring is current)
+    if (s->vr.on) { // the segment in force starts here: any integer pair is a legal clock; the step is what it was
+        s->vr.k_s = out_frames;
+        s->vr.t_s = (i128)((u128)in_frames << 64);
+    }
+    return nullptr;
+}
+} // namespace hipsoxr

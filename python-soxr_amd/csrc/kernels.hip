@@ -99,6 +99,17 @@ const Switches &switches()
     return sw;
 }
 
+} // namespace hipsoxr
+// The debug-switch build's one export beyond include/hipsoxr.h (which does not declare it; a test sets its signature on the
+// loaded library): device.h debug_stream_seek.
+#ifdef HIPSOXR_DEBUG_SWITCHES
+extern "C" HIPSOXR_API hipsoxr_error_t hipsoxr_debug_stream_seek(hipsoxr_stream_t *s, uint64_t in_frames, uint64_t out_frames)
+{
+    return hipsoxr::debug_stream_seek(s, in_frames, out_frames);
+}
+#endif
+namespace hipsoxr {
+
 // ---------------------------------------------------------------------------------------------
 // conversions
 // ---------------------------------------------------------------------------------------------
@@ -1555,12 +1566,9 @@ const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &j, const uint64_t *cl
 bool resident_post(const Plan &p, volatile uint64_t *w, uint32_t seq, int64_t in_abs0, int64_t in_frames, int64_t out_k0, int64_t out_frames,
                    const VrPos *vr)
 {
-    const __int128 kM = vr ? (__int128)0 : (__int128)out_k0 * p.M; // (variable rate: positions come from the message's own clock)
-    const int64_t d0 = (int64_t)(kM / p.L), p0 = (int64_t)(kM % p.L);
-    const uint64_t lim = 1ULL << 48;
-    if ((uint64_t)in_abs0 >= lim || (uint64_t)out_k0 >= lim || (uint64_t)d0 >= lim || (uint64_t)in_frames >= (1u << 24) ||
-        (uint64_t)p0 >= (1u << 24) || (uint64_t)out_frames >= lim)
-        return false;
+    const ResidentMsg m = resident_msg(p, in_abs0, in_frames, out_k0, out_frames, vr != nullptr); // (stream_rules.h: what the words can carry)
+    if (!m.fits) return false;
+    const int64_t d0 = m.d0, p0 = m.p0;
     const uint64_t tag = (uint64_t)(seq & 0xffffu) << 48;
     // the words validate themselves (k_chain_resident): no order is needed among them — they may sit in
     // write-combining device memory — only everything the message refers to must have left before them

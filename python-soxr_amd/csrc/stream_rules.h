@@ -110,6 +110,28 @@ inline size_t emit_count(const Plan &p, VrState &v, uint64_t n_in_total, uint64_
 // a pass that stopped there: the one case in which a call makes another
 inline bool slew_just_ended(const VrState &v, uint64_t k_done) { return v.on && v.n_slew && k_done == v.k_s + v.n_slew; }
 
+// Output frames still owed for the input so far (hipsoxr_stream_delay), constant rate: n_in L / M - handed, where `handed` is
+// what the caller has been given.  Both terms grow with the stream's age, their difference does not: formed in doubles on the
+// counters themselves it is off by a quarter of a frame at 2^50.  So the whole periods that fit below the last multiple of
+// 2^32 outputs handed out are taken off both counters first — in integers, which changes nothing of the value — and the
+// expression is formed on what is left: fewer than 2^32 + L outputs, whatever the age, so four roundings of 2^-53 relative on
+// magnitudes below 2^33 — 4e-6 of a frame at the most.  A stream below 2^32 outputs (a day of 48 kHz audio; every test of the
+// suite) gets the plain expression on its own counters, bit for bit what it always got.
+inline double delay_constant(const Plan &p, uint64_t n_in, uint64_t handed)
+{
+    const uint64_t q = (handed >> 32 << 32) / (uint64_t)p.L;
+    const i128 n = (i128)n_in - (i128)q * p.M; // (may be a frame or two below zero: handed runs half an output ahead at the end)
+    const uint64_t k = handed - q * (uint64_t)p.L;
+    return (double)n * (double)p.L / (double)p.M - (double)k;
+}
+// ... variable rate: the input not yet passed by the output clock, in output samples at the current step.  The difference of
+// the two Q64.64 positions in integers, then one conversion.
+inline double delay_vr(const VrState &v, uint64_t n_in, uint64_t k_done)
+{
+    const i128 ahead = (i128)((u128)n_in << 64) - v.pos(k_done);
+    return (double)ahead / (double)v.step(k_done);
+}
+
 // Retire rule: the ring holds frames [in_base, in_base + in_fill) and the next output needs first_needed and later ones.
 // What stays is [keep_from, end): first_needed clamped into the ring; `drop` frames go, `keep` stay.
 struct RingKeep { int64_t keep_from; size_t drop, keep; };
@@ -118,6 +140,27 @@ inline RingKeep ring_keep(int64_t first_needed, int64_t in_base, size_t in_fill)
     const int64_t keep_from = std::min<int64_t>(std::max<int64_t>(first_needed, in_base), in_base + (int64_t)in_fill);
     const size_t drop = (size_t)(keep_from - in_base);
     return RingKeep{keep_from, drop, in_fill - drop};
+}
+
+// Frequency-domain streams (engine.cpp first_needed): the engine's origin for outputs from k_done on is the period boundary
+// P0 = floor(k_done / L), and block 0 begins `lead` periods in front of it — the first input frame the ring must still hold
+inline int64_t fft_block_origin(const Plan &p, uint64_t k_done, int32_t lead)
+{
+    return ((int64_t)(k_done / (uint64_t)p.L) - lead) * p.M;
+}
+
+// What a message to a resident kernel may carry (device.h ResidentBox, kernels.hip resident_post): positions in 48-bit
+// pieces, the two short counts in 24 bits.  A message beyond that is refused and its call takes the ordinary path.
+// d0, p0: out_k0 M = L d0 + p0, in 128 bits (variable rate: 0 — positions come from the message's own clock).
+static constexpr uint64_t kResidentPosLimit = 1ULL << 48, kResidentShortLimit = 1u << 24;
+struct ResidentMsg { int64_t d0, p0; bool fits; };
+inline ResidentMsg resident_msg(const Plan &p, int64_t in_abs0, int64_t in_frames, int64_t out_k0, int64_t out_frames, bool vr)
+{
+    const __int128 kM = vr ? (__int128)0 : (__int128)out_k0 * p.M;
+    const int64_t d0 = (int64_t)(kM / p.L), p0 = (int64_t)(kM % p.L);
+    const bool fits = (uint64_t)in_abs0 < kResidentPosLimit && (uint64_t)out_k0 < kResidentPosLimit && (uint64_t)d0 < kResidentPosLimit &&
+                      (uint64_t)in_frames < kResidentShortLimit && (uint64_t)p0 < kResidentShortLimit && (uint64_t)out_frames < kResidentPosLimit;
+    return ResidentMsg{d0, p0, fits};
 }
 
 // Growth rule: capacities are the present one (at least 1024 frames) times a power of two; the smallest that holds the

@@ -207,6 +207,42 @@ static void run_vr_case(const VrCase &c)
     std::printf("  %-28s %lu outputs from %lu frames%s%s\n", c.name, (unsigned long)k_done, (unsigned long)n_in, crossed ? ", a call crossed a slew end" : "", exact_end ? ", a call began at a slew end" : "");
 }
 
+// ---- the same scripts on a stream whose clock was moved (engine.cpp debug_stream_seek: k_s = out, t_s = in 2^64, the step
+// untouched; counters n_in_total = in, k_done = out), side by side with the fresh one: the same counts in every pass, the
+// limit moved by `out`, the launch's clock with a high word larger by `in` and nothing else changed — through every
+// set_io_ratio, slew and renormalisation of the script ----
+static void run_vr_case_moved(const VrCase &c, uint64_t in, uint64_t out)
+{
+    Plan p;
+    p.T = 16; p.phases = 64;
+    VrState v, m;
+    v.on = true; v.max_io = c.io0; v.s0 = v.s1 = q64(c.io0);
+    m = v; m.k_s = out; m.t_s = (i128)((u128)in << 64);
+    uint64_t n_in = 0, k_done = 0;
+    for (int call = 0; call <= c.calls; ++call) {
+        const bool ended = call == c.calls;
+        for (const VrEvent &e : c.events)
+            if (e.call == call) { state_set_io_ratio(v, k_done, e.ratio, e.slew_len); state_set_io_ratio(m, k_done + out, e.ratio, e.slew_len); }
+        if (!ended) n_in += c.ilen;
+        for (int pass = 0; pass < 4; ++pass) {
+            CHECK(vr_k_limit(p, m, n_in + in, k_done + out, ended) == vr_k_limit(p, v, n_in, k_done, ended) + out, "%s moved by (%lu, %lu): call %d: vr_k_limit", c.name,
+                  (unsigned long)in, (unsigned long)out, call);
+            const size_t n = emit_count(p, v, n_in, k_done, ended, c.olen), nm = emit_count(p, m, n_in + in, k_done + out, ended, c.olen);
+            CHECK(n == nm, "%s moved by (%lu, %lu): call %d pass %d: emit_count %zu, fresh %zu", c.name, (unsigned long)in, (unsigned long)out, call, pass, nm, n);
+            CHECK(m.k_s == v.k_s + out && m.n_slew == v.n_slew && m.t_s == v.t_s + (i128)((u128)in << 64) && m.s0 == v.s0 && m.s1 == v.s1 && m.delta == v.delta,
+                  "%s moved by (%lu, %lu): call %d: the state is not the fresh one moved", c.name, (unsigned long)in, (unsigned long)out, call);
+            for (uint64_t k : {k_done, k_done + n / 2, k_done + n}) {
+                const VrPos a = vr_pos_at(v, k), b = vr_pos_at(m, k + out);
+                CHECK(b.t_hi == a.t_hi + in && b.t_lo == a.t_lo && b.s_hi == a.s_hi && b.s_lo == a.s_lo && b.d_hi == a.d_hi && b.d_lo == a.d_lo,
+                      "%s moved by (%lu, %lu): call %d: vr_pos_at at k=%lu", c.name, (unsigned long)in, (unsigned long)out, call, (unsigned long)k);
+            }
+            k_done += n;
+            if (!n || !slew_just_ended(v, k_done)) break;
+        }
+    }
+    CHECK(k_done > 0, "%s moved: nothing was emitted", c.name);
+}
+
 static void check_emit_count_vr()
 {
     const std::vector<VrCase> cases = {
@@ -219,6 +255,13 @@ static void check_emit_count_vr()
         {"long slew, small olen", 0.9, 441, 37, 30, {{1, 0.45, 333}}, true, true},
     };
     for (const VrCase &c : cases) run_vr_case(c);
+    // any integer pair is a legal clock: outputs that cross 2^31 and 2^32 inside the script, inputs that cross 2^32 while
+    // the outputs do not, both above 2^40, below 2^48, above 2^50
+    const uint64_t moves[6][2] = {{((uint64_t)1 << 31) + 12345, ((uint64_t)1 << 31) - 700}, {((uint64_t)1 << 32) + 99, ((uint64_t)1 << 32) - 333},
+                                  {((uint64_t)1 << 32) - 500, ((uint64_t)1 << 31) + 1000003}, {((uint64_t)1 << 40) + 7, ((uint64_t)1 << 40) + 1000003},
+                                  {((uint64_t)1 << 48) - 40000, ((uint64_t)1 << 48) - 30000}, {((uint64_t)1 << 50) + 1000003, ((uint64_t)1 << 50) + 17}};
+    for (const VrCase &c : cases)
+        for (auto &mv : moves) run_vr_case_moved(c, mv[0], mv[1]);
 }
 
 // ---- the constant-rate rules at the counts of a stream that has run for hours or years: n_in_total, k_done and in_base
@@ -329,8 +372,146 @@ static void check_large_counts()
     }
 }
 
+// ---- the translation property (engine.cpp debug_stream_seek; tests/test_gpu_stream_positions.py rests on it): a
+// constant-rate stream whose counters were moved by q whole periods — n_in_total, in_base by q M, k_done by q L — is the
+// fresh stream moved: the same counts per call from N = 0 on (the start-up transient, where nothing is due yet, included),
+// the same phases, windows and ring cuts moved by q M, the same frequency-domain blocks relative to the ring.  Exact integers;
+// q puts the counts around 2^31, 2^32, 2^40, 2^48 and 2^50. ----
+static const uint64_t kMoveAt[5] = {(uint64_t)1 << 31, (uint64_t)1 << 32, (uint64_t)1 << 40, (uint64_t)1 << 48, (uint64_t)1 << 50};
+
+static void check_translation()
+{
+    Plan p;
+    const size_t olens[] = {0, 1, 441, (size_t)-1};
+    long moved = 0;
+    for (auto &r : kBigLM)
+        for (int32_t T : {2, 30, 736}) {
+            p.L = r[0]; p.M = r[1]; p.T = T;
+            for (uint64_t at : kMoveAt)
+                for (int side = 0; side < 2; ++side) { // the outputs at the power of two, or the inputs
+                    const uint64_t q = at / (uint64_t)(side ? p.M : p.L) - (side ? 0 : 1);
+                    const uint64_t dN = q * (uint64_t)p.M, dk = q * (uint64_t)p.L;
+                    if ((dN | dk) >> 62) continue;
+                    ++moved;
+                    // emit_count: N through the transient N <= T/2 and beyond; k_done around what is due and what the stream holds
+                    std::vector<uint64_t> Ns;
+                    for (uint64_t N = 0; N <= (uint64_t)T / 2 + 3; ++N) Ns.push_back(N);
+                    for (uint64_t N : {441u, 4410u, 100003u}) Ns.push_back(N);
+                    for (uint64_t N : Ns) {
+                        const uint64_t avail = k_avail_big(p.L, p.M, T, N), total = out_len_big(p.L, p.M, N);
+                        for (uint64_t k : {(uint64_t)0, (uint64_t)1, avail > 441 ? avail - 441 : 0, avail > 0 ? avail - 1 : 0, avail, avail + 1, total, total + 2})
+                            for (int ended = 0; ended < 2; ++ended)
+                                for (size_t olen : olens) {
+                                    const size_t fresh = emit_count(p, N, k, ended != 0, olen);
+                                    CHECK(emit_count(p, N + dN, k + dk, ended != 0, olen) == fresh, "emit_count %ld/%ld T=%d N=%lu k=%lu ended=%d olen=%zu moved by %lu periods: %zu, fresh %zu",
+                                          (long)p.L, (long)p.M, T, (unsigned long)N, (unsigned long)k, ended, olen, (unsigned long)q, emit_count(p, N + dN, k + dk, ended != 0, olen), fresh);
+                                }
+                    }
+                    // locate, the retire rule on what first_needed returns, and the frequency-domain block origin
+                    for (uint64_t k = 0; k < 3 * (uint64_t)p.L + 700; k += (k < 40 ? 1 : (uint64_t)p.L / 3 + 17)) {
+                        int64_t n0 = 0, ph = 0, n0m = 0, phm = 0;
+                        locate(p, (int64_t)k, &n0, &ph);
+                        locate(p, (int64_t)(k + dk), &n0m, &phm);
+                        CHECK(n0m == n0 + (int64_t)dN && phm == ph, "locate %ld/%ld T=%d k=%lu moved by %lu periods: (%ld, %ld), fresh (%ld, %ld)", (long)p.L, (long)p.M, T,
+                              (unsigned long)k, (unsigned long)q, (long)n0m, (long)phm, (long)n0, (long)ph);
+                        for (int32_t lead : {1, 3}) {
+                            const int64_t b = fft_block_origin(p, k, lead), bm = fft_block_origin(p, k + dk, lead);
+                            CHECK(bm == b + (int64_t)dN, "fft_block_origin %ld/%ld k=%lu lead=%d moved by %lu periods", (long)p.L, (long)p.M, (unsigned long)k, lead, (unsigned long)q);
+                            for (int64_t fn : {n0, b < n0 ? b : n0}) // (a fresh stream's first_needed is negative at first: clamped to the base)
+                                for (int64_t base : {(int64_t)0, fn - 5, fn + 3})
+                                    for (size_t fill : {(size_t)0, (size_t)7, (size_t)5000}) {
+                                        if (base < 0) continue;
+                                        const RingKeep a = ring_keep(fn, base, fill), c = ring_keep(fn + (int64_t)dN, base + (int64_t)dN, fill);
+                                        CHECK(c.keep_from == a.keep_from + (int64_t)dN && c.drop == a.drop && c.keep == a.keep, "ring_keep moved by %lu periods: first needed %ld base %ld fill %zu",
+                                              (unsigned long)q, (long)fn, (long)base, fill);
+                                    }
+                        }
+                    }
+                }
+        }
+    CHECK(moved >= 7 * 3 * 5, "translations run: %ld", moved);
+}
+
+// ---- resident_msg: a message is refused exactly where one of its numbers does not fit its words — in_abs0, out_k0,
+// out_frames and d0 = floor(out_k0 M / L) in 48 bits, in_frames and p0 = out_k0 M mod L in 24 — restated in 128 bits ----
+static void check_resident_msg()
+{
+    Plan p;
+    const int64_t lim = (int64_t)1 << 48, edge[] = {0, 1, 441, ((int64_t)1 << 24) - 1, (int64_t)1 << 24, ((int64_t)1 << 31) + 5, ((int64_t)1 << 40) + 9,
+                                                    lim - 4411, lim - 2, lim - 1, lim, lim + 1, ((int64_t)1 << 50) + 1000003, -1};
+    long refused = 0, taken = 0;
+    for (auto &r : kBigLM) {
+        p.L = r[0]; p.M = r[1]; p.T = 30;
+        for (int vr = 0; vr < 2; ++vr)
+            for (int64_t in_abs0 : edge)
+                for (int64_t out_k0 : edge)
+                    for (int64_t in_frames : {(int64_t)0, (int64_t)441, ((int64_t)1 << 24) - 1, (int64_t)1 << 24})
+                        for (int64_t out_frames : {(int64_t)1, (int64_t)441, lim - 1, lim}) {
+                            const ResidentMsg m = resident_msg(p, in_abs0, in_frames, out_k0, out_frames, vr != 0);
+                            const i128 kM = vr ? (i128)0 : (i128)out_k0 * p.M, d0 = kM / p.L, p0 = kM % p.L;
+                            auto in48 = [&](i128 v) { return v >= 0 && v < (i128)lim; };
+                            const bool want = in48(in_abs0) && in48(out_k0) && in48(out_frames) && in48(d0) && in_frames >= 0 && in_frames < (1 << 24) && p0 >= 0 && p0 < (1 << 24);
+                            CHECK(m.fits == want, "resident_msg %ld/%ld vr=%d in_abs0=%ld in_frames=%ld out_k0=%ld out_frames=%ld: fits=%d", (long)p.L, (long)p.M, vr, (long)in_abs0,
+                                  (long)in_frames, (long)out_k0, (long)out_frames, (int)m.fits);
+                            if (m.fits) CHECK((i128)m.d0 == d0 && (i128)m.p0 == p0, "resident_msg %ld/%ld out_k0=%ld: d0 / p0", (long)p.L, (long)p.M, (long)out_k0);
+                            if (m.fits) ++taken; else ++refused;
+                            // below every limit a message is taken; at or above one it is refused
+                            if (in_abs0 >= lim || out_k0 >= lim || out_frames >= lim || in_frames >= (1 << 24)) CHECK(!m.fits, "resident_msg takes a number at or above its limit");
+                        }
+    }
+    CHECK(refused > 0 && taken > 0, "resident_msg: %ld refused, %ld taken", refused, taken);
+}
+
+// ---- delay_constant / delay_vr: a stream below 2^32 outputs gets the plain double expression on its counters, bit for bit;
+// at any age the value is within 4e-6 of a frame of the exact one (the bound stream_rules.h derives: four roundings of 2^-53
+// relative on magnitudes below 2^33), where the plain expression on the counters themselves is off by a tenth of a frame ----
+static void check_delay()
+{
+    Plan p;
+    double worst = 0, worst_plain = 0;
+    for (auto &r : kBigLM) {
+        p.L = r[0]; p.M = r[1]; p.T = 30;
+        for (uint64_t N : {(uint64_t)0, (uint64_t)1, (uint64_t)441, (uint64_t)1000, (uint64_t)100003, (uint64_t)400000000}) {
+            const uint64_t total = out_len_big(p.L, p.M, N);
+            for (uint64_t back : {(uint64_t)0, (uint64_t)1, (uint64_t)27, (uint64_t)300}) {
+                if (back > total) continue;
+                const uint64_t k = total - back;
+                const double plain = (double)N * (double)p.L / (double)p.M - (double)k, got = delay_constant(p, N, k);
+                if (k < ((uint64_t)1 << 32)) CHECK(got == plain, "delay_constant %ld/%ld N=%lu k=%lu: %.17g, the plain expression %.17g", (long)p.L, (long)p.M, (unsigned long)N, (unsigned long)k, got, plain);
+                for (uint64_t at : kMoveAt) {
+                    const uint64_t q = at / (uint64_t)p.L + 1, Nq = N + q * (uint64_t)p.M, kq = k + q * (uint64_t)p.L;
+                    if ((Nq | kq) >> 62) continue;
+                    const double exact = (double)((i128)Nq * p.L - (i128)kq * p.M) / (double)p.M;
+                    const double e = std::fabs(delay_constant(p, Nq, kq) - exact), ep = std::fabs((double)Nq * (double)p.L / (double)p.M - (double)kq - exact);
+                    CHECK(e <= 4e-6, "delay_constant %ld/%ld N=%lu k=%lu: off by %g", (long)p.L, (long)p.M, (unsigned long)Nq, (unsigned long)kq, e);
+                    if (e > worst) worst = e;
+                    if (ep > worst_plain) worst_plain = ep;
+                }
+            }
+        }
+    }
+    CHECK(worst_plain > 0.05, "the plain expression at 2^50 was expected to be off by a tenth of a frame: %g", worst_plain);
+    std::printf("  delay_constant: worst error %.3g frames at counts up to 2^50 (the plain double expression: %.3g)\n", worst, worst_plain);
+    // variable rate: the clock moved by an integer pair gives the value of the clock at zero, bit for bit; against the exact quotient
+    VrState v;
+    v.on = true; v.s0 = v.s1 = q64(2.75625);
+    for (uint64_t n_in : {(uint64_t)441, (uint64_t)100003})
+        for (uint64_t k : {(uint64_t)0, (uint64_t)63, (uint64_t)150}) {
+            const double fresh = delay_vr(v, n_in, k);
+            CHECK(std::fabs(fresh - ((double)n_in - 2.75625 * (double)k) / 2.75625) < 1e-9, "delay_vr n_in=%lu k=%lu: %.17g", (unsigned long)n_in, (unsigned long)k, fresh);
+            for (uint64_t at : kMoveAt) {
+                VrState m = v;
+                m.k_s = at + 17; m.t_s = (i128)((u128)(at + 1000003) << 64);
+                CHECK(delay_vr(m, n_in + at + 1000003, k + at + 17) == fresh, "delay_vr moved to 2^%d differs", (int)std::log2((double)at));
+            }
+        }
+}
+
 int main()
 {
+    check_delay();
+    check_translation();
+    check_resident_msg();
     check_large_counts();
     check_k_avail();
     check_ring_keep();

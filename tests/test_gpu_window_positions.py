@@ -37,8 +37,9 @@ k_interp_tile job.  Compared here, tolerance zero (a result is a 
 
 Every kernel of the list is reachable with window fields: launch_typed / launch_gather (csrc/kernels.hip) read nothing of the
 window when they pick a form, and no launcher refuses or reroutes one.  Not reachable through a job at all — their positions
-come from a stream handle's counters, which no entry point sets: k_chain_multi, the variable-rate kernels (mode 2),
-k_chain_resident, launch_fft_window (profiles/NOTES_window_positions.md)."""
+come from a stream handle's counters, which no product entry point sets: k_chain_multi, the variable-rate kernels (mode 2),
+k_chain_resident, launch_fft_window.  tests/test_gpu_stream_positions.py holds those, through the debug-switch build's seek
+(profiles/NOTES_stream_positions.md)."""
 import hashlib
 import json
 import os
