@@ -153,13 +153,26 @@ typedef enum {
 /* Selector of hipsoxr_run_device_adjoint alone (job.kernel there; the forward entries refuse it by name), numbered on from
  * hipsoxr_kernel_t. */
 typedef enum {
-    HIPSOXR_KERNEL_ADJOINT = 10 /* hipsoxr_run_device_adjoint (and its _ragged form) only: the exact engine's transposed operator for EVERY
+    HIPSOXR_KERNEL_ADJOINT = 10, /* hipsoxr_run_device_adjoint (and its _ragged form) only: the exact engine's transposed operator for EVERY
                                   constant-rate plan.  On an exact-bank plan it runs what AUTO runs there, bit for bit; on an
                                   interpolated-phase plan (hipsoxr_plan_info_t::interpolated != 0, which AUTO and EXACT
                                   refuse) the gather-form adjoint on the plan's own interpolation table — the coefficients
                                   the forward's HIPSOXR_KERNEL_EXACT multiplies by, to the bit.  float32 / float64, whole
                                   signals, a clip_table on the _ragged entry alone, constant-rate plans (not hipsoxr_plan_create_vr's); refused by
                                   name otherwise, and on hipsoxr_run_device. */
+    HIPSOXR_KERNEL_ADJOINT_FFT = 11 /* the same two entries only: the transposed operator on the FREQUENCY-DOMAIN engine, for
+                                  exact-bank HQ / VHQ plans.  gx = A^T gy is computed as the forward float job of the plan's
+                                  transposed plan (L' = M, M' = L, the prototype mirrored: the same float64 coefficients) on the
+                                  kernels HIPSOXR_KERNEL_FFT runs — so it is in that engine's class, 1e-6 (float32) / 2e-9 VHQ,
+                                  1e-6 HQ (float64) relative RMS, not bit-identical to the exact adjoint, at about the
+                                  forward engine's cost for the reversed ratio.  float32 / float64 (HIPSOXR_F16 / _BF16 on the
+                                  equal-length entry: the float32 job on the widened cotangent, rounded once), whole
+                                  signals, every layout the engine serves for the reversed ratio, a clip_table on the _ragged
+                                  entry (one launch).  Opt-in by name only: AUTO and EXACT keep the exact adjoint, bit for bit.
+                                  Refused by name: integer types, variable-rate and interpolated-phase plans, recipes below
+                                  120 dB, in_abs0 / out_k0 != 0, a clip_table on the equal-length entry or none on the ragged
+                                  one; where the engine has no form for the plan or layout the call fails ("unavailable") —
+                                  it never runs the exact adjoint instead.  No new field, no new entry. */
 } hipsoxr_adjoint_kernel_t;
 
 typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase bank (host + device) */
@@ -282,7 +295,7 @@ typedef struct {
 } hipsoxr_job_t;
 /* ZERO-INITIALISE the struct (memset / = {0}) before filling it: fields are only ever APPENDED, a zero field always
  * means "feature not used", and hipsoxr_version() changes when one is added (0.1: up to dither_seed; 0.3: clip_table,
- * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form; no new field — the element types HIPSOXR_F16 / HIPSOXR_BF16; no new field — the entries hipsoxr_plan_vr_out_len and hipsoxr_run_device_vr_ragged).  A client compiled against an older header must not be run against a newer struct-consuming
+ * clip_table_dev; 0.6: no new field — the kernel selector HIPSOXR_KERNEL_FFT_PCM; 0.7: no new field — the stream flag HIPSOXR_STREAM_FFT; no new field — the selector HIPSOXR_KERNEL_ADJOINT; no new field — the entry hipsoxr_run_device_adjoint_ragged; no new field, no new entry — a clip_table on the exact engine is one launch; no new field, no new entry — a float clip_table of an interpolated-phase plan is a constant number of launches of the two-stage form; no new field — the element types HIPSOXR_F16 / HIPSOXR_BF16; no new field — the entries hipsoxr_plan_vr_out_len and hipsoxr_run_device_vr_ragged; no new field — the selector HIPSOXR_KERNEL_ADJOINT_FFT).  A client compiled against an older header must not be run against a newer struct-consuming
  * library without recompiling — check the version string at load time as soxr_amd/_native.py does. */
 
 /* Enqueue the job on `hip_stream` (a hipStream_t; NULL = default stream). Asynchronous. */

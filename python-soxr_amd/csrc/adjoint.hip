@@ -397,6 +397,7 @@ static void adj_free(AdjBank *b)
 
 void adjoint_release(const Plan *p)
 {
+    adjoint_fft_release(p); // (the transposed plan of HIPSOXR_KERNEL_ADJOINT_FFT lives and dies with these tables)
     std::lock_guard<std::mutex> lk(g_adj_mu);
     for (size_t i = 0; i < g_adj.size();)
         if (g_adj[i]->plan == p) {
@@ -616,6 +617,7 @@ static const char *adj_run(const Plan &p, const AdjBank *b, const hipsoxr_job_t 
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft(p, j, stream); // the frequency-domain engine, by name
     if (elem_is_half(j.elem)) {
         // float16 / bfloat16: the float32 adjoint on the widened cotangent, rounded once (half.hip) — under every selector
         // this entry serves for float32.  The refusals by name and the empty job first, asked of the float32 job without clips.
@@ -640,6 +642,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 // loops wrap.
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft_ragged(p, j, stream);
     const auto out_len = [&](uint64_t n) { return plan_out_len(*p, n); };
     if (const char *e = adj_entry_refusal(kAdjRagged, adj_ask(*p, j))) return e;
     for (uint32_t c = 0; c < j.n_clips; ++c)

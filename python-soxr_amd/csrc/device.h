@@ -209,6 +209,12 @@ const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &job, const uint64_t *
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &job, void *stream);
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &job, void *stream); // hipsoxr_run_device_adjoint_ragged: job.clip_table, one launch
 void adjoint_release(const Plan *p);
+// ... on the frequency-domain engine (adjoint_fft.hip; HIPSOXR_KERNEL_ADJOINT_FFT, which the two entries above hand over
+// first thing): the forward float job of the plan's transposed plan through launch_fft, or an error by name — never the
+// exact adjoint.  adjoint_fft_release drops the transposed plan (adjoint_release calls it).
+const char *launch_adjoint_fft(Plan *p, const hipsoxr_job_t &job, void *stream);
+const char *launch_adjoint_fft_ragged(Plan *p, const hipsoxr_job_t &job, void *stream);
+void adjoint_fft_release(const Plan *p);
 // float16 / bfloat16 jobs that no fused kernel takes (half.hip): one widening pass into stream-ordered float32 temporaries
 // packed in the caller's dimension order, the float32 job of the same selector (adjoint: through launch_adjoint, else
 // launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_table_clips, the clip-by-clip loop,

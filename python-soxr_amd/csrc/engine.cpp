@@ -19,6 +19,7 @@
 #include <new>
 #include <vector>
 
+#include "adjoint_fft_rules.h" // kAdjFftForwardRefusal
 #include "device.h"
 #include "vr_ragged_rules.h"
 
@@ -457,6 +458,7 @@ hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, 
     if (job->elem < 0 || job->elem > HIPSOXR_BF16) return "invalid element type";
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT)
         return "HIPSOXR_KERNEL_ADJOINT selects the transposed operator: it is valid on hipsoxr_run_device_adjoint only (forward jobs have AUTO, EXACT and the engines' own names)";
+    if (job->kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return kAdjFftForwardRefusal;
     if (job->out_frames < 0 || job->in_frames < 0 || job->out_k0 < 0) return "invalid job extent";
     if ((job->out_frames > 0 && !job->out) || (job->out_frames > 0 && job->in_frames > 0 && !job->in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;

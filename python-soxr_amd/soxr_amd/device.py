@@ -12,7 +12,8 @@ import numpy as np
 from . import _native as _n
 from . import _quality_to_enum
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
-                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT)
+                      KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT,
+                      KERNEL_ADJOINT_FFT)
 
 
 class Plan:
@@ -225,6 +226,12 @@ def _adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
     return None
 
 
+def _adjoint_forward_kernel(kernel):
+    """The forward selector an adjoint's own backward runs: the engine the adjoint ran on — KERNEL_FFT for
+    KERNEL_ADJOINT_FFT, the exact engine for every other selector."""
+    return _n.KERNEL_FFT if kernel == _n.KERNEL_ADJOINT_FFT else _n.KERNEL_EXACT
+
+
 def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO):
     """The transposed operator as a function: gx = A^T gy, where A is the resample of `in_frames` input frames that
     `resample_tensor(plan, x, kernel=KERNEL_EXACT)` computes (what its backward pass runs; the adjoint an iterative
@@ -241,7 +248,14 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO
     with kernel=KERNEL_EXACT multiplies by.  There a non-finite gy[k] reaches exactly the frames of its true support.
     Ragged batches: `dist.resample_ragged_adjoint` / `dist.resample_ragged`.  The two-stage form's adjoint, variable
     rate, streams and integer types are not served.  float16 / bfloat16 cotangents: the float32 adjoint on `gy.float()`,
-    rounded once (every selector above; not the ragged entry)."""
+    rounded once (every selector above; not the ragged entry).
+
+    kernel=KERNEL_ADJOINT_FFT: the adjoint on the frequency-domain engine, for exact-bank HQ / VHQ plans — the forward
+    float job of the plan's transposed plan (L' = M, M' = L, the mirrored prototype: the same coefficients) on the kernels
+    KERNEL_FFT runs, at about that engine's cost for the reversed ratio.  1e-6-class (float32; float64: 2e-9 VHQ, 1e-6
+    HQ), not bit-identical to the exact adjoint; opt-in by name, the defaults keep their bits.  Its own backward is the
+    forward with KERNEL_FFT.  Interpolated-phase and variable-rate plans, recipes below HQ and integer types are refused
+    by name, and a plan or layout the engine has no form for raises ("unavailable") — it never runs the exact adjoint."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch
@@ -300,7 +314,7 @@ def _autograd_fns():
 
         @staticmethod
         def backward(ctx, ggx):  # (the forward on the exact engine; its own gradient is this adjoint again, same selector)
-            y = resample_tensor(ctx.plan, ggx, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
+            y = resample_tensor(ctx.plan, ggx, kernel=_adjoint_forward_kernel(ctx.kernel), grad_kernel=ctx.kernel)
             return y.narrow(y.ndim - 2 if y.ndim > 1 else 0, 0, ctx.n_y), None, None, None
 
     _AUTOGRAD = (ResampleFn, AdjointFn)
@@ -336,6 +350,9 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     called — and the gradient is then the adjoint of the forward the exact engine computes on that plan.  Under
     kernel=KERNEL_AUTO a float job of an interpolated-phase plan runs the two-stage form, so forward and gradient agree in
     that form's class, 1e-6 (float32) / 2e-9 (float64); with kernel=KERNEL_EXACT they agree to rounding.
+    grad_kernel=KERNEL_ADJOINT_FFT (exact-bank HQ / VHQ plans): the backward runs on the frequency-domain engine, at about
+    the forward's own cost there instead of several times it — see `resample_tensor_adjoint`; forward and gradient agree
+    in that engine's class.  What it refuses is raised when the forward is called, as for the other selectors.
     """
     if x.is_cuda and x.requires_grad:
         import torch

@@ -341,7 +341,7 @@ def _ragged_autograd_fns():
         @staticmethod
         def backward(ctx, ggx):  # (the ragged forward on the exact engine; its own gradient is this adjoint again, same selector)
             xs = _split(ggx.contiguous(), ctx.n_x, [False] * len(ctx.n_x))
-            ys = resample_ragged(ctx.plan, xs, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
+            ys = resample_ragged(ctx.plan, xs, kernel=_dev._adjoint_forward_kernel(ctx.kernel), grad_kernel=ctx.kernel)
             need = ctx.needs_input_grad[3:]
             return (None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
                                               for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
@@ -361,7 +361,10 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
     [sum(in_frames), channels] buffer; every element is written.  Each clip has the bits of
     `device.resample_tensor_adjoint` on that clip alone (finite cotangents).  On the current torch stream,
     asynchronously.  Selectors as there: KERNEL_AUTO / KERNEL_EXACT on exact-bank plans, KERNEL_ADJOINT on every
-    constant-rate plan.  Differentiable: its backward is the ragged forward on the exact engine."""
+    constant-rate plan.  Differentiable: its backward is the ragged forward on the exact engine.
+    kernel=KERNEL_ADJOINT_FFT (exact-bank HQ / VHQ plans): the one launch runs on the frequency-domain engine — the clip
+    table read as a forward table of the plan's transposed plan; each clip is then within that engine's 1e-6 class of the
+    clip alone, not bit-equal to it, and the backward is the ragged forward with KERNEL_FFT."""
     import torch
     monos = [g.ndim == 1 for g in gys]
     if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
@@ -384,7 +387,8 @@ def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AU
     backward is the ragged forward with KERNEL_EXACT: one launch as well, on interpolated-phase plans too).  A clip
     that does not require grad gets none.  As for `device.resample_tensor`, the gradient is the EXACT engine's adjoint
     (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
-    interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called."""
+    interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called.
+    grad_kernel=KERNEL_ADJOINT_FFT: the backward's one launch runs on the frequency-domain engine (`resample_ragged_adjoint`)."""
     import torch
     if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
         why = _ragged_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
