@@ -160,7 +160,7 @@ typedef enum {
                                   the forward's HIPSOXR_KERNEL_EXACT multiplies by, to the bit.  float32 / float64, whole
                                   signals, a clip_table on the _ragged entry alone, constant-rate plans (not hipsoxr_plan_create_vr's); refused by
                                   name otherwise, and on hipsoxr_run_device. */
-    HIPSOXR_KERNEL_ADJOINT_FFT = 11 /* the same two entries only: the transposed operator on the FREQUENCY-DOMAIN engine, for
+    HIPSOXR_KERNEL_ADJOINT_FFT = 11, /* the same two entries only: the transposed operator on the FREQUENCY-DOMAIN engine, for
                                   exact-bank HQ / VHQ plans.  gx = A^T gy is computed as the forward float job of the plan's
                                   transposed plan (L' = M, M' = L, the prototype mirrored: the same float64 coefficients) on the
                                   kernels HIPSOXR_KERNEL_FFT runs — so it is in that engine's class, 1e-6 (float32) / 2e-9 VHQ,
@@ -173,6 +173,23 @@ typedef enum {
                                   120 dB, in_abs0 / out_k0 != 0, a clip_table on the equal-length entry or none on the ragged
                                   one; where the engine has no form for the plan or layout the call fails ("unavailable") —
                                   it never runs the exact adjoint instead.  No new field, no new entry. */
+    HIPSOXR_KERNEL_ADJOINT_TWO_STAGE = 12 /* hipsoxr_run_device_adjoint only: the transposed TWO-STAGE FORM, for the interpolated-phase
+                                  HQ / VHQ plans (arbitrary ratios: 48000 -> 44101, float rates) whose float forward AUTO runs on
+                                  that form.  gx = A^T gy with A the forward job the form runs for (in_frames = n_x, out_frames =
+                                  n_y), transposed stage by stage around the same intermediate window: the FFT stage's
+                                  transposed plan (1:2 <-> 2:1) on the kernels HIPSOXR_KERNEL_FFT runs, and k_poly_adj, the
+                                  gather-form transpose of the polyphase stage on the forward's own cubic table and position
+                                  arithmetic — no atomics, bitwise reproducible, at about the forward form's cost where
+                                  HIPSOXR_KERNEL_ADJOINT walks the plan's full tap count with a cubic per tap.  In the form's
+                                  class against the exact adjoint: 1e-6 (float32) / 2e-9 VHQ, 1e-6 HQ (float64) relative RMS.
+                                  float32 / float64 (HIPSOXR_F16 / _BF16: the float32 job on the widened cotangent, rounded
+                                  once), whole cotangents, any clips x channels and strides.  Opt-in by name only.  Refused by
+                                  name: integer types, variable-rate plans, exact-bank plans (HIPSOXR_KERNEL_ADJOINT_FFT serves
+                                  those), in_abs0 / out_k0 != 0, a clip_table, and the _ragged entry (clip tables are not served
+                                  yet); a plan without the form (below HQ, a bank installed from outside, steeper than 4:1), a
+                                  job it does not admit (fewer than 8192 frames either side, too many columns, LDS) or an FFT
+                                  stage that declines fails ("unavailable", naming HIPSOXR_KERNEL_ADJOINT as the exact
+                                  alternative) — it never runs the exact adjoint instead.  No new field, no new entry. */
 } hipsoxr_adjoint_kernel_t;
 
 typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase bank (host + device) */

@@ -85,6 +85,7 @@
 #include "adjoint_rules.h" // kAdjRS, floor_div, ceil_div; the tables, the launch forms, the refusals
 #include "device.h"
 #include "job_rules.h"
+#include "poly_adj_rules.h" // kPolyAdjRaggedRefusal
 
 namespace hipsoxr {
 
@@ -618,6 +619,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft(p, j, stream); // the frequency-domain engine, by name
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return launch_adjoint_two_stage(p, j, stream); // the two-stage form's transpose, by name
     if (elem_is_half(j.elem)) {
         // float16 / bfloat16: the float32 adjoint on the widened cotangent, rounded once (half.hip) — under every selector
         // this entry serves for float32.  The refusals by name and the empty job first, asked of the float32 job without clips.
@@ -643,6 +645,7 @@ const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft_ragged(p, j, stream);
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return kPolyAdjRaggedRefusal; // (poly_adj_rules.h: clip tables are not served yet)
     const auto out_len = [&](uint64_t n) { return plan_out_len(*p, n); };
     if (const char *e = adj_entry_refusal(kAdjRagged, adj_ask(*p, j))) return e;
     for (uint32_t c = 0; c < j.n_clips; ++c)

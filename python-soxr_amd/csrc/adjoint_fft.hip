@@ -44,6 +44,20 @@ void adjoint_fft_release(const Plan *p)
     delete pt; // (outside the lock: Plan::~Plan comes back here for pt itself)
 }
 
+// The transposed plan of an exact-bank plan (the two-stage form's adjoint builds its FFT stage's the same way)
+Plan *adj_fft_transposed(const Plan &p)
+{
+    Plan *pt = new Plan();
+    pt->in_rate = p.out_rate; pt->out_rate = p.in_rate;
+    pt->recipe = p.recipe; pt->q = p.q; pt->att_db = p.att_db; pt->beta = p.beta;
+    pt->L = p.M; pt->M = p.L; pt->T = adj_fft_taps(p.L, p.M, p.T);
+    pt->phases = 0; pt->vr = false;
+    pt->bank = adj_fft_bank(p);
+    pt->custom_bank = p.custom_bank;
+    pt->device = p.device;
+    return pt;
+}
+
 // The plan's transposed plan, built on first use (exact-bank plans; the caller has checked).
 static const char *adj_fft_ensure(Plan *p, Plan **out)
 {
@@ -55,14 +69,7 @@ static const char *adj_fft_ensure(Plan *p, Plan **out)
     std::lock_guard<std::mutex> lk2(g_adjfft_mu);
     for (const AdjFftPlan &e : g_adjfft)
         if (e.owner == p) { *out = e.pt; return nullptr; }
-    Plan *pt = new Plan();
-    pt->in_rate = p->out_rate; pt->out_rate = p->in_rate;
-    pt->recipe = p->recipe; pt->q = p->q; pt->att_db = p->att_db; pt->beta = p->beta;
-    pt->L = p->M; pt->M = p->L; pt->T = adj_fft_taps(p->L, p->M, p->T);
-    pt->phases = 0; pt->vr = false;
-    pt->bank = adj_fft_bank(*p);
-    pt->custom_bank = p->custom_bank;
-    pt->device = p->device;
+    Plan *pt = adj_fft_transposed(*p);
     g_adjfft.push_back({p, pt});
     *out = pt;
     return nullptr;

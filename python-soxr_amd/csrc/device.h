@@ -215,6 +215,13 @@ void adjoint_release(const Plan *p);
 const char *launch_adjoint_fft(Plan *p, const hipsoxr_job_t &job, void *stream);
 const char *launch_adjoint_fft_ragged(Plan *p, const hipsoxr_job_t &job, void *stream);
 void adjoint_fft_release(const Plan *p);
+// (adjoint_fft.hip) the transposed plan of an exact-bank plan as a fresh Plan the caller owns: L' = M, M' = L, the mirrored
+// prototype (adjoint_fft_rules.h), the forward's recipe and device — what both fast adjoints hand to launch_fft
+Plan *adj_fft_transposed(const Plan &p);
+// ... of the two-stage form (twostage.hip; HIPSOXR_KERNEL_ADJOINT_TWO_STAGE, handed over by launch_adjoint first thing):
+// interpolated-phase plans the forward two-stage form takes — the transposed plan of its FFT stage through launch_fft and
+// k_poly_adj, or an error by name — never the exact adjoint
+const char *launch_adjoint_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream);
 // float16 / bfloat16 jobs that no fused kernel takes (half.hip): one widening pass into stream-ordered float32 temporaries
 // packed in the caller's dimension order, the float32 job of the same selector (adjoint: through launch_adjoint, else
 // launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_table_clips, the clip-by-clip loop,

@@ -21,6 +21,7 @@
 
 #include "adjoint_fft_rules.h" // kAdjFftForwardRefusal
 #include "device.h"
+#include "poly_adj_rules.h" // kPolyAdjForwardRefusal
 #include "vr_ragged_rules.h"
 
 using namespace hipsoxr;
@@ -459,6 +460,7 @@ hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, 
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT)
         return "HIPSOXR_KERNEL_ADJOINT selects the transposed operator: it is valid on hipsoxr_run_device_adjoint only (forward jobs have AUTO, EXACT and the engines' own names)";
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return kAdjFftForwardRefusal;
+    if (job->kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return kPolyAdjForwardRefusal;
     if (job->out_frames < 0 || job->in_frames < 0 || job->out_k0 < 0) return "invalid job extent";
     if ((job->out_frames > 0 && !job->out) || (job->out_frames > 0 && job->in_frames > 0 && !job->in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;

@@ -29,7 +29,10 @@
 #include <mutex>
 #include <vector>
 
+#include "adjoint_rules.h" // adj_extent_refusal: the adjoint's length rule is the exact adjoint's
 #include "device.h"
+#include "job_rules.h"     // job_empty
+#include "poly_adj_rules.h"
 #include "poly_rules.h"
 #include "ragged_rules.h" // ragged_span_skip
 
@@ -54,6 +57,7 @@ struct TwoStage {
     // (lane_mul 0 = not simulated yet).  Written behind a const TwoStage & under g_lanes_mu.
     mutable PolyLane lanes[3][16] = {};
     void *tab_f = nullptr, *tab_d = nullptr; // device: [P2f][row] float4 / [P2][row] double4 records (a0..a3 of the cubic in x in [0, 1))
+    Plan *fft_t = nullptr;    // the transposed plan of `fft` (HIPSOXR_KERNEL_ADJOINT_TWO_STAGE: built on first use, released with this)
 };
 
 void twostage_release(Plan *p)
@@ -61,6 +65,7 @@ void twostage_release(Plan *p)
     if (!p->two) return;
     if (p->two->tab_f) (void)hipFree(p->two->tab_f);
     if (p->two->tab_d) (void)hipFree(p->two->tab_d);
+    delete p->two->fft_t;
     delete p->two; // (the FFT stage's plan releases its own device tables: Plan::~Plan)
     p->two = nullptr;
 }
@@ -234,7 +239,7 @@ template <typename Real> __device__ __forceinline__ const PolyArgs &poly_column_
     return v;
 }
 
-__device__ __forceinline__ int64_t floor_div(int64_t q, int64_t d) // d > 0
+__device__ __forceinline__ int64_t poly_floor_div(int64_t q, int64_t d) // d > 0
 {
     const int64_t n = q / d;
     return n * d > q ? n - 1 : n;
@@ -242,6 +247,54 @@ __device__ __forceinline__ int64_t floor_div(int64_t q, int64_t d) // d > 0
 template <typename Real> struct Rec4;
 template <> struct Rec4<float> { typedef float4 type; };
 template <> struct Rec4<double> { typedef double4 type; };
+
+// The position arithmetic of the polyphase stage, shared by k_poly, k_poly2 and k_poly_adj — one definition per element width,
+// so that the transpose multiplies by the coefficients of the very (n_k, interval, x) the forward used.
+// float32 path: output k sits at k_lo's exact position (one 64-bit division per thread and launch) plus (k - k_lo) steps of
+// Ms / Ls as a 64.64 binary fraction (step_fx is truncated: at most 2^-33 of a sample short after 2^31 outputs — a position
+// that is exactly an integer may land one sample lower with a fraction just under 1).
+struct PolyFx { int64_t nK0; uint64_t phK0; };
+__device__ __forceinline__ PolyFx poly_fx_origin(const PolyArgs &a)
+{
+    PolyFx o;
+    o.nK0 = poly_floor_div(a.k_lo * a.Ms, a.Ls);
+    o.phK0 = (uint64_t)((double)(a.k_lo * a.Ms - o.nK0 * a.Ls) * a.fx_per_rem); // remainder / Ls in units of 2^-64
+    return o;
+}
+// ... output k's sample n_k (returned) and fraction `ph`, from the origin: a closure over the kernel's own variables (this shape,
+// and each helper's below, is the one that leaves k_poly's instances instruction for instruction what they were)
+struct PolyPosFx {
+    const PolyArgs &a; const int64_t &nK0; const uint64_t &phK0;
+    __device__ int64_t operator()(int64_t k, uint64_t &ph) const
+    {
+        const uint64_t dk = (uint64_t)(k - a.k_lo), lo = dk * a.step_fx;
+        ph = phK0 + lo;
+        return nK0 + (int64_t)dk * a.Mq + (int64_t)__umul64hi(dk, a.step_fx) + (ph < lo ? 1 : 0);
+    }
+};
+// ... the table interval and the cubic's argument of a 64-bit fraction
+__device__ __forceinline__ void poly_fx_interval(uint64_t phase, int lg, uint32_t &i, float &x)
+{
+    const uint32_t hi = (uint32_t)(phase >> 32);
+    i = hi >> (32 - lg);
+    x = (float)(uint32_t)(hi << lg) * 0x1p-32f;
+}
+// float64 path (and float32 beyond MQ = 1): the exact rational position, k Ms = n Ls + rem, and the interval of rem / Ls
+__device__ __forceinline__ int64_t poly_exact_n(const PolyArgs &a, int64_t k) { return poly_floor_div(k * a.Ms, a.Ls); }
+__device__ __forceinline__ int64_t poly_exact_rem(const PolyArgs &a, int64_t k, int64_t n) { return k * a.Ms - n * a.Ls; }
+// ... f P, the interval floor(f P) — guarded against f P == P by rounding — and the cubic's argument.  (k_poly applies the
+// guard in its own text, the two lines of poly_exact_interval: moved into a function there, it reorders operands of two of
+// that kernel's additions.)
+__device__ __forceinline__ double poly_exact_fp(int64_t rem, double invL, int P) { return (double)rem * invL * (double)P; }
+template <typename Real> __device__ __forceinline__ Real poly_exact_x(double fP, int i) { return (Real)(fP - (double)i); }
+template <typename Real>
+__device__ __forceinline__ void poly_exact_interval(int64_t rem, double invL, int P, int &i, Real &x)
+{
+    const double fP = poly_exact_fp(rem, invL, P);
+    i = (int)fP;
+    if (i >= P) i = P - 1;
+    x = poly_exact_x<Real>(fP, i);
+}
 
 // TT = taps (compile time: the tap loop unrolls and every LDS read of an output is in flight at once).
 // MQ = floor(Ms / Ls) when that is 0 or 1 (every ratio the two-stage form takes but down-sampling beyond 2:1): consecutive
@@ -296,14 +349,10 @@ __global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type 
     int64_t nK0 = 0;
     uint64_t phK0 = 0;
     if constexpr (FAST) {
-        nK0 = floor_div(a.k_lo * a.Ms, a.Ls);
-        phK0 = (uint64_t)((double)(a.k_lo * a.Ms - nK0 * a.Ls) * a.fx_per_rem); // remainder / Ls in units of 2^-64
+        const PolyFx o = poly_fx_origin(a);
+        nK0 = o.nK0; phK0 = o.phK0;
     }
-    auto position = [&](int64_t k, uint64_t &ph) -> int64_t {
-        const uint64_t dk = (uint64_t)(k - a.k_lo), lo = dk * a.step_fx;
-        ph = phK0 + lo;
-        return nK0 + (int64_t)dk * a.Mq + (int64_t)__umul64hi(dk, a.step_fx) + (ph < lo ? 1 : 0);
-    };
+    const PolyPosFx position{a, nK0, phK0};
     const int slot = (tid * a.lane_mul) & 255; // this thread's run of R outputs within a tile
     constexpr int NPF = FAST ? 8 : 0; // float32 path: samples per thread of the NEXT tile's span held in registers
     Real pf[NPF > 0 ? NPF : 1];
@@ -335,7 +384,7 @@ __global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type 
             uint64_t ph;
             nA = position(kA, ph) - (H - 1); nB = position(kB, ph) + H;
         } else {
-            nA = floor_div(kA * a.Ms, a.Ls) - (H - 1); nB = floor_div(kB * a.Ms, a.Ls) + H;
+            nA = poly_floor_div(kA * a.Ms, a.Ls) - (H - 1); nB = poly_floor_div(kB * a.Ms, a.Ls) + H;
         }
         const int span = (int)(nB - nA + 1);
         if constexpr (FAST) { // the first NPF * 256 samples were fetched while the tile before was being computed
@@ -375,9 +424,9 @@ __global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type 
                 const int lg = a.lgP;
                 int left = (int)(kB - k1 + 1 < (int64_t)a.R ? kB - k1 + 1 : (int64_t)a.R);
                 for (; left > 0; --left) {
-                    const uint32_t hi = (uint32_t)(phase >> 32);
-                    const uint32_t i = hi >> (32 - lg);
-                    const float x = (float)(uint32_t)(hi << lg) * 0x1p-32f;
+                    uint32_t i;
+                    float x;
+                    poly_fx_interval(phase, lg, i, x);
                     const v4f *row = tabv + i * (uint32_t)a.row;
                     v2f s01e = {0.f, 0.f}, s23e = {0.f, 0.f}, s01o = {0.f, 0.f}, s23o = {0.f, 0.f};
 #pragma unroll
@@ -416,8 +465,8 @@ __global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type 
             }
         } else
         if (k1 <= kB) {
-            int64_t n = floor_div(k1 * a.Ms, a.Ls);
-            int64_t rem = k1 * a.Ms - n * a.Ls;
+            int64_t n = poly_exact_n(a, k1);
+            int64_t rem = poly_exact_rem(a, k1, n);
             const double invL = 1. / (double)a.Ls;
             Real u[TT];
             if constexpr (MQ >= 0) {
@@ -426,10 +475,10 @@ __global__ void __launch_bounds__(256) k_poly(typename PolyArgsOf<RAGGED>::type 
                 for (int j = 0; j < TT; ++j) u[j] = w[j];
             }
             for (int r = 0; r < a.R && k1 + r <= kB; ++r) {
-                const double fP = (double)rem * invL * (double)a.P;
+                const double fP = poly_exact_fp(rem, invL, a.P);
                 int i = (int)fP;
                 if (i >= a.P) i = a.P - 1;
-                const Real x = (Real)(fP - (double)i);
+                const Real x = poly_exact_x<Real>(fP, i);
                 const R4 *row = tab + (size_t)i * a.row;
                 const Real *w = xs + (n - nA - (H - 1));
                 Real acc0 = (Real)0, acc1 = (Real)0;
@@ -521,13 +570,9 @@ __global__ void __launch_bounds__(256, TT >= 32 ? 2 : POLY2_OCC) k_poly2(PolyArg
 #else
     constexpr int CH = TT % 16 == 0 ? 16 : TT % 12 == 0 ? 12 : TT % 8 == 0 ? 8 : 4; // taps whose LDS reads are in flight together
 #endif
-    const int64_t nK0 = floor_div(a.k_lo * a.Ms, a.Ls);
+    const int64_t nK0 = poly_floor_div(a.k_lo * a.Ms, a.Ls); // (poly_fx_origin's two lines)
     const uint64_t phK0 = (uint64_t)((double)(a.k_lo * a.Ms - nK0 * a.Ls) * a.fx_per_rem);
-    auto position = [&](int64_t k, uint64_t &ph) -> int64_t { // (as in k_poly)
-        const uint64_t dk = (uint64_t)(k - a.k_lo), lo = dk * a.step_fx;
-        ph = phK0 + lo;
-        return nK0 + (int64_t)dk * a.Mq + (int64_t)__umul64hi(dk, a.step_fx) + (ph < lo ? 1 : 0);
-    };
+    const PolyPosFx position{a, nK0, phK0}; // (as in k_poly)
     const int slot = (tid * a.lane_mul) & 255;
 #ifdef POLY_TRACE
     unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = __builtin_amdgcn_s_memtime();
@@ -602,9 +647,9 @@ __global__ void __launch_bounds__(256, TT >= 32 ? 2 : POLY2_OCC) k_poly2(PolyArg
             const int lg = a.lgP;
             int left = (int)(kB - k1 + 1 < (int64_t)a.R ? kB - k1 + 1 : (int64_t)a.R);
             for (; left > 0; --left) {
-                const uint32_t hi = (uint32_t)(phase >> 32);
-                const uint32_t i = hi >> (32 - lg);
-                const float x = (float)(uint32_t)(hi << lg) * 0x1p-32f;
+                uint32_t i;
+                float x;
+                poly_fx_interval(phase, lg, i, x);
                 const v4f *row = tab + i * (uint32_t)a.row;
                 // the cubic per tap ONCE for both channels (three scalar FMAs), then one packed FMA over the channel pair
                 // with the coefficient broadcast: 3 + 1 instructions per tap against k_poly's 2 x 2 for two channels
@@ -672,6 +717,126 @@ __global__ void __launch_bounds__(256, TT >= 32 ? 2 : POLY2_OCC) k_poly2(PolyArg
         o[5] = tq0; o[6] = tq; o[7] = 0;
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_poly_adj: the transpose of k_poly (HIPSOXR_KERNEL_ADJOINT_TWO_STAGE), in gather form — no atomics, a fixed order of
+// additions: bitwise reproducible.  The argument block is k_poly's, read in the forward's direction: `dst` is the stage's
+// output side and holds the cotangent gdst[k], k in [k_lo, k_lo + n_out) (READ here); `src` is its input side, and
+// gsrc[n] is WRITTEN for every n in [n_lo, n_src):
+//   gsrc[n] = sum over k in [k_lo, k_lo + n_out) with 0 <= j = n - n_k + T/2 - 1 < T  of  c_j(f_k) gdst[k]
+// with (n_k, interval, x) from the forward's own device functions for the element width (poly_fx_* where k_poly takes its
+// float32 path, poly_exact_* otherwise) — zeros where no output reaches.  A workgroup takes tiles of 256 R consecutive
+// samples of one column (grid row = column, tiles walked by the workgroup: the table is copied to LDS once):
+//   1. the outputs that can reach the tile (poly_adj_rules.h poly_adj_bracket: closed-form, conservative) are staged in LDS,
+//      one per lane and pass: {gdst[k], x} and {n_k - n_A, row offset of the interval};
+//   2. a thread owns R consecutive samples and walks the staged outputs that can reach them (poly_adj_run_span);
+//      membership is decided per (k, sample) by 0 <= j < T, and the record [interval][j] gives the coefficient;
+//   3. the tile's results are staged and leave as whole lines.
+// Work: T Ls / Ms contributions per sample — the forward's multiply-accumulates for the same job.
+// ---------------------------------------------------------------------------------------------
+template <typename Real> struct Rec2;
+template <> struct Rec2<float> { typedef float2 type; };
+template <> struct Rec2<double> { typedef double2 type; };
+
+template <typename Real, int TT>
+__global__ void __launch_bounds__(256) k_poly_adj(PolyArgs a)
+{
+    typedef typename Rec4<Real>::type R4;
+    typedef typename Rec2<Real>::type R2;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    R4 *tab = reinterpret_cast<R4 *>(smem);
+    R2 *gs = reinterpret_cast<R2 *>(smem + (size_t)a.P * a.row * sizeof(R4)); // [span_max] {gdst[k], x}
+    int2 *ni = reinterpret_cast<int2 *>(gs + a.span_max);                     // [span_max] {n_k - n_A, interval * row}
+    Real *ys = reinterpret_cast<Real *>(ni + a.span_max);                     // [256 R] the tile's results
+    const uint32_t col = blockIdx.y, ch = col % a.n_channels, clip = col / a.n_channels;
+    Real *gsrc = const_cast<Real *>((const Real *)a.src) + (int64_t)clip * a.scs + (int64_t)ch * a.schs;
+    const Real *gdst = (const Real *)a.dst + (int64_t)clip * a.dcs + (int64_t)ch * a.dchs;
+    const int tid = (int)threadIdx.x;
+    {
+        const R4 *g = (const R4 *)a.tab;
+        for (int i = tid; i < a.P * a.row; i += 256) tab[i] = g[i];
+    }
+    constexpr int H = TT / 2;
+    const bool fast = sizeof(Real) == 4 && (a.Mq == 0 || a.Mq == 1); // k_poly's FAST instances
+    PolyFx fx0 = {0, 0};
+    if (fast) fx0 = poly_fx_origin(a);
+    const PolyPosFx position{a, fx0.nK0, fx0.phK0};
+    const double invL = 1. / (double)a.Ls;
+    const int R = a.R;
+    const int64_t per_tile = 256LL * R, n_tiles = (a.n_src - a.n_lo + per_tile - 1) / per_tile;
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int64_t nA = a.n_lo + tile * per_tile, nB = (nA + per_tile < a.n_src ? nA + per_tile : a.n_src) - 1;
+        const PolyAdjSpan sp = poly_adj_bracket(nA, nB, TT, a.Ls, a.Ms, a.k_lo, a.n_out);
+        const int64_t cnt64 = sp.k_last - sp.k_first + 1;
+        const int cnt = (int)(cnt64 < 0 ? 0 : cnt64 > a.span_max ? a.span_max : cnt64); // (never above span_max: poly_adj_span_max)
+        for (int s = tid; s < cnt; s += 256) {
+            const int64_t k = sp.k_first + s;
+            int64_t n;
+            int i;
+            Real x;
+            if (fast) {
+                uint64_t ph;
+                uint32_t iu;
+                float xf;
+                n = position(k, ph);
+                poly_fx_interval(ph, a.lgP, iu, xf);
+                i = (int)iu; x = (Real)xf;
+            } else {
+                n = poly_exact_n(a, k);
+                poly_exact_interval<Real>(poly_exact_rem(a, k, n), invL, a.P, i, x);
+            }
+            R2 g;
+            g.x = gdst[(k - a.k_lo) * a.dfs]; g.y = x;
+            gs[s] = g;
+            ni[s] = make_int2((int)(n - nA), i * a.row);
+        }
+        __syncthreads();
+        const int64_t n0 = nA + (int64_t)tid * R;
+        Real acc[kPolyAdjRunMax];
+#pragma unroll
+        for (int r = 0; r < kPolyAdjRunMax; ++r) acc[r] = (Real)0;
+        if (n0 <= nB && cnt > 0) {
+            const int64_t n1 = n0 + R - 1 < nB ? n0 + R - 1 : nB;
+            int sF, sL;
+            poly_adj_run_span(n0, n1, TT, sp.k_first, a.Ls, a.Ms, cnt, &sF, &sL);
+            const int base = (int)(n0 - nA) + H - 1;
+            for (int s = sF; s <= sL; ++s) {
+                const int2 q = ni[s];
+                const R2 g = gs[s];
+                const int j0 = base - q.x; // j of the run's first sample
+#pragma unroll
+                for (int r = 0; r < kPolyAdjRunMax; ++r) {
+                    // (no branch: a tap outside [0, T) reads record T of the row — the table's spreading record, all zeros.
+                    //  Samples r >= R of a shorter run are computed and not stored.)
+                    const int j = j0 + r, jj = (unsigned)j < (unsigned)TT ? j : TT;
+                    const R4 c = tab[q.y + jj];
+                    acc[r] += (((c.w * g.y + c.z) * g.y + c.y) * g.y + c.x) * g.x;
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < kPolyAdjRunMax; ++r)
+            if (r < R) ys[tid * R + r] = acc[r];
+        __syncthreads(); // the tile's results are staged (and its staged outputs are free for the next tile)
+        {
+            Real *go = gsrc + nA * a.sfs;
+            const int n_res = (int)(nB - nA + 1);
+            for (int i = tid; i < n_res; i += 256) go[(int64_t)i * a.sfs] = ys[i];
+        }
+    }
+}
+
+// k_poly_adj's instances: one per tap count of HIPSOXR_POLY_TAPS and element type
+template <typename Real>
+static void (*poly_adj_kernel(int T2))(PolyArgs)
+{
+    switch (T2) {
+#define HIPSOXR_POLY_T(t) case t: return k_poly_adj<Real, t>;
+        HIPSOXR_POLY_TAPS(HIPSOXR_POLY_T)
+#undef HIPSOXR_POLY_T
+    }
+    return nullptr;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -905,6 +1070,152 @@ const char *launch_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream, bool
     HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)m.n_mid * es, st));
     const char *err = two_stage_run(p, j, m, mid, stream, handled);
     (void)hipFreeAsync(mid, st); // (behind whatever was queued: success, error and a declined FFT stage alike)
+    return err;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The adjoint of the two-stage form (HIPSOXR_KERNEL_ADJOINT_TWO_STAGE on hipsoxr_run_device_adjoint): gx = A^T gy, A the
+// forward job launch_two_stage runs for (in_frames = n_x, out_frames = n_y) — the same TwoStage, the same TwoStageMid, the
+// same intermediate window [-pad, n_core + pad) with zeros outside it: the structural transpose of the forward as launched.
+//   down (forward x --k_poly--> v --FFT 2:1, in_abs0 = -pad--> y):  gv = F^T gy, the forward float job of the FFT stage's
+//        TRANSPOSED PLAN (1:2; adjoint_fft_rules.h) with in_abs0 = pad / 2 into the intermediate; gx = P^T gv: k_poly_adj.
+//   up   (forward x --FFT 1:2, in_abs0 = pad / 2--> u --k_poly--> y):  gu = P^T gy: k_poly_adj over the whole window; gx =
+//        F^T gu, the transposed plan (2:1) with in_abs0 = -pad.
+// Every decision that reads only numbers is poly_adj_rules.h; the refusals are made by name before the device is asked for
+// anything, and a plan or job the form does not take fails with kPolyAdjUnavailable — never the exact adjoint.
+// ---------------------------------------------------------------------------------------------
+// HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): k_poly_adj's line, in poly_launch_log's style
+static void poly_adj_launch_log(size_t width, const PolyArgs &a, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid)
+{
+    FILE *fl = fopen(switches().dbg_launch_log, "a");
+    if (!fl) return;
+    fprintf(fl, "kernel=poly_adj width=%zu T=%d MQ=%d R=%d span_max=%d lds=%zu cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_lo=%lld n_src=%lld k_lo=%lld n_out=%lld\n",
+            width, a.T, a.Mq == 0 || a.Mq == 1 ? (int)a.Mq : -1, a.R, a.span_max, lds, (unsigned long long)cols, (long long)n_tiles, grid.x, grid.y, grid.z,
+            (long long)a.n_lo, (long long)a.n_src, (long long)a.k_lo, (long long)a.n_out);
+    fclose(fl);
+}
+
+// One k_poly_adj launch; j in the FORWARD's direction (src: the stage's input side, written; dst: its output side, read).
+// dry: everything but the launch — the run, the instance, the LDS attribute — so that nothing can fail behind a queued stage.
+template <typename Real>
+static const char *launch_poly_adj(const TwoStage &ts, const PolyJob &j, hipStream_t st, bool dry)
+{
+    constexpr size_t W = sizeof(Real);
+    const PolyStage s = poly_stage(ts.T2, W == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms);
+    PolyArgs a = poly_args(s, W == 4 ? ts.tab_f : ts.tab_d, poly_form_ragged(j.n_out), j);
+    const size_t tab_bytes = poly_tab_bytes(s.P, s.row, W);
+    a.R = poly_adj_run(tab_bytes, s.T2, s.ratio, W);
+    if (a.R <= 0) return kPolyAdjUnavailable; // (poly_adj_admits has asked: not reached)
+    a.lane_mul = 1;
+    a.span_max = poly_adj_span_max(poly_adj_tile(a.R), s.T2, s.ratio);
+    const size_t lds = poly_adj_lds_bytes(tab_bytes, a.R, s.T2, s.ratio, W);
+    void (*kern)(PolyArgs) = poly_adj_kernel<Real>(s.T2);
+    if (!kern) return "two-stage: no polyphase instance for this tap count";
+    if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
+    if (dry || j.n_src <= j.n_lo) return nullptr;
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    int dev = 0, n_cu = 256, per_cu = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 256, lds));
+    const int64_t n_tiles = poly_adj_tiles(j.n_src - j.n_lo, a.R);
+    const dim3 grid(poly_adj_grid_x(n_tiles, per_cu, n_cu, cols), (unsigned)cols, 1);
+    if (switches().dbg_launch_log) poly_adj_launch_log(W, a, lds, cols, n_tiles, grid);
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    return nullptr;
+}
+static const char *run_poly_adj(int elem, const TwoStage &ts, const PolyJob &j, hipStream_t st, bool dry)
+{
+    return elem == HIPSOXR_F32 ? launch_poly_adj<float>(ts, j, st, dry) : launch_poly_adj<double>(ts, j, st, dry);
+}
+
+// The two launches of an admitted adjoint job around the intermediate `mid` (m: the FORWARD job's layout)
+static const char *two_stage_adj_run(Plan *p, const hipsoxr_job_t &j, const TwoStageMid &m, void *mid, void *stream)
+{
+    const TwoStage &ts = *p->two;
+    const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
+    const int64_t n_y = j.in_frames, n_x = j.out_frames;
+    const int64_t ystr[3] = {j.in_clip_stride, j.in_frame_stride, j.in_chan_stride};
+    const int64_t xstr[3] = {j.out_clip_stride, j.out_frame_stride, j.out_chan_stride};
+    hipsoxr_job_t fj = j; // the FFT stage's transposed plan, forward, by name
+    fj.kernel = HIPSOXR_KERNEL_FFT;
+    fj.clip_counter = nullptr; fj.dither = 0; fj.dither_seed = 0; fj.clip_table = nullptr; fj.clip_table_dev = nullptr;
+    PolyJob pj;
+    pj.n_clips = j.n_clips; pj.n_channels = j.n_channels;
+    if (ts.up) { // gu = P^T gy over the whole window, then gx = F^T gu
+        pj.src = (char *)mid + (size_t)(m.pad * m.mstr[1]) * es; pj.n_lo = -m.pad; pj.n_src = m.n_core + m.pad; pj.sstr = m.mstr;
+        pj.dst = const_cast<void *>(j.in); pj.k_lo = 0; pj.n_out = n_y; pj.dstr = ystr;
+        fj.in = mid; fj.in_abs0 = -m.pad; fj.in_clip_stride = m.mstr[0]; fj.in_frame_stride = m.mstr[1]; fj.in_chan_stride = m.mstr[2];
+        fj.in_frames = m.n_mid; fj.out_frames = n_x;
+    } else {     // gv = F^T gy into the window, then gx = P^T gv
+        fj.in_abs0 = m.pad / 2;
+        fj.out = mid; fj.out_clip_stride = m.mstr[0]; fj.out_frame_stride = m.mstr[1]; fj.out_chan_stride = m.mstr[2];
+        fj.in_frames = n_y; fj.out_frames = m.n_mid;
+        pj.src = j.out; pj.n_lo = 0; pj.n_src = n_x; pj.sstr = xstr;
+        pj.dst = mid; pj.k_lo = -m.pad; pj.n_out = m.n_mid; pj.dstr = m.mstr;
+    }
+    if (const char *e = run_poly_adj(j.elem, ts, pj, (hipStream_t)stream, true)) return e; // (nothing queued yet)
+    bool fft_done = false;
+    if (!ts.up) {
+        if (const char *e = launch_fft(ts.fft_t, fj, stream, &fft_done)) return e;
+        if (!fft_done) return kPolyAdjUnavailable;
+    }
+    if (const char *e = run_poly_adj(j.elem, ts, pj, (hipStream_t)stream, false)) return e;
+    if (ts.up) {
+        if (const char *e = launch_fft(ts.fft_t, fj, stream, &fft_done)) return e;
+        if (!fft_done) return kPolyAdjUnavailable;
+    }
+    return nullptr;
+}
+
+// the plan's two-stage form with the transposed plan of its FFT stage, built on first use under the plan's mutex
+static const char *two_stage_adj_ensure(Plan *p)
+{
+    std::lock_guard<std::mutex> lk(p->mu);
+    if (!p->two)
+        if (const char *e = twostage_build(p)) return e;
+    TwoStage *ts = p->two;
+    if (ts->ok && !ts->fft_t) {
+        ts->fft_t = adj_fft_transposed(ts->fft);
+        ts->fft_t->device = p->device;
+    }
+    return nullptr;
+}
+
+const char *launch_adjoint_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream)
+{
+    if (elem_is_half(j.elem)) {
+        // float16 / bfloat16: the float32 job of this selector on the widened cotangent, rounded once (half.hip) — the
+        // refusals by name and the empty job first, asked of the float32 job without clips
+        hipsoxr_job_t f = j;
+        f.elem = HIPSOXR_F32; f.n_clips = 0;
+        if (const char *e = launch_adjoint_two_stage(p, f, stream)) return e;
+        if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
+        if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+        if (device_count() <= 0) return kNoDevice;
+        return launch_half(p, j, stream, true);
+    }
+    const PolyAdjAsk q = {j.elem == HIPSOXR_F32 || j.elem == HIPSOXR_F64, p->vr, p->phases == 0, j.in_abs0 != 0 || j.out_k0 != 0, j.clip_table != nullptr};
+    if (const char *e = poly_adj_refusal(q)) return e;
+    if (const char *e = adj_extent_refusal(kAdjEqual, j.in_frames, j.out_frames, [&](uint64_t n) { return plan_out_len(*p, n); })) return e;
+    if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
+    if (device_count() <= 0) return kNoDevice;
+    if (const char *e = two_stage_adj_ensure(p)) return e;
+    const TwoStage &ts = *p->two;
+    if (!ts.ok) return kPolyAdjUnavailable;
+    const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
+    const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    const int64_t n_y = j.in_frames, n_x = j.out_frames;
+    if (!poly_adj_admits(n_x, n_y, cols, es, poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms))) return kPolyAdjUnavailable;
+    const bool inter = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1;
+    const TwoStageMid m = two_stage_mid(ts.up, ts.T2, ts.Ls, ts.Ms, n_x, two_stage_mid_outputs(ts.up, ts.Ls, ts.Ms, n_x, n_y, ts.fft.T), j.n_channels, inter);
+    hipStream_t st = (hipStream_t)stream;
+    void *mid = nullptr;
+    HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)m.n_mid * es, st));
+    const char *err = two_stage_adj_run(p, j, m, mid, stream);
+    (void)hipFreeAsync(mid, st); // (behind whatever was queued)
     return err;
 }
 

@@ -63,6 +63,7 @@ STREAM_FFT = 512  # device-chunk streams on the frequency-domain engine (TensorS
 KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA, KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM = range(10)
 KERNEL_ADJOINT = 10  # hipsoxr_run_device_adjoint / _adjoint_ragged only: the transposed operator on every constant-rate plan (interpolated-phase plans too)
 KERNEL_ADJOINT_FFT = 11  # the same two entries only: the transposed operator on the frequency-domain engine (exact-bank HQ / VHQ plans; 1e-6-class)
+KERNEL_ADJOINT_TWO_STAGE = 12  # hipsoxr_run_device_adjoint only: the transposed two-stage form (interpolated-phase HQ / VHQ plans; 1e-6-class)
 ADJOINT_INTERP_TILE = 256  # frames per workgroup of k_adj_interp (csrc/adjoint.hip kAdjIW): where its tile edges fall
 
 

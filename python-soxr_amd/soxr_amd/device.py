@@ -13,7 +13,7 @@ from . import _native as _n
 from . import _quality_to_enum
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
                       KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT,
-                      KERNEL_ADJOINT_FFT)
+                      KERNEL_ADJOINT_FFT, KERNEL_ADJOINT_TWO_STAGE)
 
 
 class Plan:
@@ -228,7 +228,10 @@ def _adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
 
 def _adjoint_forward_kernel(kernel):
     """The forward selector an adjoint's own backward runs: the engine the adjoint ran on — KERNEL_FFT for
-    KERNEL_ADJOINT_FFT, the exact engine for every other selector."""
+    KERNEL_ADJOINT_FFT, KERNEL_AUTO (the two-stage form on the plans that selector serves) for KERNEL_ADJOINT_TWO_STAGE, the
+    exact engine for every other selector."""
+    if kernel == _n.KERNEL_ADJOINT_TWO_STAGE:
+        return _n.KERNEL_AUTO
     return _n.KERNEL_FFT if kernel == _n.KERNEL_ADJOINT_FFT else _n.KERNEL_EXACT
 
 
@@ -255,7 +258,17 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO
     KERNEL_FFT runs, at about that engine's cost for the reversed ratio.  1e-6-class (float32; float64: 2e-9 VHQ, 1e-6
     HQ), not bit-identical to the exact adjoint; opt-in by name, the defaults keep their bits.  Its own backward is the
     forward with KERNEL_FFT.  Interpolated-phase and variable-rate plans, recipes below HQ and integer types are refused
-    by name, and a plan or layout the engine has no form for raises ("unavailable") — it never runs the exact adjoint."""
+    by name, and a plan or layout the engine has no form for raises ("unavailable") — it never runs the exact adjoint.
+
+    kernel=KERNEL_ADJOINT_TWO_STAGE: the transposed two-stage form, for the interpolated-phase HQ / VHQ plans (arbitrary
+    ratios) whose float forward KERNEL_AUTO runs on that form — the transpose of that very job, stage by stage: the FFT
+    stage's transposed plan on the frequency-domain engine and `k_poly_adj`, the gather-form transpose of the polyphase
+    stage on the forward's own table and positions (no atomics: bitwise reproducible).  About the forward form's cost where
+    KERNEL_ADJOINT walks the plan's full tap count; in the form's class against the exact adjoint, 1e-6 (float32) / 2e-9
+    VHQ, 1e-6 HQ (float64).  Its own backward is the forward under KERNEL_AUTO.  float32 / float64 (float16 / bfloat16
+    widened), any clips x channels and strides.  Exact-bank and variable-rate plans, integer types and clip tables
+    (`dist.resample_ragged*`) are refused by name; a plan without the form, fewer than 8192 frames either side or an FFT
+    stage that declines raises ("unavailable", naming KERNEL_ADJOINT) — it never runs the exact adjoint."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch
@@ -353,6 +366,10 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     grad_kernel=KERNEL_ADJOINT_FFT (exact-bank HQ / VHQ plans): the backward runs on the frequency-domain engine, at about
     the forward's own cost there instead of several times it — see `resample_tensor_adjoint`; forward and gradient agree
     in that engine's class.  What it refuses is raised when the forward is called, as for the other selectors.
+    grad_kernel=KERNEL_ADJOINT_TWO_STAGE (interpolated-phase HQ / VHQ plans): the backward is the transpose of the two-stage
+    form that kernel=KERNEL_AUTO runs on such a plan, at about that form's cost — forward and gradient then transpose each
+    other to rounding, not only in the 1e-6 class.  Jobs the form does not admit (fewer than 8192 frames either side)
+    raise in backward ("unavailable"); no fast gradient is ever chosen by AUTO.
     """
     if x.is_cuda and x.requires_grad:
         import torch

@@ -364,7 +364,9 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
     constant-rate plan.  Differentiable: its backward is the ragged forward on the exact engine.
     kernel=KERNEL_ADJOINT_FFT (exact-bank HQ / VHQ plans): the one launch runs on the frequency-domain engine — the clip
     table read as a forward table of the plan's transposed plan; each clip is then within that engine's 1e-6 class of the
-    clip alone, not bit-equal to it, and the backward is the ragged forward with KERNEL_FFT."""
+    clip alone, not bit-equal to it, and the backward is the ragged forward with KERNEL_FFT.
+    kernel=KERNEL_ADJOINT_TWO_STAGE is passed through and refused by the C entry by name: the transposed two-stage form
+    does not serve clip tables yet (clip by clip: `device.resample_tensor_adjoint`)."""
     import torch
     monos = [g.ndim == 1 for g in gys]
     if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
@@ -388,7 +390,8 @@ def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AU
     that does not require grad gets none.  As for `device.resample_tensor`, the gradient is the EXACT engine's adjoint
     (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
     interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called.
-    grad_kernel=KERNEL_ADJOINT_FFT: the backward's one launch runs on the frequency-domain engine (`resample_ragged_adjoint`)."""
+    grad_kernel=KERNEL_ADJOINT_FFT: the backward's one launch runs on the frequency-domain engine (`resample_ragged_adjoint`).
+    grad_kernel=KERNEL_ADJOINT_TWO_STAGE: refused by name when the forward is called (no clip tables on that selector yet)."""
     import torch
     if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
         why = _ragged_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
