@@ -173,7 +173,7 @@ typedef enum {
                                   120 dB, in_abs0 / out_k0 != 0, a clip_table on the equal-length entry or none on the ragged
                                   one; where the engine has no form for the plan or layout the call fails ("unavailable") —
                                   it never runs the exact adjoint instead.  No new field, no new entry. */
-    HIPSOXR_KERNEL_ADJOINT_TWO_STAGE = 12 /* hipsoxr_run_device_adjoint only: the transposed TWO-STAGE FORM, for the interpolated-phase
+    HIPSOXR_KERNEL_ADJOINT_TWO_STAGE = 12, /* hipsoxr_run_device_adjoint only: the transposed TWO-STAGE FORM, for the interpolated-phase
                                   HQ / VHQ plans (arbitrary ratios: 48000 -> 44101, float rates) whose float forward AUTO runs on
                                   that form.  gx = A^T gy with A the forward job the form runs for (in_frames = n_x, out_frames =
                                   n_y), transposed stage by stage around the same intermediate window: the FFT stage's
@@ -190,6 +190,25 @@ typedef enum {
                                   job it does not admit (fewer than 8192 frames either side, too many columns, LDS) or an FFT
                                   stage that declines fails ("unavailable", naming HIPSOXR_KERNEL_ADJOINT as the exact
                                   alternative) — it never runs the exact adjoint instead.  No new field, no new entry. */
+    HIPSOXR_KERNEL_ADJOINT_AUTO = 13 /* hipsoxr_run_device_adjoint and hipsoxr_run_device_adjoint_ragged only: the TRANSPOSE OF THE
+                                  JOB THE FORWARD LAUNCHES UNDER HIPSOXR_KERNEL_AUTO for the same plan and shape — the selector that
+                                  picks a fast gradient where there is one and never answers "unavailable".  Exact-bank plan:
+                                  the frequency-domain engine (HIPSOXR_KERNEL_ADJOINT_FFT's launch) when the forward's outputs in
+                                  all — cotangent frames over clips or rows, times channels — reach 8192 on an HQ / VHQ plan and
+                                  the engine takes the transposed plan, else the exact adjoint.  Interpolated-phase plan, equal
+                                  lengths: the transposed two-stage form (HIPSOXR_KERNEL_ADJOINT_TWO_STAGE's launch) when the
+                                  plan has the form, the job is admitted (8192 frames either side) and the FFT stage accepts,
+                                  else k_adj_interp.  Interpolated-phase plan, clip table: per clip — a clip the form admits
+                                  alone runs on it (k_poly_adj's ragged instance and the FFT stage's transposed plan over the
+                                  table's columns: a constant number of launches per range of at most 1 GiB of intermediate),
+                                  every other clip in ONE ragged launch of the exact adjoint, a clip with n_x == 0 writes
+                                  nothing; each clip's engine, and on the exact adjoint its bits, are those of the clip alone.
+                                  HIPSOXR_NO_FFT / HIPSOXR_NO_TWO_STAGE send it to the exact adjoint as they send AUTO's forward
+                                  to the exact engine.  Where it resolves to a named selector the bits are that selector's.
+                                  Refused by name, as under HIPSOXR_KERNEL_ADJOINT: integer types, variable-rate plans, in_abs0 /
+                                  out_k0 != 0, a clip_table on the equal-length entry and none on the ragged one, HIPSOXR_F16 /
+                                  _BF16 on the ragged entry (the equal-length entry widens them), rows above the plan's output
+                                  length.  HIPSOXR_KERNEL_AUTO / _EXACT on these entries keep their meaning and their bits. */
 } hipsoxr_adjoint_kernel_t;
 
 typedef struct hipsoxr_plan hipsoxr_plan_t;     /* immutable: ratio + polyphase bank (host + device) */

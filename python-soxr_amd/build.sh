@@ -32,6 +32,8 @@ mkdir -p "$OBJ"
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/adjoint.hip" -o "$OBJ/adjoint.o" & P14=$!
 # (adjoint_fft.hip: the adjoint on the frequency-domain engine — host code alone: the transposed plan, handed to fft.hip)
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/adjoint_fft.hip" -o "$OBJ/adjoint_fft.o" & P19=$!
+# (adjoint_auto.hip: HIPSOXR_KERNEL_ADJOINT_AUTO — host code alone: the decision, handed to the three adjoint launchers)
+"$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/adjoint_auto.hip" -o "$OBJ/adjoint_auto.o" & P20=$!
 # (half.hip: the widening / narrowing passes of float16 / bfloat16 jobs no fused kernel takes — copies, no arithmetic)
 "$HIPCC" $COMMON -ffp-contract=off ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/half.hip" -o "$OBJ/half.o" & P15=$!
 # The A/B and timing-experiment switches (device.h `Switches`, everything but four product names) are read from the
@@ -56,8 +58,8 @@ FFTFLAGS="${HIPSOXR_FFTFLAGS:--ffp-contract=fast -fno-slp-vectorize}"
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -DFFT_PART=8 -c "$SRC/fft.hip" -o "$OBJ/fft8.o" & P18=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/twostage.hip" -o "$OBJ/twostage.o" & P9=$!
 "$HIPCC" $COMMON $FFTFLAGS ${HIPSOXR_EXTRA_FLAGS} -c "$SRC/fftwave.hip" -o "$OBJ/fftwave.o" & P10=$!
-wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13; wait $P14; wait $P15; wait $P16; wait $P17; wait $P18; wait $P19   # set -e: any failed compile aborts here
-OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/fft6.o $OBJ/fft7.o $OBJ/fft8.o $OBJ/half.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/adjoint.o $OBJ/adjoint_fft.o $OBJ/soxr_abi.o"
+wait $P1; wait $P2; wait $P3; wait $P4; wait $P5; wait $P6; wait $P7; wait $P9; wait $P10; wait $P11; wait $P12; wait $P13; wait $P14; wait $P15; wait $P16; wait $P17; wait $P18; wait $P19; wait $P20   # set -e: any failed compile aborts here
+OBJS="$OBJ/plan.o $OBJ/engine.o $OBJ/kernels.o $OBJ/fft.o $OBJ/fft1.o $OBJ/fft2.o $OBJ/fft3.o $OBJ/fft4.o $OBJ/fft5.o $OBJ/fft6.o $OBJ/fft7.o $OBJ/fft8.o $OBJ/half.o $OBJ/twostage.o $OBJ/fftwave.o $OBJ/adjoint.o $OBJ/adjoint_fft.o $OBJ/adjoint_auto.o $OBJ/soxr_abi.o"
 "$HIPCC" --offload-arch=gfx950 -shared -fPIC $OBJS -o "$OUT"
 # The same engine under libsoxr's name: what `find_library(SOXR_LIBRARY NAMES soxr)` of the
 # reference's USE_SYSTEM_LIBSOXR build picks up (reference CMakeLists.txt:83-93).

@@ -615,11 +615,21 @@ static const char *adj_run(const Plan &p, const AdjBank *b, const hipsoxr_job_t 
     return with_real(j.elem, [&](auto r) { return adj_launch<decltype(r)>(*b, j, st, rows); });
 }
 
+// (device.h) the exact adjoint behind the entries' refusals, for the launchers that resolve to it or hand it a sub-table
+// (adjoint_auto.hip, twostage.hip): the tables, then — unless dry — the launch; rows: the device copy of a clip table, or NULL
+const char *adj_exact_run(Plan *p, const hipsoxr_job_t &j, void *stream, const int64_t *rows, bool dry)
+{
+    AdjBank *b = nullptr;
+    if (const char *e = adj_tables_ensure(p, j, &b)) return e;
+    return dry ? nullptr : adj_run(*p, b, j, (hipStream_t)stream, rows);
+}
+
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     // the job is read in the adjoint's own direction: in = gy (in_frames = n_y), out = gx (out_frames = n_x)
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft(p, j, stream); // the frequency-domain engine, by name
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return launch_adjoint_two_stage(p, j, stream); // the two-stage form's transpose, by name
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_AUTO) return launch_adjoint_auto(p, j, stream); // the transpose of AUTO's forward (adjoint_auto.hip)
     if (elem_is_half(j.elem)) {
         // float16 / bfloat16: the float32 adjoint on the widened cotangent, rounded once (half.hip) — under every selector
         // this entry serves for float32.  The refusals by name and the empty job first, asked of the float32 job without clips.
@@ -646,6 +656,7 @@ const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
 {
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return launch_adjoint_fft_ragged(p, j, stream);
     if (j.kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return kPolyAdjRaggedRefusal; // (poly_adj_rules.h: clip tables are not served yet)
+    if (j.kernel == HIPSOXR_KERNEL_ADJOINT_AUTO) return launch_adjoint_auto_ragged(p, j, stream);
     const auto out_len = [&](uint64_t n) { return plan_out_len(*p, n); };
     if (const char *e = adj_entry_refusal(kAdjRagged, adj_ask(*p, j))) return e;
     for (uint32_t c = 0; c < j.n_clips; ++c)

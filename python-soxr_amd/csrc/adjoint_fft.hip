@@ -94,8 +94,11 @@ static const char *adj_fft_device_refusal(const hipsoxr_job_t &j)
 }
 
 // The float job of pt the engine runs: by name, no integer output stage.  rows: the device copy of a clip table, or NULL.
-static const char *adj_fft_run(Plan *p, const hipsoxr_job_t &j, void *stream, const int64_t *rows)
+// *handled_out = false with no error: the engine declined before anything was queued (HIPSOXR_KERNEL_ADJOINT_AUTO then runs the
+// exact adjoint: adjoint_auto.hip).
+const char *adj_fft_try(Plan *p, const hipsoxr_job_t &j, void *stream, const int64_t *rows, bool *handled_out)
 {
+    *handled_out = false;
     Plan *pt = nullptr;
     if (const char *e = adj_fft_ensure(p, &pt)) return e;
     hipsoxr_job_t f = j;
@@ -104,6 +107,14 @@ static const char *adj_fft_run(Plan *p, const hipsoxr_job_t &j, void *stream, co
     f.clip_table_dev = rows;
     bool handled = false;
     if (const char *e = launch_fft(pt, f, stream, &handled)) return e;
+    *handled_out = handled;
+    return nullptr;
+}
+// ... by name: a decline is an error
+static const char *adj_fft_run(Plan *p, const hipsoxr_job_t &j, void *stream, const int64_t *rows)
+{
+    bool handled = false;
+    if (const char *e = adj_fft_try(p, j, stream, rows, &handled)) return e;
     return handled ? nullptr : kAdjFftUnavailable;
 }
 

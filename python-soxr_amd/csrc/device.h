@@ -222,6 +222,20 @@ Plan *adj_fft_transposed(const Plan &p);
 // interpolated-phase plans the forward two-stage form takes — the transposed plan of its FFT stage through launch_fft and
 // k_poly_adj, or an error by name — never the exact adjoint
 const char *launch_adjoint_two_stage(Plan *p, const hipsoxr_job_t &job, void *stream);
+// ... and the transpose of the job HIPSOXR_KERNEL_AUTO launches (adjoint_auto.hip; HIPSOXR_KERNEL_ADJOINT_AUTO, handed over by both
+// entries first thing): the frequency-domain engine, the transposed two-stage form — a clip table too — or the exact adjoint,
+// by adjoint_auto_rules.h; never "unavailable".  It puts together the inner functions of the three launchers:
+//   adj_fft_try (adjoint_fft.hip): the transposed plan's float job through launch_fft; *handled = false, nothing queued: declined
+//   launch_adjoint_two_stage_try (twostage.hip): the equal-length transposed form behind its refusals; *handled as above
+//   launch_adjoint_two_stage_ragged (twostage.hip): a validated clip table — per range k_poly_adj<.., RAGGED> and the FFT stage's
+//     transposed plan, the short clips through adj_exact_run; *handled = false: gx untouched, the exact adjoint takes the table
+//   adj_exact_run (adjoint.hip): the exact adjoint's tables and — unless dry — its launch; rows: a table's device copy, or NULL
+const char *launch_adjoint_auto(Plan *p, const hipsoxr_job_t &job, void *stream);
+const char *launch_adjoint_auto_ragged(Plan *p, const hipsoxr_job_t &job, void *stream);
+const char *adj_fft_try(Plan *p, const hipsoxr_job_t &job, void *stream, const int64_t *rows, bool *handled);
+const char *launch_adjoint_two_stage_try(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+const char *launch_adjoint_two_stage_ragged(Plan *p, const hipsoxr_job_t &job, void *stream, bool *handled);
+const char *adj_exact_run(Plan *p, const hipsoxr_job_t &job, void *stream, const int64_t *rows, bool dry);
 // float16 / bfloat16 jobs that no fused kernel takes (half.hip): one widening pass into stream-ordered float32 temporaries
 // packed in the caller's dimension order, the float32 job of the same selector (adjoint: through launch_adjoint, else
 // launch_job), one narrowing pass over exactly the job's output elements.  No clip_table (launch_table_clips, the clip-by-clip loop,

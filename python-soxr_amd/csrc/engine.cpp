@@ -19,6 +19,7 @@
 #include <new>
 #include <vector>
 
+#include "adjoint_auto_rules.h" // kAdjAutoForwardRefusal
 #include "adjoint_fft_rules.h" // kAdjFftForwardRefusal
 #include "device.h"
 #include "poly_adj_rules.h" // kPolyAdjForwardRefusal
@@ -461,6 +462,7 @@ hipsoxr_error_t hipsoxr_run_device(hipsoxr_plan_t *h, const hipsoxr_job_t *job, 
         return "HIPSOXR_KERNEL_ADJOINT selects the transposed operator: it is valid on hipsoxr_run_device_adjoint only (forward jobs have AUTO, EXACT and the engines' own names)";
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT_FFT) return kAdjFftForwardRefusal;
     if (job->kernel == HIPSOXR_KERNEL_ADJOINT_TWO_STAGE) return kPolyAdjForwardRefusal;
+    if (job->kernel == HIPSOXR_KERNEL_ADJOINT_AUTO) return kAdjAutoForwardRefusal;
     if (job->out_frames < 0 || job->in_frames < 0 || job->out_k0 < 0) return "invalid job extent";
     if ((job->out_frames > 0 && !job->out) || (job->out_frames > 0 && job->in_frames > 0 && !job->in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;

@@ -97,6 +97,18 @@ inline int poly_adj_run(size_t tab_bytes, int32_t T2, double ratio, size_t width
 inline int64_t poly_adj_tiles(int64_t n_samples, int R) { return (n_samples + poly_adj_tile(R) - 1) / poly_adj_tile(R); }
 // the grid: workgroups walk tiles (the table is loaded once per workgroup) — the forward's rule, one column per grid row
 inline unsigned poly_adj_grid_x(int64_t n_tiles, int per_cu, int n_cu, uint64_t cols) { return poly_grid_x(n_tiles, per_cu, n_cu, cols); }
+// ... a clip table's columns are of unequal length, and the grid's x is the longest column's: with as many workgroups as the
+// chip holds, the short columns' workgroups leave early and their slots stay empty until the longest column's have walked all
+// its tiles (64 clips of 1-10 s: 41 % of the launch), and the forward's multiple-of-8 rule drops 12 workgroups per column to 8.
+// So a column gets kPolyAdjRaggedOver times its share of the slots, no rounding: the workgroups behind the first round start
+// as earlier columns finish, which levels the columns (the table is copied once per workgroup: 17-50 KB against the 4
+// tiles or more each still walks).  n_tiles: the longest column's.
+constexpr int kPolyAdjRaggedOver = 4;
+inline unsigned poly_adj_grid_x_ragged(int64_t n_tiles, int per_cu, int n_cu, uint64_t cols)
+{
+    const int64_t want = std::max<int64_t>(1, (int64_t)kPolyAdjRaggedOver * std::max(per_cu, 1) * n_cu / (int64_t)cols);
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_tiles, want));
+}
 
 // ---- the job ---------------------------------------------------------------------------------------------------------------
 // The adjoint job in = gy (n_y frames), out = gx (n_x frames) transposes the forward job (in_frames = n_x, out_frames = n_y):

@@ -299,15 +299,18 @@ struct RaggedPolyPlan {
 };
 // rows: the caller's table; in_chs / out_chs: its channel strides (the frame strides are the launcher's: offsets here are of sample 0); fft_T: the FFT stage's taps; budget:
 // kPolyMidBudget (the debug-switch build may lower it)
-inline RaggedPolyPlan ragged_poly_plan(const int64_t *rows, uint32_t n_clips, uint32_t n_channels, int64_t in_chs, int64_t out_chs, size_t width, bool up,
-                                       const PolyStage &s, int32_t fft_T, int64_t budget)
+// ... over the partition `cls(in frames, out frames)` -> RaggedPolyClass: the forward's is ragged_poly_class (below); the
+// transposed form asks its own question of the same table (adjoint_auto_rules.h) and takes everything else from here
+template <typename ClassOf>
+inline RaggedPolyPlan ragged_poly_plan_by(const int64_t *rows, uint32_t n_clips, uint32_t n_channels, int64_t in_chs, int64_t out_chs, size_t width, bool up,
+                                          const PolyStage &s, int32_t fft_T, int64_t budget, ClassOf cls)
 {
     RaggedPolyPlan r;
     r.pad = two_stage_mid(up, s.T2, s.Ls, s.Ms, 0, 0, 1, false).pad;
     r.cls.resize(n_clips);
     for (uint32_t c = 0; c < n_clips; ++c) {
         const int64_t *row = rows + 4 * (size_t)c;
-        r.cls[c] = (uint8_t)ragged_poly_class(row[1], row[3], n_channels, width, s);
+        r.cls[c] = (uint8_t)cls(row[1], row[3]);
         if (r.cls[c] == kRaggedPolyShort) r.short_rows.insert(r.short_rows.end(), row, row + 4);
         if (r.cls[c] != kRaggedPolyTwo) continue;
         for (uint32_t ch = 0; ch < n_channels; ++ch) {
@@ -343,6 +346,12 @@ inline RaggedPolyPlan ragged_poly_plan(const int64_t *rows, uint32_t n_clips, ui
     }
     if (g.count) r.ranges.push_back(g);
     return r;
+}
+inline RaggedPolyPlan ragged_poly_plan(const int64_t *rows, uint32_t n_clips, uint32_t n_channels, int64_t in_chs, int64_t out_chs, size_t width, bool up,
+                                       const PolyStage &s, int32_t fft_T, int64_t budget)
+{
+    return ragged_poly_plan_by(rows, n_clips, n_channels, in_chs, out_chs, width, up, s, fft_T, budget,
+                               [&](int64_t n, int64_t n_out) { return ragged_poly_class(n, n_out, n_channels, width, s); });
 }
 // the form of a ragged polyphase launch: k_poly, one column per grid row (k_poly2 has no ragged form)
 inline PolyForm poly_form_ragged(int64_t longest) { return PolyForm{false, false, 0, longest, longest, 0, 0, 0}; }

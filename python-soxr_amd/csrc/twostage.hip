@@ -29,6 +29,7 @@
 #include <mutex>
 #include <vector>
 
+#include "adjoint_auto_rules.h" // ragged_poly_adj_plan: a clip table on the transposed form
 #include "adjoint_rules.h" // adj_extent_refusal: the adjoint's length rule is the exact adjoint's
 #include "device.h"
 #include "job_rules.h"     // job_empty
@@ -739,11 +740,22 @@ template <typename Real> struct Rec2;
 template <> struct Rec2<float> { typedef float2 type; };
 template <> struct Rec2<double> { typedef double2 type; };
 
-template <typename Real, int TT>
-__global__ void __launch_bounds__(256) k_poly_adj(PolyArgs a)
+// RAGGED (a clip table on the transposed form, launch_adjoint_two_stage_ragged): as for k_poly, a second instantiation whose
+// argument block carries the device rows behind the usual arguments — the equal-length instances keep theirs, instruction for
+// instruction.  One grid row per (clip, channel) COLUMN (blockIdx.y; one channel, clip strides 0); the column's row {src offset
+// of sample 0, n_src, dst offset of output k_lo, n_out} — the FORWARD's poly row as it stands: dst is read, src written —
+// replaces the job-wide n_src / n_out; n_lo and k_lo stay job-wide.  R and the LDS size do not depend on length
+// (poly_adj_run), the grid's x axis is the longest column's: a workgroup whose first tile lies at or behind its column's end
+// leaves before the table is copied and before the first barrier, and the tile loop's bound is the column's own — both
+// uniform over the workgroup (block index and row alone), so no barrier is met by part of a workgroup.
+template <typename Real, int TT, bool RAGGED = false>
+__global__ void __launch_bounds__(256) k_poly_adj(typename PolyArgsOf<RAGGED>::type a_)
 {
     typedef typename Rec4<Real>::type R4;
     typedef typename Rec2<Real>::type R2;
+    PolyArgs a_row;
+    const PolyArgs a = poly_column_args<Real>(a_, a_row); // (a copy: through a reference the equal-length instances' tile-count select changes by one instruction)
+    if (RAGGED && ragged_span_skip(blockIdx.x, 256LL * a.R, a.n_src - a.n_lo)) return; // (uniform: none of this column's tiles is this workgroup's)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     R4 *tab = reinterpret_cast<R4 *>(smem);
     R2 *gs = reinterpret_cast<R2 *>(smem + (size_t)a.P * a.row * sizeof(R4)); // [span_max] {gdst[k], x}
@@ -828,11 +840,11 @@ __global__ void __launch_bounds__(256) k_poly_adj(PolyArgs a)
 }
 
 // k_poly_adj's instances: one per tap count of HIPSOXR_POLY_TAPS and element type
-template <typename Real>
-static void (*poly_adj_kernel(int T2))(PolyArgs)
+template <typename Real, bool RAGGED = false>
+static void (*poly_adj_kernel(int T2))(typename PolyArgsOf<RAGGED>::type)
 {
     switch (T2) {
-#define HIPSOXR_POLY_T(t) case t: return k_poly_adj<Real, t>;
+#define HIPSOXR_POLY_T(t) case t: return k_poly_adj<Real, t, RAGGED>;
         HIPSOXR_POLY_TAPS(HIPSOXR_POLY_T)
 #undef HIPSOXR_POLY_T
     }
@@ -1085,18 +1097,20 @@ const char *launch_two_stage(Plan *p, const hipsoxr_job_t &j, void *stream, bool
 // anything, and a plan or job the form does not take fails with kPolyAdjUnavailable — never the exact adjoint.
 // ---------------------------------------------------------------------------------------------
 // HIPSOXR_DEBUG_LAUNCH_LOG (debug-switch build only): k_poly_adj's line, in poly_launch_log's style
-static void poly_adj_launch_log(size_t width, const PolyArgs &a, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid)
+// A ragged launch appends ragged=1 (tiles, n_src, n_out: the longest column's).
+static void poly_adj_launch_log(size_t width, const PolyArgs &a, size_t lds, uint64_t cols, int64_t n_tiles, dim3 grid, bool ragged)
 {
     FILE *fl = fopen(switches().dbg_launch_log, "a");
     if (!fl) return;
-    fprintf(fl, "kernel=poly_adj width=%zu T=%d MQ=%d R=%d span_max=%d lds=%zu cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_lo=%lld n_src=%lld k_lo=%lld n_out=%lld\n",
+    fprintf(fl, "kernel=poly_adj width=%zu T=%d MQ=%d R=%d span_max=%d lds=%zu cols=%llu tiles=%lld grid=%ux%ux%u block=256 n_lo=%lld n_src=%lld k_lo=%lld n_out=%lld%s\n",
             width, a.T, a.Mq == 0 || a.Mq == 1 ? (int)a.Mq : -1, a.R, a.span_max, lds, (unsigned long long)cols, (long long)n_tiles, grid.x, grid.y, grid.z,
-            (long long)a.n_lo, (long long)a.n_src, (long long)a.k_lo, (long long)a.n_out);
+            (long long)a.n_lo, (long long)a.n_src, (long long)a.k_lo, (long long)a.n_out, ragged ? " ragged=1" : "");
     fclose(fl);
 }
 
 // One k_poly_adj launch; j in the FORWARD's direction (src: the stage's input side, written; dst: its output side, read).
 // dry: everything but the launch — the run, the instance, the LDS attribute — so that nothing can fail behind a queued stage.
+// j.rows (launch_adjoint_two_stage_ragged): the ragged instance over the table's columns, j.n_src the longest column's.
 template <typename Real>
 static const char *launch_poly_adj(const TwoStage &ts, const PolyJob &j, hipStream_t st, bool dry)
 {
@@ -1109,19 +1123,28 @@ static const char *launch_poly_adj(const TwoStage &ts, const PolyJob &j, hipStre
     a.lane_mul = 1;
     a.span_max = poly_adj_span_max(poly_adj_tile(a.R), s.T2, s.ratio);
     const size_t lds = poly_adj_lds_bytes(tab_bytes, a.R, s.T2, s.ratio, W);
-    void (*kern)(PolyArgs) = poly_adj_kernel<Real>(s.T2);
-    if (!kern) return "two-stage: no polyphase instance for this tap count";
-    if (const char *e = ensure_dyn_lds((const void *)kern, lds)) return e;
+    void (*kern)(PolyArgs) = j.rows ? nullptr : poly_adj_kernel<Real>(s.T2);
+    void (*kern_r)(PolyArgsR) = j.rows ? poly_adj_kernel<Real, true>(s.T2) : nullptr;
+    const void *fn = j.rows ? (const void *)kern_r : (const void *)kern;
+    if (!fn) return "two-stage: no polyphase instance for this tap count";
+    if (const char *e = ensure_dyn_lds(fn, lds)) return e;
     if (dry || j.n_src <= j.n_lo) return nullptr;
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
+    if (cols > kPolyMaxCols) return "two-stage: too many columns"; // (poly_adj_admits / the ranges have asked: not reached)
     int dev = 0, n_cu = 256, per_cu = 0;
     HIP_TRY(hipGetDevice(&dev));
     HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)kern, 256, lds));
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds));
     const int64_t n_tiles = poly_adj_tiles(j.n_src - j.n_lo, a.R);
-    const dim3 grid(poly_adj_grid_x(n_tiles, per_cu, n_cu, cols), (unsigned)cols, 1);
-    if (switches().dbg_launch_log) poly_adj_launch_log(W, a, lds, cols, n_tiles, grid);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
+    const dim3 grid(j.rows ? poly_adj_grid_x_ragged(n_tiles, per_cu, n_cu, cols) : poly_adj_grid_x(n_tiles, per_cu, n_cu, cols), (unsigned)cols, 1);
+    if (switches().dbg_launch_log) poly_adj_launch_log(W, a, lds, cols, n_tiles, grid, j.rows != nullptr);
+    if (j.rows) {
+        PolyArgsR ar;
+        (PolyArgs &)ar = a;
+        ar.rows = j.rows;
+        hipLaunchKernelGGL(kern_r, grid, dim3(256), lds, st, ar);
+    } else
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a);
     HIP_TRY(hipGetLastError());
     return nullptr;
 }
@@ -1130,8 +1153,10 @@ static const char *run_poly_adj(int elem, const TwoStage &ts, const PolyJob &j, 
     return elem == HIPSOXR_F32 ? launch_poly_adj<float>(ts, j, st, dry) : launch_poly_adj<double>(ts, j, st, dry);
 }
 
-// The two launches of an admitted adjoint job around the intermediate `mid` (m: the FORWARD job's layout)
-static const char *two_stage_adj_run(Plan *p, const hipsoxr_job_t &j, const TwoStageMid &m, void *mid, void *stream)
+// The two launches of an admitted adjoint job around the intermediate `mid` (m: the FORWARD job's layout).  *handled = false
+// with no error: the FFT stage declined — down: before anything was queued; up: behind k_poly_adj, which wrote the
+// intermediate only — and gx is untouched either way.
+static const char *two_stage_adj_run(Plan *p, const hipsoxr_job_t &j, const TwoStageMid &m, void *mid, void *stream, bool *handled)
 {
     const TwoStage &ts = *p->two;
     const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
@@ -1159,13 +1184,14 @@ static const char *two_stage_adj_run(Plan *p, const hipsoxr_job_t &j, const TwoS
     bool fft_done = false;
     if (!ts.up) {
         if (const char *e = launch_fft(ts.fft_t, fj, stream, &fft_done)) return e;
-        if (!fft_done) return kPolyAdjUnavailable;
+        if (!fft_done) return nullptr;
     }
     if (const char *e = run_poly_adj(j.elem, ts, pj, (hipStream_t)stream, false)) return e;
     if (ts.up) {
         if (const char *e = launch_fft(ts.fft_t, fj, stream, &fft_done)) return e;
-        if (!fft_done) return kPolyAdjUnavailable;
+        if (!fft_done) return nullptr;
     }
+    *handled = true;
     return nullptr;
 }
 
@@ -1202,19 +1228,31 @@ const char *launch_adjoint_two_stage(Plan *p, const hipsoxr_job_t &j, void *stre
     if (job_empty(j.out_frames, j.n_clips, j.n_channels)) return nullptr;
     if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;
+    bool handled = false;
+    if (const char *e = launch_adjoint_two_stage_try(p, j, stream, &handled)) return e;
+    return handled ? nullptr : kPolyAdjUnavailable;
+}
+
+// ... behind the refusals: a float32 / float64 whole-cotangent job of an interpolated-phase plan, not empty, buffers and device
+// asked for.  *handled = false with no error and gx untouched — a plan without the form, a job poly_adj_admits does not take,
+// an FFT stage that declines: by name that is kPolyAdjUnavailable (above), under HIPSOXR_KERNEL_ADJOINT_AUTO the exact
+// adjoint's job (adjoint_auto.hip).
+const char *launch_adjoint_two_stage_try(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+{
+    *handled = false;
     if (const char *e = two_stage_adj_ensure(p)) return e;
     const TwoStage &ts = *p->two;
-    if (!ts.ok) return kPolyAdjUnavailable;
+    if (!ts.ok) return nullptr;
     const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
     const uint64_t cols = (uint64_t)j.n_clips * j.n_channels;
     const int64_t n_y = j.in_frames, n_x = j.out_frames;
-    if (!poly_adj_admits(n_x, n_y, cols, es, poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms))) return kPolyAdjUnavailable;
+    if (!poly_adj_admits(n_x, n_y, cols, es, poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms))) return nullptr;
     const bool inter = j.n_channels % 2 == 0 && j.in_chan_stride == 1 && j.out_chan_stride == 1;
     const TwoStageMid m = two_stage_mid(ts.up, ts.T2, ts.Ls, ts.Ms, n_x, two_stage_mid_outputs(ts.up, ts.Ls, ts.Ms, n_x, n_y, ts.fft.T), j.n_channels, inter);
     hipStream_t st = (hipStream_t)stream;
     void *mid = nullptr;
     HIP_TRY(hipMallocAsync(&mid, (size_t)cols * (size_t)m.n_mid * es, st));
-    const char *err = two_stage_adj_run(p, j, m, mid, stream);
+    const char *err = two_stage_adj_run(p, j, m, mid, stream, handled);
     (void)hipFreeAsync(mid, st); // (behind whatever was queued)
     return err;
 }
@@ -1331,6 +1369,103 @@ const char *launch_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *strea
         bool h = false;
         err = launch_ragged_short(p, sj, stream, &h);
         if (!err && !h) all = false;
+    }
+    (void)hipFreeAsync(tabs, st);
+    if (err) return err;
+    *handled = all;
+    return nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------
+// A clip table on the TRANSPOSED two-stage form (HIPSOXR_KERNEL_ADJOINT_AUTO on hipsoxr_run_device_adjoint_ragged;
+// adjoint_auto.hip has made the refusals, validated the rows and asked for buffers and device): launch_two_stage_ragged in the
+// adjoint's order.  Every decision that reads only numbers is adjoint_auto_rules.h ragged_poly_adj_plan — the partition
+// (adj_auto_class), ragged_poly_plan's columns, intermediates, packing and ranges on the swapped table, the forward's poly
+// rows, the transposed plan's FFT rows; here: a dry pass, ONE upload of every derived table, per range one allocation, the two
+// launches (down: FFT^T into the intermediate, then k_poly_adj; up: k_poly_adj over the whole window, then FFT^T) and one
+// free, in stream order; the short clips' ONE ragged launch of the exact adjoint last.
+// *handled = false with no error and gx untouched — a layout not served, a plan without the form, no clip the form admits, a
+// short clip too long for one launch, or an FFT stage that declines the FIRST range (down: before anything is queued; up:
+// behind a k_poly_adj that wrote the intermediate alone) — and the caller runs the exact ragged adjoint over the whole table.
+// A decline behind the first range is an error by name: gx is part written.
+// ---------------------------------------------------------------------------------------------
+const char *launch_adjoint_two_stage_ragged(Plan *p, const hipsoxr_job_t &j, void *stream, bool *handled)
+{
+    *handled = false;
+    if (j.in_frame_stride < 1 || j.out_frame_stride < 1 || j.n_channels > kPolyMaxCols) return nullptr;
+    if (const char *e = two_stage_adj_ensure(p)) return e;
+    const TwoStage &ts = *p->two;
+    if (!ts.ok) return nullptr;
+    const size_t es = j.elem == HIPSOXR_F32 ? 4 : 8;
+    const PolyStage s = poly_stage(ts.T2, es == 4 ? ts.P2f : ts.P2, ts.row, ts.Ls, ts.Ms);
+    const int64_t budget = switches().dbg_poly_mid_budget > 0 ? (int64_t)switches().dbg_poly_mid_budget : kPolyMidBudget;
+    const RaggedPolyAdjPlan rp = ragged_poly_adj_plan(j.clip_table, j.n_clips, j.n_channels, j.in_chan_stride, j.out_chan_stride, es, ts.up, s, ts.fft.T, budget);
+    const uint32_t n_short = rp.n_short(), n_cols = rp.n_cols();
+    if (!n_cols) return nullptr; // (every clip empty or short: the exact adjoint's one launch over the table as it stands)
+    for (uint32_t c = 0; c < n_short; ++c) // (a clip the exact adjoint may answer kAdjTooLong for: asked of the whole table, before anything is queued)
+        if (std::max(rp.short_rows[4 * (size_t)c + 1], rp.short_rows[4 * (size_t)c + 3]) > ((int64_t)1 << 30)) return nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t unit[3] = {0, 1, 0}, cy[3] = {0, j.in_frame_stride, 0}, cx[3] = {0, j.out_frame_stride, 0};
+    hipsoxr_job_t sj = j; // the short clips' job: the exact adjoint by name over the compacted sub-table
+    sj.kernel = HIPSOXR_KERNEL_ADJOINT; sj.n_clips = n_short; sj.clip_table = rp.short_rows.data();
+    PolyJob pj; // (what every range shares: columns — no clip stride, one channel; the intermediate unit-stride, the caller's sides at the caller's frame strides)
+    pj.n_channels = 1; pj.n_lo = rp.n_lo; pj.k_lo = ts.up ? 0 : -rp.fwd.pad;
+    pj.src = ts.up ? nullptr : j.out; pj.sstr = ts.up ? unit : cx;
+    pj.dst = ts.up ? const_cast<void *>(j.in) : nullptr; pj.dstr = ts.up ? cy : unit;
+    { // the dry pass: the instance and its LDS attribute, the FFT stage's tables, the exact adjoint's — nothing is queued yet
+        PolyJob dj = pj;
+        dj.rows = rp.fwd.poly_rows.data(); dj.n_clips = 1; dj.n_src = 0; dj.n_out = 0;
+        if (const char *e = run_poly_adj(j.elem, ts, dj, st, true)) return e;
+        if (const char *e = device_bank_ensure(ts.fft_t, engine_prec(j.elem))) return e;
+        if (n_short)
+            if (const char *e = adj_exact_run(p, sj, stream, nullptr, true)) return e;
+        int64_t peak = 0;
+        for (const RaggedPolyRange &g : rp.fwd.ranges) peak = std::max(peak, g.mid_elems);
+        mid_pool_retain((uint64_t)peak * es);
+    }
+    // every derived table in one host buffer and one upload: [short rows][poly rows][FFT rows] (pageable: as launch_two_stage_ragged)
+    std::vector<int64_t> host(rp.short_rows);
+    host.insert(host.end(), rp.fwd.poly_rows.begin(), rp.fwd.poly_rows.end());
+    host.insert(host.end(), rp.fft_rows.begin(), rp.fft_rows.end());
+    int64_t *tabs = nullptr;
+    if (hipMallocAsync((void **)&tabs, host.size() * sizeof(int64_t), st) != hipSuccess) return kAdjAutoFormNoMemory;
+    const int64_t *short_dev = tabs, *poly_dev = tabs + 4 * (size_t)n_short, *fft_dev = poly_dev + 4 * (size_t)n_cols;
+    const char *err = nullptr;
+    bool all = true;
+    if (hipMemcpyAsync(tabs, host.data(), host.size() * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) err = kAdjAutoFormUploadFailed;
+    for (size_t r = 0; r < rp.fwd.ranges.size() && !err && all; ++r) {
+        const RaggedPolyRange &g = rp.fwd.ranges[r];
+        const RaggedPolyAdjRange &ga = rp.ranges[r];
+        void *mid = nullptr;
+        if (hipMallocAsync(&mid, (size_t)g.mid_elems * es, st) != hipSuccess) { err = kAdjAutoFormNoMemory; break; }
+        pj.n_clips = g.count; pj.rows = poly_dev + 4 * (size_t)g.first;
+        pj.n_src = rp.n_lo + ga.src_longest; pj.n_out = g.poly_longest;
+        if (ts.up) pj.src = mid; // (the rows carry each column's offset of sample 0 in the range's intermediate)
+        else pj.dst = mid;
+        hipsoxr_job_t fj = j; // the FFT stage's transposed plan, forward, by name, over the range's columns
+        fj.kernel = HIPSOXR_KERNEL_FFT; fj.clip_counter = nullptr; fj.dither = 0; fj.dither_seed = 0;
+        fj.n_clips = g.count; fj.n_channels = 1;
+        fj.in_clip_stride = fj.out_clip_stride = 0; fj.in_chan_stride = fj.out_chan_stride = 0;
+        fj.clip_table = rp.fft_rows.data() + 4 * (size_t)g.first; fj.clip_table_dev = fft_dev + 4 * (size_t)g.first;
+        fj.in_frames = ga.fft_in_longest; fj.out_frames = ga.fft_out_longest;
+        if (ts.up) { fj.in = mid; fj.in_frame_stride = 1; fj.in_abs0 = -rp.fwd.pad; }       // gu --FFT^T 2:1--> gx
+        else { fj.out = mid; fj.out_frame_stride = 1; fj.in_abs0 = rp.fwd.pad / 2; }       // gy --FFT^T 1:2--> gv
+        bool fft_done = false;
+        if (!ts.up) {
+            err = launch_fft(ts.fft_t, fj, stream, &fft_done);
+            if (!err && !fft_done) all = false;
+        }
+        if (!err && all) err = run_poly_adj(j.elem, ts, pj, st, false);
+        if (!err && all && ts.up) {
+            err = launch_fft(ts.fft_t, fj, stream, &fft_done);
+            if (!err && !fft_done) all = false;
+        }
+        (void)hipFreeAsync(mid, st); // (behind whatever was queued)
+        if (!err && !all && r > 0) err = kAdjAutoLateDecline;
+    }
+    if (!err && all && n_short) { // the clips the form does not admit: the exact adjoint's ragged launch over the compacted sub-table
+        sj.clip_table_dev = short_dev;
+        err = adj_exact_run(p, sj, stream, short_dev, false);
     }
     (void)hipFreeAsync(tabs, st);
     if (err) return err;

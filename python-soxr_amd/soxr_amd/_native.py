@@ -64,6 +64,7 @@ KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA, KER
 KERNEL_ADJOINT = 10  # hipsoxr_run_device_adjoint / _adjoint_ragged only: the transposed operator on every constant-rate plan (interpolated-phase plans too)
 KERNEL_ADJOINT_FFT = 11  # the same two entries only: the transposed operator on the frequency-domain engine (exact-bank HQ / VHQ plans; 1e-6-class)
 KERNEL_ADJOINT_TWO_STAGE = 12  # hipsoxr_run_device_adjoint only: the transposed two-stage form (interpolated-phase HQ / VHQ plans; 1e-6-class)
+KERNEL_ADJOINT_AUTO = 13  # hipsoxr_run_device_adjoint / _adjoint_ragged only: the transpose of the job KERNEL_AUTO's forward launches — a fast adjoint where one takes the job, else the exact adjoint
 ADJOINT_INTERP_TILE = 256  # frames per workgroup of k_adj_interp (csrc/adjoint.hip kAdjIW): where its tile edges fall
 
 

@@ -13,7 +13,7 @@ from . import _native as _n
 from . import _quality_to_enum
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
                       KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT,
-                      KERNEL_ADJOINT_FFT, KERNEL_ADJOINT_TWO_STAGE)
+                      KERNEL_ADJOINT_FFT, KERNEL_ADJOINT_TWO_STAGE, KERNEL_ADJOINT_AUTO)
 
 
 class Plan:
@@ -228,9 +228,10 @@ def _adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
 
 def _adjoint_forward_kernel(kernel):
     """The forward selector an adjoint's own backward runs: the engine the adjoint ran on — KERNEL_FFT for
-    KERNEL_ADJOINT_FFT, KERNEL_AUTO (the two-stage form on the plans that selector serves) for KERNEL_ADJOINT_TWO_STAGE, the
-    exact engine for every other selector."""
-    if kernel == _n.KERNEL_ADJOINT_TWO_STAGE:
+    KERNEL_ADJOINT_FFT, KERNEL_AUTO (the two-stage form on the plans that selector serves) for KERNEL_ADJOINT_TWO_STAGE,
+    KERNEL_AUTO for KERNEL_ADJOINT_AUTO (which is defined as the transpose of that selector's forward), the exact engine
+    for every other selector."""
+    if kernel in (_n.KERNEL_ADJOINT_TWO_STAGE, _n.KERNEL_ADJOINT_AUTO):
         return _n.KERNEL_AUTO
     return _n.KERNEL_FFT if kernel == _n.KERNEL_ADJOINT_FFT else _n.KERNEL_EXACT
 
@@ -268,7 +269,16 @@ def resample_tensor_adjoint(plan, gy, in_frames, out=None, kernel=_n.KERNEL_AUTO
     VHQ, 1e-6 HQ (float64).  Its own backward is the forward under KERNEL_AUTO.  float32 / float64 (float16 / bfloat16
     widened), any clips x channels and strides.  Exact-bank and variable-rate plans, integer types and clip tables
     (`dist.resample_ragged*`) are refused by name; a plan without the form, fewer than 8192 frames either side or an FFT
-    stage that declines raises ("unavailable", naming KERNEL_ADJOINT) — it never runs the exact adjoint."""
+    stage that declines raises ("unavailable", naming KERNEL_ADJOINT) — it never runs the exact adjoint.
+
+    kernel=KERNEL_ADJOINT_AUTO: the transpose of the job `resample_tensor(plan, x)` launches under KERNEL_AUTO for the same
+    plan and shape — the selector that picks the fast adjoint where there is one and never raises "unavailable".  It
+    resolves to KERNEL_ADJOINT_FFT's launch on an exact-bank HQ / VHQ plan from 8192 cotangent elements in all (frames x
+    clips x channels, the forward's own threshold), to KERNEL_ADJOINT_TWO_STAGE's launch on an interpolated-phase plan
+    with the form and 8192 frames either side, and to KERNEL_ADJOINT's exact adjoint everywhere else (short jobs, recipes
+    below HQ, an engine that declines, HIPSOXR_NO_FFT / HIPSOXR_NO_TWO_STAGE) — with that selector's bits in each case.
+    Its own backward is the forward under KERNEL_AUTO.  Refused by name: what KERNEL_ADJOINT refuses (integer types,
+    variable-rate plans, clip tables on this entry).  KERNEL_AUTO / KERNEL_EXACT here keep their meaning and their bits."""
     if not gy.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     import torch
@@ -370,6 +380,9 @@ def resample_tensor(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     form that kernel=KERNEL_AUTO runs on such a plan, at about that form's cost — forward and gradient then transpose each
     other to rounding, not only in the 1e-6 class.  Jobs the form does not admit (fewer than 8192 frames either side)
     raise in backward ("unavailable"); no fast gradient is ever chosen by AUTO.
+    grad_kernel=KERNEL_ADJOINT_AUTO: the backward is the transpose of whatever kernel=KERNEL_AUTO launches for the plan and
+    shape — KERNEL_ADJOINT_FFT's launch, KERNEL_ADJOINT_TWO_STAGE's, or the exact adjoint where no fast form takes the
+    job (see `resample_tensor_adjoint`); it never raises "unavailable", so one value serves every plan and length.
     """
     if x.is_cuda and x.requires_grad:
         import torch

@@ -366,7 +366,14 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
     table read as a forward table of the plan's transposed plan; each clip is then within that engine's 1e-6 class of the
     clip alone, not bit-equal to it, and the backward is the ragged forward with KERNEL_FFT.
     kernel=KERNEL_ADJOINT_TWO_STAGE is passed through and refused by the C entry by name: the transposed two-stage form
-    does not serve clip tables yet (clip by clip: `device.resample_tensor_adjoint`)."""
+    does not serve clip tables yet (clip by clip: `device.resample_tensor_adjoint`).
+    kernel=KERNEL_ADJOINT_AUTO: the transpose of what `resample_ragged(plan, xs)` launches under KERNEL_AUTO, never
+    "unavailable".  Exact-bank plan: KERNEL_ADJOINT_FFT's one launch when the cotangents hold 8192 elements in all on an
+    HQ / VHQ plan, else KERNEL_ADJOINT's.  Interpolated-phase plan: per clip — a clip with 8192 frames either side runs on
+    the transposed two-stage form (one ragged `k_poly_adj` launch and one FFT-stage launch per range of clips, whatever
+    their number: within the form's 1e-6 / 2e-9 class of the clip alone), every other clip in ONE ragged launch of the
+    exact adjoint (the bits of KERNEL_ADJOINT on the clip alone; a clip without cotangent gets zeros).  Its backward is
+    the ragged forward under KERNEL_AUTO."""
     import torch
     monos = [g.ndim == 1 for g in gys]
     if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
@@ -391,7 +398,10 @@ def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AU
     (kernel=KERNEL_EXACT: forward and gradient agree to rounding), and what the adjoint does not serve — an
     interpolated-phase plan without grad_kernel=KERNEL_ADJOINT — raises when the forward is called.
     grad_kernel=KERNEL_ADJOINT_FFT: the backward's one launch runs on the frequency-domain engine (`resample_ragged_adjoint`).
-    grad_kernel=KERNEL_ADJOINT_TWO_STAGE: refused by name when the forward is called (no clip tables on that selector yet)."""
+    grad_kernel=KERNEL_ADJOINT_TWO_STAGE: refused by name when the forward is called (no clip tables on that selector yet).
+    grad_kernel=KERNEL_ADJOINT_AUTO: the backward is the transpose of the launches this forward makes under KERNEL_AUTO — on an
+    interpolated-phase plan the transposed two-stage form over the clips it admits and the exact adjoint over the rest, a
+    constant number of launches (`resample_ragged_adjoint`); one value for every plan and every mix of lengths."""
     import torch
     if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
         why = _ragged_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
