@@ -8,7 +8,11 @@ read the other way round,
     =>   gx[n0_k + j] += bank[p_k][j] gy[k],
 
 accumulated with np.add.at in float64, together with its magnitude twin |A|^T |gy| (what error bounds are scaled by).
-tests/test_adjoint_ref.py pins it to the dense matrix."""
+tests/test_adjoint_ref.py pins it to the dense matrix.
+
+Interpolated-phase plans have no such closed form here, on purpose: `column` is ONE column of the dense matrix, the oracle's
+forward on one unit impulse, at any length (about 10 ms at 20 000 frames) — the adjoint formula is not restated for them.
+`probes` says which columns a long job is looked at: the ends, the seams of the kernel's tiling, and random ones."""
 import numpy as np
 
 
@@ -37,3 +41,48 @@ def dense(oracle, pl, bank, n_x):
     """A [n_y, n_x] float64: the oracle's forward ("ref" mode, on `bank`) applied to the n_x unit impulses."""
     eye = np.eye(n_x)
     return np.stack([oracle.resample_channel(pl, eye[a], "ref", bank=bank) for a in range(n_x)], axis=1)
+
+
+def column(oracle, pl, bank, a, n_x, mode):
+    """Column a of A for a job of n_x frames, [out_len(n_x)] float64: the oracle's forward on the unit impulse e_a.
+    pl: anything with L, M, T and phases (an oracle plan; a namespace will do).  mode "ref": float64 on `bank` as given;
+    "port_f64" / "port_f32": the engine's own order and width — on a unit impulse every product but one is an exact zero, so
+    with bank=Plan.bank() the column holds the very coefficients the engine multiplies by (tests/test_gpu_adjoint_interp.py
+    argues this for its dense matrix), the float32 ones widened."""
+    assert 0 <= a < n_x
+    e = np.zeros(n_x, np.float32 if mode == "port_f32" else np.float64)
+    e[a] = 1.0
+    n_out = int(oracle.lib().oracle_out_len(int(n_x), int(pl.L), int(pl.M)))
+    return oracle.resample_channel(pl, e, mode, n_out=n_out, bank=bank).astype(np.float64)
+
+
+def probes(n_x, seams, rng, count):
+    """Sorted frame positions of a job of n_x frames, at most `count` of them (at least the ends): 0, n_x - 1, every seam s
+    (a tile edge of the kernel: the caller says where) with the frame before it, s - 1 — where the seams would take more
+    than two thirds of the positions, a random choice of them — and random positions from `rng` (a numpy Generator) for the
+    rest."""
+    assert n_x >= 1
+    seams = sorted(set(int(s) for s in seams if 0 < int(s) < n_x))
+    pairs = max(count - 2, 0) // 3
+    if len(seams) > pairs:
+        seams = sorted(int(s) for s in rng.choice(seams, size=pairs, replace=False)) if pairs else []
+    want = [0, n_x - 1]
+    for s in seams:
+        want += [s - 1, s]
+    out = []
+    for p in want:
+        if 0 <= p < n_x and p not in out and len(out) < max(count, 2):
+            out.append(p)
+    free = n_x - len(out)
+    extra = min(max(count - len(out), 0), free)
+    if extra:
+        if n_x <= 4 * count:
+            rest = [p for p in range(n_x) if p not in out]
+            out += [int(p) for p in rng.choice(rest, size=extra, replace=False)]
+        else:
+            while extra:
+                p = int(rng.integers(0, n_x))
+                if p not in out:
+                    out.append(p)
+                    extra -= 1
+    return sorted(out)
