@@ -388,11 +388,32 @@ HIPSOXR_API uint64_t hipsoxr_plan_vr_out_len(const hipsoxr_plan_t *, uint64_t in
  * a ratio outside (2^-20, 2^20) or above the plan's in_rate / out_rate (by more than the factor 1 + 1e-12 that
  * hipsoxr_stream_set_io_ratio allows, in its words), a negative offset or count, a row above the job's in_frames /
  * out_frames, n_out[c] above hipsoxr_plan_vr_out_len, a clip of more than 2^30 outputs, in_abs0 / out_k0 != 0, HIPSOXR_F16 /
- * HIPSOXR_BF16, any other selector.  Not served: a ratio change inside a clip (streams have slews), gradients, the
- * frequency-domain engine.  No clips, no channels or out_frames == 0: success, nothing launched.  Asynchronous on
- * `hip_stream`. */
+ * HIPSOXR_BF16, any other selector.  Not served: a ratio change inside a clip (streams have slews), the
+ * frequency-domain engine.  Gradients: hipsoxr_run_device_vr_ragged_adjoint, below.  No clips, no channels or
+ * out_frames == 0: success, nothing launched.  Asynchronous on `hip_stream`. */
 HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_vr_ragged(hipsoxr_plan_t *, const hipsoxr_job_t *job,
                                                          const double *io_ratios /* host, n_clips */, void *hip_stream);
+/* The gradient of that launch — gx[c] = A_c^T gy[c] for every clip of a clip table, ONE launch whatever the number of clips:
+ * A_c is the forward hipsoxr_run_device_vr_ragged computes for n_x[c] input frames at io_ratios[c], truncated to its first
+ * n_y[c] outputs.  The job is read in the adjoint's direction, as hipsoxr_run_device_adjoint_ragged reads it: `in` is gy,
+ * `out` is gx, clip_table is REQUIRED — n_clips host rows { gy offset, n_y, gx offset, n_x } in elements from `in` / `out`
+ * (the clip strides are ignored), in_frames / out_frames the LARGEST per-clip n_y / n_x, clip_table_dev as on ragged jobs.
+ * io_ratios is a HOST array of n_clips doubles, read before the call returns and turned into steps as on the forward.
+ * The coefficient of gy[k] in gx[a] is the very value the forward multiplies x[a] by for output k (the plan's interpolation
+ * table, the same integer position arithmetic, the same fma nesting); every gx[a] is one fma chain over ascending k from +0
+ * in the element's width, at most ceil(taps / io ratio) + 1 terms.  Gather form, no atomics: bitwise reproducible, and each
+ * clip has the bits of the same clip run alone.  Every element of every clip's gx[0, n_x[c]) is written (+0 where no output
+ * reads the frame, all of a clip with n_y[c] == 0), nothing outside it — not the elements between packed clips either.  A
+ * non-finite gy[k] reaches the frames of its true support, q_k - (taps/2 - 1) .. q_k + taps/2 with q_k = (k S) >> 64, and
+ * nothing else.  HIPSOXR_F32 / HIPSOXR_F64.  Selectors: HIPSOXR_KERNEL_AUTO and HIPSOXR_KERNEL_ADJOINT, the same launch and
+ * the same bits.
+ * Refused by name, before anything is launched: a plan not made by hipsoxr_plan_create_vr, a NULL clip_table or io_ratios, a
+ * ratio the forward entry refuses (in its words), a negative offset or count, a row above the job's in_frames / out_frames,
+ * n_y[c] above hipsoxr_plan_vr_out_len(plan, n_x[c], io_ratios[c]), a clip of more than 2^30 cotangent samples, in_abs0 /
+ * out_k0 != 0, integer element types, HIPSOXR_F16 / HIPSOXR_BF16, any other selector (HIPSOXR_KERNEL_ADJOINT_AUTO, _FFT and
+ * _TWO_STAGE included).  No clips, no channels or out_frames == 0: success, nothing launched.  Asynchronous on `hip_stream`. */
+HIPSOXR_API hipsoxr_error_t hipsoxr_run_device_vr_ragged_adjoint(hipsoxr_plan_t *, const hipsoxr_job_t *job,
+                                                                 const double *io_ratios /* host, n_clips */, void *hip_stream);
 
 /* ---- stream: the soxr_t counterpart (host pointers, state carried across calls) ----------- */
 HIPSOXR_API hipsoxr_error_t hipsoxr_stream_create(double in_rate, double out_rate,

@@ -86,6 +86,7 @@
 #include "device.h"
 #include "job_rules.h"
 #include "poly_adj_rules.h" // kPolyAdjRaggedRefusal
+#include "vr_adjoint_rules.h" // vr_adj_k_range, vr_adj_grid
 
 namespace hipsoxr {
 
@@ -282,8 +283,15 @@ struct AdjInterpArgs {
     int64_t n_y, n_x;    // RAGGED: the largest per-clip values
 };
 struct AdjInterpRaggedArgs : AdjInterpArgs { const int64_t *rows; }; // as AdjRaggedArgs::rows
-template <bool RAGGED> struct AdjInterpArgsOf { typedef AdjInterpArgs type; };
-template <> struct AdjInterpArgsOf<true> { typedef AdjInterpRaggedArgs type; };
+// VR (hipsoxr_run_device_vr_ragged_adjoint): a second table behind the arguments, a clip's clock — its Q64.64 step {hi, lo};
+// T0 = 0, D = 0 — as kernels_interp.h's InterpArgsR::clock; L and M are not read
+struct AdjInterpVrArgs : AdjInterpRaggedArgs {
+    const uint64_t *clock; // [n_clips][2]
+    int32_t lgP;           // P = 1 << lgP
+};
+template <bool RAGGED, bool VR = false> struct AdjInterpArgsOf { typedef AdjInterpArgs type; };
+template <> struct AdjInterpArgsOf<true, false> { typedef AdjInterpRaggedArgs type; };
+template <> struct AdjInterpArgsOf<true, true> { typedef AdjInterpVrArgs type; };
 
 template <typename Real> struct AdjVec4;
 template <> struct AdjVec4<float> { typedef float4 type; };
@@ -296,27 +304,41 @@ template <typename Real> struct AdjRec { int32_t dq, row; Real xx, g; };
 // RAGGED: the tile's frame and k ranges and the walks depend on the clip's n_x and n_y, so they are found per column; a
 // tile at or behind its clip's n_x skips the column (workgroup-uniform: no barrier is met by some threads only), and a clip
 // with n_y == 0 has an empty k range — no chunk, zeros written to all its frames.
-template <typename Real, bool UNION, bool RAGGED>
-__global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<RAGGED>::type a)
+// VR (&& RAGGED): every clip at its own constant step S, read from the clock table like its row.  The forward's VR branch
+// with T0 = 0, D = 0 to the letter: tt = k S in 128 bits, q_k = tt >> 64, interval and residual are bit fields of the
+// fraction — a multiplication and two shifts per k where the constant-rate branch divides.  The k range of a frame is
+// vr_adjoint_rules.h's vr_adj_k_range (no 128-bit division), its lower end cut at n_y so that a tile behind the cotangent's
+// reach has the empty range [n_y, n_y - 1].  wl / wh / dq stay int32: q_k - a0 lies within T of the tile, and a tile's k
+// range holds at most (kAdjIW + T) / s + 1 < 2^31 samples at the smallest admitted io ratio s > 2^-20 (T <= ~740).
+template <typename Real, bool UNION, bool RAGGED, bool VR = false>
+__global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<RAGGED, VR>::type a)
 {
+    static_assert(!VR || RAGGED, "the variable-rate form reads a clip table");
     typedef typename AdjVec4<Real>::type V4;
     constexpr int SH = sizeof(Real) == 4 ? 24 : 32;
     __shared__ AdjRec<Real> rec[kAdjIC];
     const int32_t T = a.T, H = T / 2;
     const int tid = (int)threadIdx.x;
     const int64_t a0 = (int64_t)blockIdx.x * kAdjIW, fr = a0 + tid;
-    auto k_lo = [&](int64_t f) { const int64_t k = ceil_div((f - H) * a.L, a.M); return k > 0 ? k : (int64_t)0; };
-    auto k_hi = [&](int64_t f, int64_t n_y) { const int64_t k = ceil_div((f + H) * a.L, a.M); return (k < n_y ? k : n_y) - 1; };
+    [[maybe_unused]] unsigned __int128 S = 0; // VR: the column's clip's step
+    auto k_lo = [&](int64_t f, [[maybe_unused]] int64_t n_y) {
+        if constexpr (VR) { const int64_t k = vr_adj_k_range(f, H, S, n_y).lo; return k < n_y ? k : n_y; }
+        else { const int64_t k = ceil_div((f - H) * a.L, a.M); return k > 0 ? k : (int64_t)0; }
+    };
+    auto k_hi = [&](int64_t f, int64_t n_y) {
+        if constexpr (VR) return vr_adj_k_range(f, H, S, n_y).hi;
+        else { const int64_t k = ceil_div((f + H) * a.L, a.M); return (k < n_y ? k : n_y) - 1; }
+    };
     // the tile's share of a clip of n_x frames and n_y cotangent samples (equal lengths: found once, here; RAGGED: per column)
     int64_t k_first = 0, k_end = 0;
     int32_t wl = 0, wh = -1;
     auto geo = [&](int64_t n_y, int64_t n_x) {
         const int64_t a_end = a0 + kAdjIW < n_x ? a0 + kAdjIW : n_x; // the tile's frames: [a0, a_end), never empty
-        k_first = k_lo(a0); k_end = k_hi(a_end - 1, n_y) + 1;        // the tile reads gy[k_first, k_end)
+        k_first = k_lo(a0, n_y); k_end = k_hi(a_end - 1, n_y) + 1;   // the tile reads gy[k_first, k_end)
         // this wave's (UNION) or this lane's walk, relative to k_first: [wl, wh], empty behind the signal's end
         const int64_t f0 = UNION ? a0 + (tid & ~63) : fr, f1 = UNION ? (f0 + 63 < a_end ? f0 + 63 : a_end - 1) : fr;
         int32_t l = 0, h = -1;
-        if (f0 < a_end) { l = (int32_t)(k_lo(f0) - k_first); h = (int32_t)(k_hi(f1, n_y) - k_first); }
+        if (f0 < a_end) { l = (int32_t)(k_lo(f0, n_y) - k_first); h = (int32_t)(k_hi(f1, n_y) - k_first); }
         if (UNION) { l = __builtin_amdgcn_readfirstlane(l); h = __builtin_amdgcn_readfirstlane(h); }
         wl = l; wh = h;
     };
@@ -331,6 +353,7 @@ __global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<
         const int64_t n_x = RAGGED ? row[3] : a.n_x;
         if (RAGGED) {
             if (a0 >= n_x) continue; // nothing of this clip in this tile
+            if constexpr (VR) S = ((unsigned __int128)a.clock[2 * clip] << 64) | a.clock[2 * clip + 1];
             geo(row[1], n_x);
         }
         const Real *g = (const Real *)a.gy + (RAGGED ? row[0] : clip * a.ics) + ch * a.ichs;
@@ -339,10 +362,22 @@ __global__ void __launch_bounds__(kAdjIW) k_adj_interp(typename AdjInterpArgsOf<
             __syncthreads(); // the chunk before is still being read
             const int64_t k = kc + tid;
             if (k < k_end) { // k_interp's own arithmetic (kernels_interp.h, the constant-rate branch with p0 = d0 = 0)
-                const int64_t t = k * a.M, q = t / a.L;
-                const uint64_t r = (uint64_t)(t - q * a.L);
-                const uint64_t tp = r * (uint64_t)a.P, rem = tp % (uint64_t)a.L, iv = tp / (uint64_t)a.L;
-                const uint64_t xq = (rem << SH) / (uint64_t)a.L;
+                int64_t q;
+                uint64_t iv, xq;
+                if constexpr (VR) { // ... its VR branch with T0 = 0, D = 0
+                    const unsigned __int128 tt = (unsigned __int128)(uint64_t)k * S;
+                    const uint64_t frac = (uint64_t)tt;
+                    q = (int64_t)(uint64_t)(tt >> 64);
+                    iv = a.lgP ? frac >> (64 - a.lgP) : 0;
+                    xq = (frac << a.lgP) >> (64 - SH);
+                } else {
+                    const int64_t t = k * a.M;
+                    q = t / a.L;
+                    const uint64_t r = (uint64_t)(t - q * a.L);
+                    const uint64_t tp = r * (uint64_t)a.P, rem = tp % (uint64_t)a.L;
+                    iv = tp / (uint64_t)a.L;
+                    xq = (rem << SH) / (uint64_t)a.L;
+                }
                 AdjRec<Real> rc;
                 rc.dq = (int32_t)(q - a0);
                 rc.row = (int32_t)iv * T;
@@ -468,15 +503,16 @@ static void adj_launch_log(const char *kernel, size_t width, const AdjBank &b, i
     fputc('\n', f);
     fclose(f);
 }
-// ... and k_adj_interp's line
+// ... and k_adj_interp's line (a variable-rate launch puts " vr=1" in front of its ragged=<n_clips>)
 template <typename Real>
-static void adj_interp_log(const Plan &p, bool per_lane, dim3 grid, const AdjInterpRaggedArgs &a, uint32_t n_clips)
+static void adj_interp_log(const Plan &p, bool per_lane, dim3 grid, const AdjInterpRaggedArgs &a, uint32_t n_clips, bool vr = false)
 {
     FILE *f = fopen(switches().dbg_launch_log, "a");
     if (!f) return;
     fprintf(f, "kernel=adj_interp width=%zu L=%lld M=%lld T=%d P=%d tile=%d chunk=%d lds=%zu walk=%s grid=%ux%ux%u block=%u", sizeof(Real),
             (long long)p.L, (long long)p.M, p.T, p.phases, kAdjIW, kAdjIC, sizeof(AdjRec<Real>) * kAdjIC, per_lane ? "lane" : "union",
             grid.x, grid.y, grid.z, (unsigned)kAdjIW);
+    if (vr) fputs(" vr=1", f);
     if (a.rows) fprintf(f, " ragged=%u", n_clips);
     fputc('\n', f);
     fclose(f);
@@ -496,10 +532,11 @@ static void adj_run_gather(const AdjRaggedArgs &a, dim3 grid, hipStream_t st)
 {
     hipLaunchKernelGGL((k_adj_gather<Real, RAGGED>), grid, dim3(kAdjGatherLanes), 0, st, static_cast<const typename AdjArgsOf<RAGGED>::type &>(a));
 }
-template <typename Real, bool UNION, bool RAGGED>
-static void adj_run_interp(const AdjInterpRaggedArgs &a, dim3 grid, hipStream_t st)
+// (Args: AdjInterpRaggedArgs, or — the variable-rate form — AdjInterpVrArgs)
+template <typename Real, bool UNION, bool RAGGED, bool VR = false, typename Args>
+static void adj_run_interp(const Args &a, dim3 grid, hipStream_t st)
 {
-    hipLaunchKernelGGL((k_adj_interp<Real, UNION, RAGGED>), grid, dim3(kAdjIW), 0, st, static_cast<const typename AdjInterpArgsOf<RAGGED>::type &>(a));
+    hipLaunchKernelGGL((k_adj_interp<Real, UNION, RAGGED, VR>), grid, dim3(kAdjIW), 0, st, static_cast<const typename AdjInterpArgsOf<RAGGED, VR>::type &>(a));
 }
 
 // The argument block of the exact-bank kernels, all but what the tile form decides.  rows: the device copy of a ragged job's
@@ -576,6 +613,30 @@ static const char *adj_interp_launch(const Plan &p, const hipsoxr_job_t &j, hipS
     else per_lane ? adj_run_interp<Real, false, false>(a, grid, st) : adj_run_interp<Real, true, false>(a, grid, st);
     HIP_TRY(hipGetLastError());
     if (switches().dbg_launch_log) adj_interp_log<Real>(p, per_lane, grid, a, j.n_clips);
+    return nullptr;
+}
+
+// k_adj_interp<.., VR> over a whole clip table: rows and clock are the device copies of the clip table and of the clips' steps.
+template <typename Real>
+static const char *adj_interp_vr_launch(const Plan &p, const hipsoxr_job_t &j, hipStream_t st, const int64_t *rows, const uint64_t *clock)
+{
+    AdjInterpVrArgs a{};
+    a.gy = j.in; a.gx = j.out; a.tab = p.dev[sizeof(Real) == 4 ? 0 : 1].interp_tab;
+    a.L = p.L; a.M = p.M; a.T = p.T; a.P = p.phases;
+    while ((1 << a.lgP) < a.P) ++a.lgP;
+    if ((1 << a.lgP) != a.P) return "variable-rate needs a power-of-two phase count";
+    a.n_cols = (uint64_t)j.n_clips * j.n_channels; a.n_channels = j.n_channels;
+    a.ifs = j.in_frame_stride; a.ichs = j.in_chan_stride; // (a clip's place is its row's: the clip strides are not read)
+    a.ofs = j.out_frame_stride; a.ochs = j.out_chan_stride;
+    a.n_y = j.in_frames; a.n_x = j.out_frames;
+    a.rows = rows; a.clock = clock;
+    const AdjGrid g = vr_adj_grid(j.out_frames, a.n_cols, kAdjIW);
+    if (!g.ok) return kAdjTooLong;
+    const dim3 grid(g.gx, g.gy);
+    const bool per_lane = switches().adj_interp_per_lane;
+    per_lane ? adj_run_interp<Real, false, true, true>(a, grid, st) : adj_run_interp<Real, true, true, true>(a, grid, st);
+    HIP_TRY(hipGetLastError());
+    if (switches().dbg_launch_log) adj_interp_log<Real>(p, per_lane, grid, a, j.n_clips, true);
     return nullptr;
 }
 
@@ -676,6 +737,29 @@ const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &j, void *stream)
     const char *e = adj_run(*p, b, j, st, rows);
     if (tmp) (void)hipFreeAsync(tmp, st);
     return e;
+}
+
+// hipsoxr_run_device_vr_ragged_adjoint (the entry, engine.cpp, has refused by name and validated the table): clip c's
+// gx = A_c^T gy at its own step clock[c] = {hi, lo} (host memory), all clips in ONE launch of k_adj_interp<.., VR>.  The clock
+// table and — where the caller gave no device copy — the clip table are uploaded in stream order and released behind the
+// launch, as launch_vr_ragged and launch_adjoint_ragged do.
+const char *launch_adjoint_vr_ragged(Plan *p, const hipsoxr_job_t &j, const uint64_t *clock, void *stream)
+{
+    const hipStream_t st = (hipStream_t)stream;
+    if (const char *e = device_bank_ensure(p, engine_prec(j.elem))) return e;
+    const int64_t *rows = nullptr;
+    void *tmp = nullptr, *clk = nullptr;
+    static constexpr ClipTableTexts texts = {"variable-rate ragged adjoint: no device memory for the clip table",
+                                             "variable-rate ragged adjoint: clip table upload failed"};
+    if (const char *e = clip_table_device(j, stream, &rows, &tmp, texts)) return e;
+    const size_t bytes = (size_t)j.n_clips * kVrClockRow * sizeof(uint64_t);
+    const char *err = nullptr;
+    if (hipMallocAsync(&clk, bytes, st) != hipSuccess) { clk = nullptr; err = "variable-rate ragged adjoint: no device memory for the clock table"; }
+    else if (hipMemcpyAsync(clk, clock, bytes, hipMemcpyHostToDevice, st) != hipSuccess) err = "variable-rate ragged adjoint: clock table upload failed";
+    if (!err) err = with_real(j.elem, [&](auto r) { return adj_interp_vr_launch<decltype(r)>(*p, j, st, rows, (const uint64_t *)clk); });
+    if (clk) (void)hipFreeAsync(clk, st);
+    if (tmp) (void)hipFreeAsync(tmp, st);
+    return err;
 }
 
 } // namespace hipsoxr

@@ -208,6 +208,9 @@ const char *launch_vr_ragged(Plan *p, const hipsoxr_job_t &job, const uint64_t *
 // forward's own table, device_bank_ensure).  adjoint_release drops the plan's transposed tables (rebuilt on next use).
 const char *launch_adjoint(Plan *p, const hipsoxr_job_t &job, void *stream);
 const char *launch_adjoint_ragged(Plan *p, const hipsoxr_job_t &job, void *stream); // hipsoxr_run_device_adjoint_ragged: job.clip_table, one launch
+// ... of a ragged variable-rate launch (hipsoxr_run_device_vr_ragged_adjoint): job.clip_table = rows {gy offset, n_y, gx offset,
+// n_x} validated by the entry, clock = the n_clips steps {hi, lo} of its io ratios (host memory) — one launch of k_adj_interp<.., VR>
+const char *launch_adjoint_vr_ragged(Plan *p, const hipsoxr_job_t &job, const uint64_t *clock, void *stream);
 void adjoint_release(const Plan *p);
 // ... on the frequency-domain engine (adjoint_fft.hip; HIPSOXR_KERNEL_ADJOINT_FFT, which the two entries above hand over
 // first thing): the forward float job of the plan's transposed plan through launch_fft, or an error by name — never the

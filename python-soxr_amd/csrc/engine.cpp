@@ -23,6 +23,7 @@
 #include "adjoint_fft_rules.h" // kAdjFftForwardRefusal
 #include "device.h"
 #include "poly_adj_rules.h" // kPolyAdjForwardRefusal
+#include "vr_adjoint_rules.h"
 #include "vr_ragged_rules.h"
 
 using namespace hipsoxr;
@@ -517,6 +518,41 @@ hipsoxr_error_t hipsoxr_run_device_vr_ragged(hipsoxr_plan_t *h, const hipsoxr_jo
     if (!j.out || (j.in_frames > 0 && !j.in)) return "null buffer";
     if (device_count() <= 0) return kNoDevice;
     return launch_vr_ragged(&h->p, j, clock.data(), hip_stream);
+}
+
+// The gradient of that launch: gx[c] = A_c^T gy[c], A_c the forward above on n_x[c] input frames at io_ratios[c], truncated
+// to its first n_y[c] outputs.  Refused here as there, by name and before the device is asked for; the launch is
+// adjoint.hip's (launch_adjoint_vr_ragged).
+hipsoxr_error_t hipsoxr_run_device_vr_ragged_adjoint(hipsoxr_plan_t *h, const hipsoxr_job_t *job, const double *io_ratios, void *hip_stream)
+{
+    if (!h || !job) return "null argument";
+    const Plan &p = h->p;
+    const hipsoxr_job_t &j = *job;
+    if (j.elem == HIPSOXR_F16 || j.elem == HIPSOXR_BF16)
+        return "variable-rate ragged adjoint: float16 / bfloat16 clip tables are not served (float32 or float64)";
+    if (j.elem < 0 || j.elem > HIPSOXR_BF16) return "invalid element type";
+    if (j.elem != HIPSOXR_F32 && j.elem != HIPSOXR_F64)
+        return "variable-rate ragged adjoint: float32 or float64 elements only (integer types have no gradient)";
+    if (j.kernel != HIPSOXR_KERNEL_AUTO && j.kernel != HIPSOXR_KERNEL_ADJOINT)
+        return "variable-rate ragged adjoint: served by the exact adjoint alone (HIPSOXR_KERNEL_AUTO or HIPSOXR_KERNEL_ADJOINT)";
+    if (!p.vr) return "variable-rate ragged adjoint: the plan is not a variable-rate plan (hipsoxr_plan_create_vr makes one, for the largest io ratio)";
+    if (!j.clip_table) return "variable-rate ragged adjoint: the entry needs a clip_table (rows { gy offset, n_y, gx offset, n_x })";
+    if (!io_ratios) return "variable-rate ragged adjoint: the entry needs io_ratios (one io ratio per clip)";
+    if (j.in_abs0 != 0 || j.out_k0 != 0) return "variable-rate ragged adjoint: whole signals only (in_abs0 == 0, out_k0 == 0)";
+    if (j.in_frames < 0 || j.out_frames < 0) return "variable-rate ragged adjoint: invalid job extent";
+    const double max_io = p.in_rate / p.out_rate;
+    std::vector<uint64_t> clock((size_t)j.n_clips * kVrClockRow);
+    for (uint32_t c = 0; c < j.n_clips; ++c) {
+        if (const char *e = vr_ragged_ratio_refusal(io_ratios[c], max_io)) return e; // (the forward's rule, in its own words)
+        const u128 step = vr_ragged_step(io_ratios[c]);
+        if (const char *e = vr_adj_row_refusal(j.clip_table + kRaggedRow * (size_t)c, j.in_frames, j.out_frames, step)) return e;
+        clock[kVrClockRow * (size_t)c] = (uint64_t)(step >> 64);
+        clock[kVrClockRow * (size_t)c + 1] = (uint64_t)step;
+    }
+    if (j.n_clips == 0 || j.n_channels == 0 || j.out_frames == 0) return nullptr; // nothing to write
+    if (!j.out || (j.in_frames > 0 && !j.in)) return "variable-rate ragged adjoint: null buffer";
+    if (device_count() <= 0) return kNoDevice;
+    return launch_adjoint_vr_ragged(&h->p, j, clock.data(), hip_stream);
 }
 
 } // extern "C"

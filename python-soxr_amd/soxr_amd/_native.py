@@ -107,6 +107,7 @@ SIGNATURES = {
     "hipsoxr_run_device_adjoint_ragged": (_err, [C.c_void_p, _P(Job), C.c_void_p]),
     "hipsoxr_plan_vr_out_len": (C.c_uint64, [C.c_void_p, C.c_uint64, C.c_double]),
     "hipsoxr_run_device_vr_ragged": (_err, [C.c_void_p, _P(Job), C.c_void_p, C.c_void_p]),
+    "hipsoxr_run_device_vr_ragged_adjoint": (_err, [C.c_void_p, _P(Job), C.c_void_p, C.c_void_p]),
     "hipsoxr_stream_create": (_err, [C.c_double, C.c_double, C.c_uint, C.c_int, C.c_ulong, C.c_ulong,
                                      _P(C.c_void_p)]),
     "hipsoxr_stream_create_with_plan": (_err, [C.c_void_p, C.c_uint, C.c_int, C.c_ulong, _P(C.c_void_p)]),

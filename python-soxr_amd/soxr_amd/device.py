@@ -143,6 +143,31 @@ class Plan:
         j.dither, j.dither_seed = int(bool(dither)), int(dither_seed) & 0xFFFFFFFF
         _n.check(_n.lib.hipsoxr_run_device_vr_ragged(self._h, _C.byref(j), r.ctypes.data, stream))
 
+    def run_vr_ragged_adjoint(self, gy_ptr, gx_ptr, elem, n_channels, table, io_ratios, gy_strides, gx_strides, stream=None,
+                              kernel=_n.KERNEL_AUTO, table_dev=None):
+        """Raw launch of the transposed operator of `run_vr_ragged` (hipsoxr_run_device_vr_ragged_adjoint) on a `vr` plan:
+        ONE launch for all clips, gx[c] = A_c^T gy[c] with A_c the forward of n_x[c] input frames at io_ratios[c].  table:
+        int64 host array [n_clips, 4] of rows (gy offset, n_y, gx offset, n_x), offsets in elements from gy_ptr / gx_ptr,
+        n_y <= vr_out_len(n_x, io_ratios[c]) per clip; table_dev: a device copy of it (pointer), or None = uploaded in
+        stream order.  strides = (frame, channel) in elements.  float32 / float64; KERNEL_AUTO and KERNEL_ADJOINT run
+        the same launch."""
+        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
+        r = np.ascontiguousarray(io_ratios, dtype=np.float64).reshape(-1)
+        n = t.shape[0]
+        if r.shape[0] != n:
+            raise ValueError("one io ratio per clip")
+        if n == 0:  # (an empty array has no address worth passing: the entry refuses NULL tables)
+            t, r = np.zeros((1, 4), np.int64), np.ones(1, np.float64)
+        j = _n.Job()
+        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
+        j.n_clips, j.n_channels = n, n_channels
+        j.in_frame_stride, j.in_chan_stride = gy_strides
+        j.out_frame_stride, j.out_chan_stride = gx_strides
+        j.in_abs0, j.out_k0 = 0, 0
+        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
+        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
+        _n.check(_n.lib.hipsoxr_run_device_vr_ragged_adjoint(self._h, _C.byref(j), r.ctypes.data, stream))
+
 
 class PreparedJob:
     """A device job whose descriptor is built once: `launch()` is a single C call

@@ -19,7 +19,9 @@ the GIL released (src/soxr_ext.cpp:222,297; tests/gil_bench.py:22-56).  The MI35
   (`hipsoxr_run_device_adjoint_ragged`) — what its backward runs.
 
 * a rate per clip (speed perturbation): `resample_varispeed(plan, clips, io_ratios)` / `RaggedJob(..., io_ratios=...)` on a
-  variable-rate plan — every clip at its own ratio in ONE launch (`hipsoxr_run_device_vr_ragged`).
+  variable-rate plan — every clip at its own ratio in ONE launch (`hipsoxr_run_device_vr_ragged`).  With
+  `grad_kernel=KERNEL_ADJOINT` it is differentiable: `resample_varispeed_adjoint(plan, gys, in_frames, io_ratios)` is the
+  transposed operator over all clips in ONE launch (`hipsoxr_run_device_vr_ragged_adjoint`) — what its backward runs.
 
 bench.py and the multi-process tests import these from here; nothing below touches `oracle/`.
 """
@@ -225,7 +227,8 @@ class RaggedJob:
         return outs
 
 
-def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=None, dither_seed=0, clip_counter=None):
+def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=None, dither_seed=0, clip_counter=None,
+                       grad_kernel=None):
     """Resample every clip of a batch at a rate of its own, all clips in ONE launch; returns the list of per-clip outputs
     (views of one packed buffer), clip c with `plan.vr_out_len(len(clips[c]), io_ratios[c])` frames.
 
@@ -242,15 +245,150 @@ def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=Non
     `TensorStream(plan.in_rate, plan.out_rate, ..., vr=True)` returns after `set_io_ratio(io_ratios[c], 1.0)` when it is fed
     the whole clip with last=True: the exact engine under every admitted selector (KERNEL_AUTO, KERNEL_EXACT,
     KERNEL_GATHER).  dither / dither_seed / clip_counter as for `RaggedJob`.  On the current torch stream, asynchronously.
-    No gradient is served: a clip with requires_grad raises."""
+
+    Gradients are served by name.  grad_kernel=None (the default): a clip with requires_grad raises.
+    grad_kernel=KERNEL_ADJOINT: float32 / float64 clips; the forward is the same one launch with the same bits, and the
+    result carries a grad_fn whose backward is ONE launch of the transposed operator (`resample_varispeed_adjoint`),
+    whatever the number of clips; the double backward is this forward again on the exact engine, so gradients flow to any
+    order.  A clip that does not require grad gets none.  Integer clips, and dither / dither_seed / clip_counter (which
+    are integer-only), are refused together with grad_kernel when the forward is called; so is every selector the C entry
+    refuses (KERNEL_ADJOINT_AUTO, _FFT, _TWO_STAGE: no fast form of this gradient exists)."""
     import torch
-    if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
+    if grad_kernel is not None:
+        if dither is not None or dither_seed != 0 or clip_counter is not None:
+            raise ValueError("resample_varispeed: dither, dither_seed and clip_counter belong to integer clips, which have no "
+                             "gradient: they are not taken together with grad_kernel")
+        if not clips:
+            raise ValueError("no clips")
+        if not all(c.dtype in (torch.float32, torch.float64) for c in clips):
+            raise TypeError("resample_varispeed: grad_kernel needs float32 or float64 clips (integer types have no gradient), "
+                            f"not {clips[0].dtype}")
+        why = _varispeed_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
+        if why:
+            raise RuntimeError(why)
+        if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
+            ratios = [float(r) for r in io_ratios]
+            y = _varispeed_autograd_fns()[0].apply(plan, kernel, grad_kernel, ratios, *clips)
+            n_out = [plan.vr_out_len(int(c.shape[0]), r) for c, r in zip(clips, ratios)]
+            return _split(y, n_out, [c.ndim == 1 for c in clips])
+    elif torch.is_grad_enabled() and any(c.requires_grad for c in clips):
         raise RuntimeError("resample_varispeed: no gradient is served for per-clip rates (the adjoint kernels take constant-rate "
                            "plans); detach the clips or call it under torch.no_grad()")
     job = RaggedJob(plan, clips, kernel=kernel, dither=dither, dither_seed=dither_seed, clip_counter=clip_counter,
                     io_ratios=io_ratios)
     job.launch()
     return job.outputs()
+
+
+def _varispeed_adjoint_refusal(plan, elem, kernel):
+    """The C entry's own refusal of (plan, element type, selector) for a varispeed gradient, or None: asked with an empty
+    job, so that a forward that could not be differentiated fails when it is called, not in the middle of backward."""
+    try:
+        plan.run_vr_ragged_adjoint(None, None, elem, 0, np.zeros((0, 4), np.int64), np.zeros(0), (0, 0), (0, 0), kernel=kernel)
+    except RuntimeError as e:
+        return str(e)
+    return None
+
+
+def _varispeed_adjoint_plain(plan, gys, in_frames, io_ratios, kernel):
+    """`resample_varispeed_adjoint` proper: the one C call, without autograd.  -> packed gx [sum(in_frames), channels]"""
+    import torch
+    if not gys:
+        raise ValueError("no clips")
+    if len(gys) != len(in_frames) or len(gys) != len(io_ratios):
+        raise ValueError("one in_frames entry and one io ratio per cotangent clip")
+    device, dtype = gys[0].device, gys[0].dtype
+    ch = 1 if gys[0].ndim == 1 else gys[0].shape[1]
+    for g in gys:
+        if g.device != device or g.dtype != dtype or g.ndim not in (1, 2) or (1 if g.ndim == 1 else g.shape[1]) != ch:
+            raise ValueError("clips of one job share device, dtype and channel count; each is [frames] or [frames, channels]")
+    if not gys[0].is_cuda:
+        raise RuntimeError("resample_varispeed_adjoint needs device tensors (soxr_amd has no CPU fallback)")
+    elem, es = _dev._torch_elem(dtype), gys[0].element_size()
+    keep = [g if g.is_contiguous() else g.contiguous() for g in gys]  # (a strided clip is the one case that is copied)
+    n_y, n_x = [int(g.shape[0]) for g in keep], [int(n) for n in in_frames]
+    gx = torch.empty((sum(n_x), ch), dtype=dtype, device=device)
+    ptrs = [g.data_ptr() for g in keep if g.shape[0] > 0]   # (an empty tensor has no storage address)
+    base = min(ptrs) if ptrs else gx.data_ptr()
+    gy_off = np.array([(g.data_ptr() - base) // es if g.shape[0] > 0 else 0 for g in keep], dtype=np.int64)
+    gx_off = np.concatenate([[0], np.cumsum(n_x)[:-1]]).astype(np.int64) * ch
+    table = np.ascontiguousarray(np.stack([gy_off, n_y, gx_off, n_x], axis=1), dtype=np.int64)
+    plan.run_vr_ragged_adjoint(base, gx.data_ptr(), elem, ch, table, [float(r) for r in io_ratios], (ch, 1), (ch, 1),
+                               stream=torch.cuda.current_stream(device).cuda_stream, kernel=kernel)
+    return gx
+
+
+_VARISPEED_AUTOGRAD = None
+
+
+def _varispeed_autograd_fns():
+    """The torch.autograd.Function pair over a batch with a rate per clip, shaped like `_ragged_autograd_fns`: each takes
+    the clips as separate inputs and returns ONE packed tensor, so a backward is one launch — the forward's backward is the
+    variable-rate ragged adjoint, the adjoint's backward the variable-rate forward on the exact engine, sliced to the
+    cotangents' lengths: differentiable to any order."""
+    global _VARISPEED_AUTOGRAD
+    if _VARISPEED_AUTOGRAD is not None:
+        return _VARISPEED_AUTOGRAD
+    import torch
+
+    class VarispeedFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, kernel, grad_kernel, ratios, *clips):
+            job = RaggedJob(plan, [c.detach() for c in clips], kernel=kernel, io_ratios=ratios)
+            job.launch()
+            ctx.plan, ctx.grad_kernel, ctx.ratios, ctx.n_in, ctx.n_out = plan, grad_kernel, ratios, job.n_in, job.n_out
+            ctx.monos = [c.ndim == 1 for c in clips]
+            return job.y
+
+        @staticmethod
+        def backward(ctx, gy):
+            gys = _split(gy.contiguous(), ctx.n_out, [False] * len(ctx.n_out))
+            gxs = resample_varispeed_adjoint(ctx.plan, gys, ctx.n_in, ctx.ratios, kernel=ctx.grad_kernel)
+            need = ctx.needs_input_grad[4:]
+            return (None, None, None, None) + tuple((g[:, 0] if mono else g) if nd else None
+                                                    for g, mono, nd in zip(gxs, ctx.monos, need))
+
+    class VarispeedAdjointFn(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, plan, in_frames, ratios, kernel, *gys):
+            ctx.plan, ctx.kernel, ctx.ratios, ctx.n_x = plan, kernel, ratios, [int(n) for n in in_frames]
+            ctx.n_y, ctx.monos = [int(g.shape[0]) for g in gys], [g.ndim == 1 for g in gys]
+            return _varispeed_adjoint_plain(plan, [g.detach() for g in gys], in_frames, ratios, kernel)
+
+        @staticmethod
+        def backward(ctx, ggx):  # (the varispeed forward on the exact engine; its own gradient is this adjoint again)
+            xs = _split(ggx.contiguous(), ctx.n_x, [False] * len(ctx.n_x))
+            ys = resample_varispeed(ctx.plan, xs, ctx.ratios, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
+            need = ctx.needs_input_grad[4:]
+            return (None, None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
+                                                    for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
+
+    _VARISPEED_AUTOGRAD = (VarispeedFn, VarispeedAdjointFn)
+    return _VARISPEED_AUTOGRAD
+
+
+def resample_varispeed_adjoint(plan, gys, in_frames, io_ratios, kernel=_n.KERNEL_AUTO):
+    """The transposed operator of `resample_varispeed`, ONE launch for all clips: gx[c] = A_c^T gys[c], A_c the resample of
+    in_frames[c] input frames at io_ratios[c] that `resample_varispeed` computes on the variable-rate `plan` (what the
+    backward of `resample_varispeed(..., grad_kernel=KERNEL_ADJOINT)` runs; the A^T an iterative solver needs).
+
+    gys : list of [frames] / [frames, channels] float32 / float64 device tensors of one device, dtype and channel count,
+          clip c with at most plan.vr_out_len(in_frames[c], io_ratios[c]) frames (a truncated cotangent).  They are read
+          where they lie (a non-contiguous one is copied).
+    Returns per-clip views ([in_frames[c]] or [in_frames[c], channels], as gys[c]) of one packed
+    [sum(in_frames), channels] buffer; every element is written.  The coefficients are the forward's own, each element is
+    one fma chain over ascending output index: bitwise reproducible, each clip with the bits of the clip run alone; a
+    non-finite cotangent sample reaches the frames of its true support only.  KERNEL_AUTO and KERNEL_ADJOINT run the same
+    launch; every other selector is refused by name.  On the current torch stream, asynchronously.  Differentiable: its
+    backward is the varispeed forward on the exact engine, sliced to the cotangents' lengths."""
+    import torch
+    monos = [g.ndim == 1 for g in gys]
+    ratios = [float(r) for r in io_ratios]
+    if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
+        gx = _varispeed_autograd_fns()[1].apply(plan, [int(n) for n in in_frames], ratios, kernel, *gys)
+    else:
+        gx = _varispeed_adjoint_plain(plan, list(gys), in_frames, ratios, kernel)
+    return _split(gx, [int(n) for n in in_frames], monos)
 
 
 def _split(packed, lengths, monos):
