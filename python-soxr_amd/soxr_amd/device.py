@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _native as _n
 from . import _quality_to_enum
+from ._job import make_job as _make_job, table_job as _table_job, refusal as _refusal
 from ._native import (KERNEL_AUTO, KERNEL_GATHER, KERNEL_TILE, KERNEL_TILE_VALU, KERNEL_TILE_MFMA,  # noqa: F401
                       KERNEL_FFT, KERNEL_EXACT, KERNEL_WAVE_DOT, KERNEL_FFT_F64, KERNEL_FFT_PCM, KERNEL_ADJOINT,
                       KERNEL_ADJOINT_FFT, KERNEL_ADJOINT_TWO_STAGE, KERNEL_ADJOINT_AUTO)
@@ -71,15 +72,11 @@ class Plan:
             out_strides, stream=None, kernel=_n.KERNEL_AUTO, in_abs0=0, out_k0=0, clip_counter=None,
             dither=False, dither_seed=0):
         """Raw launch: device pointers (ints), strides = (clip, frame, channel) in elements."""
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = in_ptr, out_ptr, elem, kernel
-        j.n_clips, j.n_channels = n_clips, n_channels
-        j.in_clip_stride, j.in_frame_stride, j.in_chan_stride = in_strides
-        j.out_clip_stride, j.out_frame_stride, j.out_chan_stride = out_strides
-        j.in_abs0, j.in_frames, j.out_k0, j.out_frames = in_abs0, in_frames, out_k0, out_frames
-        j.clip_counter = clip_counter
-        j.dither, j.dither_seed = int(bool(dither)), dither_seed
-        _n.check(_n.lib.hipsoxr_run_device(self._h, _C.byref(j), stream))
+        j = _make_job(in_ptr, out_ptr, elem, kernel, n_clips, n_channels, in_strides, out_strides, in_frames, out_frames,
+                      in_abs0, out_k0, clip_counter, dither, dither_seed)
+        err = _n.lib.hipsoxr_run_device(self._h, j, stream)  # (ctypes passes the struct by reference: argtypes says POINTER(Job))
+        if err:
+            _n.check(err)
 
     def run_adjoint(self, gy_ptr, gx_ptr, elem, n_clips, n_channels, gy_frames, gx_frames, gy_strides, gx_strides,
                     stream=None, kernel=_n.KERNEL_AUTO, clip_table=None):
@@ -87,13 +84,8 @@ class Plan:
         `run(..., kernel=KERNEL_EXACT)` computes — gy has gy_frames <= out_len(gx_frames) frames, gx has gx_frames.
         Device pointers (ints), strides = (clip, frame, channel) in elements.  float32 / float64, exact-bank plans;
         kernel=KERNEL_ADJOINT: every constant-rate plan, interpolated-phase plans included."""
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
-        j.n_clips, j.n_channels = n_clips, n_channels
-        j.in_clip_stride, j.in_frame_stride, j.in_chan_stride = gy_strides
-        j.out_clip_stride, j.out_frame_stride, j.out_chan_stride = gx_strides
-        j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, gy_frames, 0, gx_frames
-        j.clip_table = clip_table
+        j = _make_job(gy_ptr, gx_ptr, elem, kernel, n_clips, n_channels, gy_strides, gx_strides, gy_frames, gx_frames,
+                      clip_table=clip_table)
         _n.check(_n.lib.hipsoxr_run_device_adjoint(self._h, _C.byref(j), stream))
 
     def run_adjoint_ragged(self, gy_ptr, gx_ptr, elem, n_channels, table, gy_strides, gx_strides, stream=None,
@@ -102,18 +94,9 @@ class Plan:
         all clips.  table: int64 host array [n_clips, 4] of rows (gy offset, n_y, gx offset, n_x), offsets in elements
         from gy_ptr / gx_ptr, n_y <= out_len(n_x) per clip; table_dev: a device copy of it (pointer), or None = uploaded
         in stream order.  strides = (frame, channel) in elements.  Selectors as for `run_adjoint`."""
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
-        n = t.shape[0]
-        if n == 0:  # (an empty array has no address worth passing: the entry refuses a NULL table)
-            t = np.zeros((1, 4), np.int64)
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
-        j.n_clips, j.n_channels = n, n_channels
-        j.in_frame_stride, j.in_chan_stride = gy_strides
-        j.out_frame_stride, j.out_chan_stride = gx_strides
-        j.in_abs0, j.out_k0 = 0, 0
-        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
-        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
+        t, n, n_y, n_x, _ = _table_job(table)
+        j = _make_job(gy_ptr, gx_ptr, elem, kernel, n, n_channels, gy_strides, gx_strides, n_y, n_x,
+                      clip_table=t.ctypes.data, clip_table_dev=table_dev)
         _n.check(_n.lib.hipsoxr_run_device_adjoint_ragged(self._h, _C.byref(j), stream))
 
     def run_vr_ragged(self, in_ptr, out_ptr, elem, n_channels, table, io_ratios, in_strides, out_strides, stream=None,
@@ -124,23 +107,10 @@ class Plan:
         out_ptr, n_out <= vr_out_len(n_in, io_ratios[c]) per clip; table_dev: a device copy of it (pointer), or None =
         uploaded in stream order.  strides = (frame, channel) in elements.  KERNEL_AUTO, KERNEL_EXACT and KERNEL_GATHER
         all run the exact engine: each clip has the bits of a variable-rate stream set to its ratio and fed the clip."""
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
-        r = np.ascontiguousarray(io_ratios, dtype=np.float64).reshape(-1)
-        n = t.shape[0]
-        if r.shape[0] != n:
-            raise ValueError("one io ratio per clip")
-        if n == 0:  # (an empty array has no address worth passing: the entry refuses NULL tables)
-            t, r = np.zeros((1, 4), np.int64), np.ones(1, np.float64)
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = in_ptr, out_ptr, elem, kernel
-        j.n_clips, j.n_channels = n, n_channels
-        j.in_frame_stride, j.in_chan_stride = in_strides
-        j.out_frame_stride, j.out_chan_stride = out_strides
-        j.in_abs0, j.out_k0 = 0, 0
-        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
-        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
-        j.clip_counter = clip_counter
-        j.dither, j.dither_seed = int(bool(dither)), int(dither_seed) & 0xFFFFFFFF
+        t, n, n_in, n_out, r = _table_job(table, io_ratios)
+        j = _make_job(in_ptr, out_ptr, elem, kernel, n, n_channels, in_strides, out_strides, n_in, n_out,
+                      clip_counter=clip_counter, dither=dither, dither_seed=dither_seed,
+                      clip_table=t.ctypes.data, clip_table_dev=table_dev)
         _n.check(_n.lib.hipsoxr_run_device_vr_ragged(self._h, _C.byref(j), r.ctypes.data, stream))
 
     def run_vr_ragged_adjoint(self, gy_ptr, gx_ptr, elem, n_channels, table, io_ratios, gy_strides, gx_strides, stream=None,
@@ -151,21 +121,9 @@ class Plan:
         n_y <= vr_out_len(n_x, io_ratios[c]) per clip; table_dev: a device copy of it (pointer), or None = uploaded in
         stream order.  strides = (frame, channel) in elements.  float32 / float64; KERNEL_AUTO and KERNEL_ADJOINT run
         the same launch."""
-        t = np.ascontiguousarray(table, dtype=np.int64).reshape(-1, 4)
-        r = np.ascontiguousarray(io_ratios, dtype=np.float64).reshape(-1)
-        n = t.shape[0]
-        if r.shape[0] != n:
-            raise ValueError("one io ratio per clip")
-        if n == 0:  # (an empty array has no address worth passing: the entry refuses NULL tables)
-            t, r = np.zeros((1, 4), np.int64), np.ones(1, np.float64)
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = gy_ptr, gx_ptr, elem, kernel
-        j.n_clips, j.n_channels = n, n_channels
-        j.in_frame_stride, j.in_chan_stride = gy_strides
-        j.out_frame_stride, j.out_chan_stride = gx_strides
-        j.in_abs0, j.out_k0 = 0, 0
-        j.in_frames, j.out_frames = (int(t[:n, 1].max()), int(t[:n, 3].max())) if n else (0, 0)
-        j.clip_table, j.clip_table_dev = t.ctypes.data, table_dev
+        t, n, n_y, n_x, r = _table_job(table, io_ratios)
+        j = _make_job(gy_ptr, gx_ptr, elem, kernel, n, n_channels, gy_strides, gx_strides, n_y, n_x,
+                      clip_table=t.ctypes.data, clip_table_dev=table_dev)
         _n.check(_n.lib.hipsoxr_run_device_vr_ragged_adjoint(self._h, _C.byref(j), r.ctypes.data, stream))
 
 
@@ -177,19 +135,13 @@ class PreparedJob:
 
     def __init__(self, plan, x, out, kernel=_n.KERNEL_AUTO, dither=False, clip_counter=None, dither_seed=0):
         import torch
-        x3 = x[None, :, None] if x.ndim == 1 else (x[None] if x.ndim == 2 else x)
-        o3 = out[None, :, None] if out.ndim == 1 else (out[None] if out.ndim == 2 else out)
+        x3, o3 = _as3(x), _as3(out)
         clips, frames, ch = x3.shape
         if tuple(o3.shape) != (clips, plan.out_len(frames), ch):
             raise ValueError("out has the wrong shape for this plan")
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = x3.data_ptr(), o3.data_ptr(), _torch_elem(x.dtype), kernel
-        j.n_clips, j.n_channels = clips, ch
-        j.in_clip_stride, j.in_frame_stride, j.in_chan_stride = x3.stride()
-        j.out_clip_stride, j.out_frame_stride, j.out_chan_stride = o3.stride()
-        j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, frames, 0, o3.shape[1]
-        j.clip_counter = clip_counter.data_ptr() if clip_counter is not None else None
-        j.dither, j.dither_seed = int(bool(dither)), int(dither_seed) & 0xFFFFFFFF
+        j = _make_job(x3.data_ptr(), o3.data_ptr(), _torch_elem(x.dtype), kernel, clips, ch, x3.stride(), o3.stride(),
+                      frames, o3.shape[1], clip_counter=clip_counter.data_ptr() if clip_counter is not None else None,
+                      dither=dither, dither_seed=dither_seed)
         self._job, self._ref = j, _C.byref(j)
         self._plan, self._keep = plan, (x, out, clip_counter)
         self._stream = torch.cuda.current_stream(x.device).cuda_stream
@@ -244,11 +196,7 @@ def _like_rank(t3, ndim):
 def _adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
     """The C entry's own refusal of (plan, element type, selector) for an adjoint job, or None: asked with an empty job, so
     that a forward that could not be differentiated fails when it is called, not in the middle of backward."""
-    try:
-        plan.run_adjoint(None, None, elem, 0, 0, 0, 0, (0, 0, 0), (0, 0, 0), kernel=kernel)
-    except RuntimeError as e:
-        return str(e)
-    return None
+    return _refusal(plan.run_adjoint, None, None, elem, 0, 0, 0, 0, (0, 0, 0), (0, 0, 0), kernel=kernel)
 
 
 def _adjoint_forward_kernel(kernel):
@@ -427,33 +375,21 @@ def _resample_plain(plan, x, out=None, kernel=_n.KERNEL_AUTO, dither=False, clip
     if not x.is_cuda:
         raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
     elem = _torch_elem(x.dtype)
-    x3 = x
-    if x.ndim == 1:
-        x3 = x[None, :, None]
-    elif x.ndim == 2:
-        x3 = x[None]
-    elif x.ndim != 3:
-        raise ValueError("Input must be 1-D, 2-D or 3-D")
+    x3 = _as3(x)
     clips, frames, ch = x3.shape
     n_out = plan.out_len(frames)
     if out is None:
-        out = torch.empty((clips, n_out, ch), dtype=x.dtype, device=x.device)
-        o3 = out
+        o3 = torch.empty((clips, n_out, ch), dtype=x.dtype, device=x.device)
     else:
-        o3 = out if out.ndim == 3 else (out[None, :, None] if out.ndim == 1 else out[None])
+        o3 = _as3(out)
         if tuple(o3.shape) != (clips, n_out, ch):
             raise ValueError(f"out has shape {tuple(out.shape)}, expected frames={n_out}")
     cc = clip_counter.data_ptr() if clip_counter is not None else None
     if n_out and clips and ch:
         stream = torch.cuda.current_stream(x.device).cuda_stream
         plan.run(x3.data_ptr(), o3.data_ptr(), elem, clips, ch, frames, n_out, tuple(x3.stride()),
-                 tuple(o3.stride()), stream=stream, kernel=kernel, clip_counter=cc, dither=dither,
-                 dither_seed=int(dither_seed) & 0xFFFFFFFF)
-    if x.ndim == 1:
-        return o3[0, :, 0]
-    if x.ndim == 2:
-        return o3[0]
-    return o3
+                 tuple(o3.stride()), stream=stream, kernel=kernel, clip_counter=cc, dither=dither, dither_seed=dither_seed)
+    return _like_rank(o3, x.ndim)
 
 
 class TensorStream:

@@ -32,6 +32,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
+from . import _job
 from . import _native as _n
 from . import device as _dev
 
@@ -162,14 +163,8 @@ class RaggedJob:
         import torch
         if not clips:
             raise ValueError("no clips")
-        device = clips[0].device
-        ch = 1 if clips[0].ndim == 1 else clips[0].shape[1]
-        for c in clips:
-            if c.device != device or c.dtype != clips[0].dtype or (1 if c.ndim == 1 else c.shape[1]) != ch or c.ndim not in (1, 2):
-                raise ValueError("clips of one job share device, dtype and channel count; each is [frames] or [frames, channels]")
-        es = clips[0].element_size()
-        keep = [c if c.is_contiguous() else c.contiguous() for c in clips]  # (a strided clip is the one case that is copied)
-        n_in = [int(c.shape[0]) for c in keep]
+        device, dtype, ch = _job.batch_check(clips)
+        n_in = [int(c.shape[0]) for c in clips]
         self._ratios = None
         if io_ratios is None:
             n_out = [plan.out_len(n) for n in n_in]
@@ -180,25 +175,14 @@ class RaggedJob:
             if self._ratios.shape[0] != len(clips):
                 raise ValueError("one io ratio per clip")
             n_out = [plan.vr_out_len(n, r) for n, r in zip(n_in, self._ratios)]
-        ptrs = [c.data_ptr() for c in keep if c.shape[0] > 0]   # (an empty tensor has no storage address)
-        self.y = torch.empty((sum(n_out), ch), dtype=keep[0].dtype, device=device)
-        base = min(ptrs) if ptrs else self.y.data_ptr()
-        in_off = np.array([(c.data_ptr() - base) // es if c.shape[0] > 0 else 0 for c in keep], dtype=np.int64)
-        out_off = np.concatenate([[0], np.cumsum(n_out)[:-1]]).astype(np.int64) * ch
-        self._table = np.ascontiguousarray(np.stack([in_off, n_in, out_off, n_out], axis=1), dtype=np.int64)
+        self.y = torch.empty((sum(n_out), ch), dtype=dtype, device=device)
+        base, keep, self._table = _job.clip_table(clips, n_out, ch, self.y.data_ptr())
         self._table_dev = torch.from_numpy(self._table).to(device)
         self.n_in, self.n_out, self._mono, self._keep = n_in, n_out, [c.ndim == 1 for c in clips], keep
-        j = _n.Job()
-        j.in_, j.out, j.elem, j.kernel = base, self.y.data_ptr(), _dev._torch_elem(keep[0].dtype), kernel
-        j.n_clips, j.n_channels = len(clips), ch
-        j.in_clip_stride = j.out_clip_stride = 0
-        j.in_frame_stride, j.in_chan_stride = ch, 1
-        j.out_frame_stride, j.out_chan_stride = ch, 1
-        j.in_abs0, j.in_frames, j.out_k0, j.out_frames = 0, max(n_in), 0, max(n_out)
-        j.clip_table, j.clip_table_dev = self._table.ctypes.data, self._table_dev.data_ptr()
-        j.dither = int(keep[0].dtype == torch.int16 if dither is None else bool(dither))
-        j.dither_seed = int(dither_seed) & 0xFFFFFFFF
-        j.clip_counter = clip_counter.data_ptr() if clip_counter is not None else None
+        j = _job.make_job(base, self.y.data_ptr(), _dev._torch_elem(dtype), kernel, len(clips), ch, (ch, 1), (ch, 1),
+                          max(n_in), max(n_out), clip_counter=clip_counter.data_ptr() if clip_counter is not None else None,
+                          dither=dtype == torch.int16 if dither is None else dither, dither_seed=dither_seed,
+                          clip_table=self._table.ctypes.data, clip_table_dev=self._table_dev.data_ptr())
         self._counter = clip_counter
         self._job, self._ref, self._plan = j, _C.byref(j), plan
         cur = torch.cuda.current_stream(device)
@@ -219,12 +203,7 @@ class RaggedJob:
             _n.check(_n.lib.hipsoxr_run_device(self._plan.handle, self._ref, self._stream))
 
     def outputs(self):
-        outs, pos = [], 0
-        for n, mono in zip(self.n_out, self._mono):
-            v = self.y[pos:pos + n]
-            outs.append(v[:, 0] if mono else v)
-            pos += n
-        return outs
+        return _split(self.y, self.n_out, self._mono)
 
 
 def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=None, dither_seed=0, clip_counter=None,
@@ -268,7 +247,7 @@ def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=Non
             raise RuntimeError(why)
         if torch.is_grad_enabled() and any(c.requires_grad for c in clips):
             ratios = [float(r) for r in io_ratios]
-            y = _varispeed_autograd_fns()[0].apply(plan, kernel, grad_kernel, ratios, *clips)
+            y = _ragged_autograd_fns()[0].apply(plan, kernel, grad_kernel, ratios, *clips)
             n_out = [plan.vr_out_len(int(c.shape[0]), r) for c, r in zip(clips, ratios)]
             return _split(y, n_out, [c.ndim == 1 for c in clips])
     elif torch.is_grad_enabled() and any(c.requires_grad for c in clips):
@@ -283,88 +262,8 @@ def resample_varispeed(plan, clips, io_ratios, kernel=_n.KERNEL_AUTO, dither=Non
 def _varispeed_adjoint_refusal(plan, elem, kernel):
     """The C entry's own refusal of (plan, element type, selector) for a varispeed gradient, or None: asked with an empty
     job, so that a forward that could not be differentiated fails when it is called, not in the middle of backward."""
-    try:
-        plan.run_vr_ragged_adjoint(None, None, elem, 0, np.zeros((0, 4), np.int64), np.zeros(0), (0, 0), (0, 0), kernel=kernel)
-    except RuntimeError as e:
-        return str(e)
-    return None
-
-
-def _varispeed_adjoint_plain(plan, gys, in_frames, io_ratios, kernel):
-    """`resample_varispeed_adjoint` proper: the one C call, without autograd.  -> packed gx [sum(in_frames), channels]"""
-    import torch
-    if not gys:
-        raise ValueError("no clips")
-    if len(gys) != len(in_frames) or len(gys) != len(io_ratios):
-        raise ValueError("one in_frames entry and one io ratio per cotangent clip")
-    device, dtype = gys[0].device, gys[0].dtype
-    ch = 1 if gys[0].ndim == 1 else gys[0].shape[1]
-    for g in gys:
-        if g.device != device or g.dtype != dtype or g.ndim not in (1, 2) or (1 if g.ndim == 1 else g.shape[1]) != ch:
-            raise ValueError("clips of one job share device, dtype and channel count; each is [frames] or [frames, channels]")
-    if not gys[0].is_cuda:
-        raise RuntimeError("resample_varispeed_adjoint needs device tensors (soxr_amd has no CPU fallback)")
-    elem, es = _dev._torch_elem(dtype), gys[0].element_size()
-    keep = [g if g.is_contiguous() else g.contiguous() for g in gys]  # (a strided clip is the one case that is copied)
-    n_y, n_x = [int(g.shape[0]) for g in keep], [int(n) for n in in_frames]
-    gx = torch.empty((sum(n_x), ch), dtype=dtype, device=device)
-    ptrs = [g.data_ptr() for g in keep if g.shape[0] > 0]   # (an empty tensor has no storage address)
-    base = min(ptrs) if ptrs else gx.data_ptr()
-    gy_off = np.array([(g.data_ptr() - base) // es if g.shape[0] > 0 else 0 for g in keep], dtype=np.int64)
-    gx_off = np.concatenate([[0], np.cumsum(n_x)[:-1]]).astype(np.int64) * ch
-    table = np.ascontiguousarray(np.stack([gy_off, n_y, gx_off, n_x], axis=1), dtype=np.int64)
-    plan.run_vr_ragged_adjoint(base, gx.data_ptr(), elem, ch, table, [float(r) for r in io_ratios], (ch, 1), (ch, 1),
-                               stream=torch.cuda.current_stream(device).cuda_stream, kernel=kernel)
-    return gx
-
-
-_VARISPEED_AUTOGRAD = None
-
-
-def _varispeed_autograd_fns():
-    """The torch.autograd.Function pair over a batch with a rate per clip, shaped like `_ragged_autograd_fns`: each takes
-    the clips as separate inputs and returns ONE packed tensor, so a backward is one launch — the forward's backward is the
-    variable-rate ragged adjoint, the adjoint's backward the variable-rate forward on the exact engine, sliced to the
-    cotangents' lengths: differentiable to any order."""
-    global _VARISPEED_AUTOGRAD
-    if _VARISPEED_AUTOGRAD is not None:
-        return _VARISPEED_AUTOGRAD
-    import torch
-
-    class VarispeedFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, plan, kernel, grad_kernel, ratios, *clips):
-            job = RaggedJob(plan, [c.detach() for c in clips], kernel=kernel, io_ratios=ratios)
-            job.launch()
-            ctx.plan, ctx.grad_kernel, ctx.ratios, ctx.n_in, ctx.n_out = plan, grad_kernel, ratios, job.n_in, job.n_out
-            ctx.monos = [c.ndim == 1 for c in clips]
-            return job.y
-
-        @staticmethod
-        def backward(ctx, gy):
-            gys = _split(gy.contiguous(), ctx.n_out, [False] * len(ctx.n_out))
-            gxs = resample_varispeed_adjoint(ctx.plan, gys, ctx.n_in, ctx.ratios, kernel=ctx.grad_kernel)
-            need = ctx.needs_input_grad[4:]
-            return (None, None, None, None) + tuple((g[:, 0] if mono else g) if nd else None
-                                                    for g, mono, nd in zip(gxs, ctx.monos, need))
-
-    class VarispeedAdjointFn(torch.autograd.Function):
-        @staticmethod
-        def forward(ctx, plan, in_frames, ratios, kernel, *gys):
-            ctx.plan, ctx.kernel, ctx.ratios, ctx.n_x = plan, kernel, ratios, [int(n) for n in in_frames]
-            ctx.n_y, ctx.monos = [int(g.shape[0]) for g in gys], [g.ndim == 1 for g in gys]
-            return _varispeed_adjoint_plain(plan, [g.detach() for g in gys], in_frames, ratios, kernel)
-
-        @staticmethod
-        def backward(ctx, ggx):  # (the varispeed forward on the exact engine; its own gradient is this adjoint again)
-            xs = _split(ggx.contiguous(), ctx.n_x, [False] * len(ctx.n_x))
-            ys = resample_varispeed(ctx.plan, xs, ctx.ratios, kernel=_n.KERNEL_EXACT, grad_kernel=ctx.kernel)
-            need = ctx.needs_input_grad[4:]
-            return (None, None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
-                                                    for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
-
-    _VARISPEED_AUTOGRAD = (VarispeedFn, VarispeedAdjointFn)
-    return _VARISPEED_AUTOGRAD
+    return _job.refusal(plan.run_vr_ragged_adjoint, None, None, elem, 0, np.zeros((0, 4), np.int64), np.zeros(0), (0, 0), (0, 0),
+                        kernel=kernel)
 
 
 def resample_varispeed_adjoint(plan, gys, in_frames, io_ratios, kernel=_n.KERNEL_AUTO):
@@ -381,14 +280,7 @@ def resample_varispeed_adjoint(plan, gys, in_frames, io_ratios, kernel=_n.KERNEL
     non-finite cotangent sample reaches the frames of its true support only.  KERNEL_AUTO and KERNEL_ADJOINT run the same
     launch; every other selector is refused by name.  On the current torch stream, asynchronously.  Differentiable: its
     backward is the varispeed forward on the exact engine, sliced to the cotangents' lengths."""
-    import torch
-    monos = [g.ndim == 1 for g in gys]
-    ratios = [float(r) for r in io_ratios]
-    if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
-        gx = _varispeed_autograd_fns()[1].apply(plan, [int(n) for n in in_frames], ratios, kernel, *gys)
-    else:
-        gx = _varispeed_adjoint_plain(plan, list(gys), in_frames, ratios, kernel)
-    return _split(gx, [int(n) for n in in_frames], monos)
+    return _packed_adjoint(plan, gys, in_frames, kernel, [float(r) for r in io_ratios])
 
 
 def _split(packed, lengths, monos):
@@ -404,38 +296,36 @@ def _split(packed, lengths, monos):
 def _ragged_adjoint_refusal(plan, elem, kernel=_n.KERNEL_AUTO):
     """The ragged C entry's own refusal of (plan, element type, selector), or None: asked with an empty job, as
     `device._adjoint_refusal` asks the equal-length entry."""
-    try:
-        plan.run_adjoint_ragged(None, None, elem, 0, np.zeros((0, 4), np.int64), (0, 0), (0, 0), kernel=kernel)
-    except RuntimeError as e:
-        return str(e)
-    return None
+    return _job.refusal(plan.run_adjoint_ragged, None, None, elem, 0, np.zeros((0, 4), np.int64), (0, 0), (0, 0), kernel=kernel)
 
 
-def _ragged_adjoint_plain(plan, gys, in_frames, kernel):
-    """`resample_ragged_adjoint` proper: the one C call, without autograd.  -> packed gx [sum(in_frames), channels]"""
+def _ragged_adjoint_plain(plan, gys, in_frames, kernel, ratios=None):
+    """`resample_ragged_adjoint` (ratios=None) and `resample_varispeed_adjoint` (a rate per clip) proper: the one C call,
+    without autograd.  -> packed gx [sum(in_frames), channels]"""
     import torch
+    vr = ratios is not None
+    if vr:  # (each entry keeps its own words)
+        miscounted = "one in_frames entry and one io ratio per cotangent clip"
+        on_host = "resample_varispeed_adjoint needs device tensors (soxr_amd has no CPU fallback)"
+    else:
+        miscounted = "one in_frames entry per cotangent clip"
+        on_host = "resample_tensor needs a device tensor (soxr_amd has no CPU fallback)"
     if not gys:
         raise ValueError("no clips")
-    if len(gys) != len(in_frames):
-        raise ValueError("one in_frames entry per cotangent clip")
-    device, dtype = gys[0].device, gys[0].dtype
-    ch = 1 if gys[0].ndim == 1 else gys[0].shape[1]
-    for g in gys:
-        if g.device != device or g.dtype != dtype or g.ndim not in (1, 2) or (1 if g.ndim == 1 else g.shape[1]) != ch:
-            raise ValueError("clips of one job share device, dtype and channel count; each is [frames] or [frames, channels]")
+    if len(gys) != len(in_frames) or (vr and len(gys) != len(ratios)):
+        raise ValueError(miscounted)
+    device, dtype, ch = _job.batch_check(gys)
     if not gys[0].is_cuda:
-        raise RuntimeError("resample_tensor needs a device tensor (soxr_amd has no CPU fallback)")
-    elem, es = _dev._torch_elem(dtype), gys[0].element_size()
-    keep = [g if g.is_contiguous() else g.contiguous() for g in gys]  # (a strided clip is the one case that is copied)
-    n_y, n_x = [int(g.shape[0]) for g in keep], [int(n) for n in in_frames]
+        raise RuntimeError(on_host)
+    elem, n_x = _dev._torch_elem(dtype), [int(n) for n in in_frames]
     gx = torch.empty((sum(n_x), ch), dtype=dtype, device=device)
-    ptrs = [g.data_ptr() for g in keep if g.shape[0] > 0]   # (an empty tensor has no storage address)
-    base = min(ptrs) if ptrs else gx.data_ptr()
-    gy_off = np.array([(g.data_ptr() - base) // es if g.shape[0] > 0 else 0 for g in keep], dtype=np.int64)
-    gx_off = np.concatenate([[0], np.cumsum(n_x)[:-1]]).astype(np.int64) * ch
-    table = np.ascontiguousarray(np.stack([gy_off, n_y, gx_off, n_x], axis=1), dtype=np.int64)
-    plan.run_adjoint_ragged(base, gx.data_ptr(), elem, ch, table, (ch, 1), (ch, 1),
-                            stream=torch.cuda.current_stream(device).cuda_stream, kernel=kernel)
+    base, keep, table = _job.clip_table(gys, n_x, ch, gx.data_ptr())
+    stream = torch.cuda.current_stream(device).cuda_stream
+    if vr:
+        plan.run_vr_ragged_adjoint(base, gx.data_ptr(), elem, ch, table, [float(r) for r in ratios], (ch, 1), (ch, 1),
+                                   stream=stream, kernel=kernel)
+    else:
+        plan.run_adjoint_ragged(base, gx.data_ptr(), elem, ch, table, (ch, 1), (ch, 1), stream=stream, kernel=kernel)
     return gx
 
 
@@ -443,10 +333,11 @@ _RAGGED_AUTOGRAD = None
 
 
 def _ragged_autograd_fns():
-    """The torch.autograd.Function pair over a ragged batch (built on first use, as `device._autograd_fns`).  Each takes
-    the clips as separate inputs and returns ONE packed tensor, so autograd hands back one packed cotangent and a backward
-    is one ragged launch: the forward's backward is the ragged adjoint, the adjoint's backward the ragged forward on the
-    exact engine — differentiable to any order."""
+    """The torch.autograd.Function pair over a ragged batch (built on first use, as `device._autograd_fns`), at the plan's
+    rate (ratios=None) or at a rate per clip.  Each takes the clips as separate inputs and returns ONE packed tensor, so
+    autograd hands back one packed cotangent and a backward is one ragged launch: the forward's backward is the ragged
+    adjoint, the adjoint's backward the ragged forward on the engine the adjoint ran on (`device._adjoint_forward_kernel`),
+    sliced to the cotangents' lengths — differentiable to any order."""
     global _RAGGED_AUTOGRAD
     if _RAGGED_AUTOGRAD is not None:
         return _RAGGED_AUTOGRAD
@@ -454,38 +345,53 @@ def _ragged_autograd_fns():
 
     class RaggedFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, plan, kernel, grad_kernel, *clips):
-            job = RaggedJob(plan, [c.detach() for c in clips], kernel=kernel)
+        def forward(ctx, plan, kernel, grad_kernel, ratios, *clips):
+            job = RaggedJob(plan, [c.detach() for c in clips], kernel=kernel, io_ratios=ratios)
             job.launch()
-            ctx.plan, ctx.grad_kernel, ctx.n_in, ctx.n_out = plan, grad_kernel, job.n_in, job.n_out
+            ctx.plan, ctx.grad_kernel, ctx.ratios, ctx.n_in, ctx.n_out = plan, grad_kernel, ratios, job.n_in, job.n_out
             ctx.monos = [c.ndim == 1 for c in clips]
             return job.y
 
         @staticmethod
         def backward(ctx, gy):
             gys = _split(gy.contiguous(), ctx.n_out, [False] * len(ctx.n_out))
-            gxs = resample_ragged_adjoint(ctx.plan, gys, ctx.n_in, kernel=ctx.grad_kernel)
-            need = ctx.needs_input_grad[3:]
-            return (None, None, None) + tuple((g[:, 0] if mono else g) if nd else None
-                                              for g, mono, nd in zip(gxs, ctx.monos, need))
+            gxs = _packed_adjoint(ctx.plan, gys, ctx.n_in, ctx.grad_kernel, ctx.ratios)
+            need = ctx.needs_input_grad[4:]
+            return (None, None, None, None) + tuple((g[:, 0] if mono else g) if nd else None
+                                                    for g, mono, nd in zip(gxs, ctx.monos, need))
 
     class RaggedAdjointFn(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, plan, in_frames, kernel, *gys):
-            ctx.plan, ctx.kernel, ctx.n_x = plan, kernel, [int(n) for n in in_frames]
+        def forward(ctx, plan, in_frames, ratios, kernel, *gys):
+            ctx.plan, ctx.kernel, ctx.ratios, ctx.n_x = plan, kernel, ratios, [int(n) for n in in_frames]
             ctx.n_y, ctx.monos = [int(g.shape[0]) for g in gys], [g.ndim == 1 for g in gys]
-            return _ragged_adjoint_plain(plan, [g.detach() for g in gys], in_frames, kernel)
+            return _ragged_adjoint_plain(plan, [g.detach() for g in gys], in_frames, kernel, ratios)
 
         @staticmethod
-        def backward(ctx, ggx):  # (the ragged forward on the exact engine; its own gradient is this adjoint again, same selector)
+        def backward(ctx, ggx):  # (the forward on the engine the adjoint ran on; its own gradient is this adjoint again, same selector)
             xs = _split(ggx.contiguous(), ctx.n_x, [False] * len(ctx.n_x))
-            ys = resample_ragged(ctx.plan, xs, kernel=_dev._adjoint_forward_kernel(ctx.kernel), grad_kernel=ctx.kernel)
-            need = ctx.needs_input_grad[3:]
-            return (None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
-                                              for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
+            forward = _dev._adjoint_forward_kernel(ctx.kernel)
+            if ctx.ratios is None:
+                ys = resample_ragged(ctx.plan, xs, kernel=forward, grad_kernel=ctx.kernel)
+            else:
+                ys = resample_varispeed(ctx.plan, xs, ctx.ratios, kernel=forward, grad_kernel=ctx.kernel)
+            need = ctx.needs_input_grad[4:]
+            return (None, None, None, None) + tuple((y[:n, 0] if mono else y[:n]) if nd else None
+                                                    for y, n, mono, nd in zip(ys, ctx.n_y, ctx.monos, need))
 
     _RAGGED_AUTOGRAD = (RaggedFn, RaggedAdjointFn)
     return _RAGGED_AUTOGRAD
+
+
+def _packed_adjoint(plan, gys, in_frames, kernel, ratios):
+    """`resample_ragged_adjoint` (ratios=None) / `resample_varispeed_adjoint`: through autograd where a cotangent asks for it"""
+    import torch
+    monos, n_x = [g.ndim == 1 for g in gys], [int(n) for n in in_frames]
+    if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
+        gx = _ragged_autograd_fns()[1].apply(plan, n_x, ratios, kernel, *gys)
+    else:
+        gx = _ragged_adjoint_plain(plan, list(gys), in_frames, kernel, ratios)
+    return _split(gx, n_x, monos)
 
 
 def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
@@ -512,13 +418,7 @@ def resample_ragged_adjoint(plan, gys, in_frames, kernel=_n.KERNEL_AUTO):
     their number: within the form's 1e-6 / 2e-9 class of the clip alone), every other clip in ONE ragged launch of the
     exact adjoint (the bits of KERNEL_ADJOINT on the clip alone; a clip without cotangent gets zeros).  Its backward is
     the ragged forward under KERNEL_AUTO."""
-    import torch
-    monos = [g.ndim == 1 for g in gys]
-    if torch.is_grad_enabled() and any(g.requires_grad for g in gys):
-        gx = _ragged_autograd_fns()[1].apply(plan, [int(n) for n in in_frames], kernel, *gys)
-    else:
-        gx = _ragged_adjoint_plain(plan, list(gys), in_frames, kernel)
-    return _split(gx, [int(n) for n in in_frames], monos)
+    return _packed_adjoint(plan, gys, in_frames, kernel, None)
 
 
 def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AUTO):
@@ -545,7 +445,7 @@ def resample_ragged(plan, clips, kernel=_n.KERNEL_AUTO, grad_kernel=_n.KERNEL_AU
         why = _ragged_adjoint_refusal(plan, _dev._torch_elem(clips[0].dtype), grad_kernel)
         if why:
             raise RuntimeError(why)
-        y = _ragged_autograd_fns()[0].apply(plan, kernel, grad_kernel, *clips)
+        y = _ragged_autograd_fns()[0].apply(plan, kernel, grad_kernel, None, *clips)
         n_out = [plan.out_len(int(c.shape[0])) for c in clips]
         return _split(y, n_out, [c.ndim == 1 for c in clips])
     job = RaggedJob(plan, clips, kernel=kernel)
@@ -734,17 +634,11 @@ class _HostPipe:
             e_in = torch.cuda.Event(); e_in.record(self.sin)
         st.ev_free_in[s] = e_in
         # the block's table: clips end to end in the packed device buffers (device copy uploaded by the library)
-        ni = np.array([st.n_in[i] for i in b], np.int64); no = np.array([st.n_out[i] for i in b], np.int64)
-        table = np.ascontiguousarray(np.stack([np.concatenate([[0], np.cumsum(ni)[:-1]]) * ch, ni,
-                                               np.concatenate([[0], np.cumsum(no)[:-1]]) * ch, no], axis=1), dtype=np.int64)
-        j = _n.Job()
-        j.in_, j.out = self.dev_in[s].data_ptr(), self.dev_out[s].data_ptr()
-        j.elem, j.kernel = _dev._torch_elem(self.tdtype), self.kernel
-        j.n_clips, j.n_channels = len(b), ch
-        j.in_frame_stride, j.in_chan_stride, j.out_frame_stride, j.out_chan_stride = ch, 1, ch, 1
-        j.in_frames, j.out_frames = int(ni.max()), int(no.max())
-        j.clip_table, j.clip_table_dev = table.ctypes.data, None
-        j.dither = int(self.tdtype == torch.int16)
+        ni, no = [st.n_in[i] for i in b], [st.n_out[i] for i in b]
+        table = _job.table_rows(_job.packed_offsets(ni, ch), ni, no, ch)
+        j = _job.make_job(self.dev_in[s].data_ptr(), self.dev_out[s].data_ptr(), _dev._torch_elem(self.tdtype), self.kernel,
+                          len(b), ch, (ch, 1), (ch, 1), max(ni), max(no), dither=self.tdtype == torch.int16,
+                          clip_table=table.ctypes.data)
         if self.pinned_results:
             st.own_out[k] = torch.empty(max(tot_out, 1), dtype=self.tdtype, pin_memory=True)
         else:
